@@ -27,9 +27,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# engines on several host threads launch concurrently only as far as their streams get hardware queues of their own (the
-# runtime's default is 4 per process; a persistent climb kernel holds its queue for a whole sweep: profiles/r3/concurrent_climbs.txt)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 I8_PEAK_TOPS = 5000.0      # dense int8 MFMA, 2 x bf16 (MI355X_MICROARCH.md, matrix cores)
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 measured copy)
@@ -217,6 +214,9 @@ def main():
     ap.add_argument("--bootstrap-replicates", type=int, default=1000,
                     help="samples of the online phase whose trees are refined afterwards (IQTree::optimizeBootTrees), "
                          "sharded over the GPUs; capped by --ufboot-samples (0 = skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what rank 0's last timed step returned (sweep_scan: insertion tests, shortest "
+                         "tree length of the sweep) as DIR/n_tests.npy and DIR/min_mp.npy (float64), to compare two builds")
     ap.add_argument("--random-start-leg", type=int, default=1,
                     help="1 = also run the climb / -bb flow from a random topology (a start tree that is not already SPR-optimal)")
     ap.add_argument("--legs-timeout", type=int, default=180,
@@ -249,6 +249,8 @@ def main():
                     help="bootstrap samples of the online UFBoot-MP leg (-bb): one pllOptimizeSprParsimony call with "
                          "saveCurrentTree after every insertion test, timed after the main metric (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     legs_wanted = set(x.strip() for x in args.legs.split(","))
     leg_on = lambda name: "all" in legs_wanted or name in legs_wanted
     # wall clock of the run, leg by leg (what the driver's own clock around this command is made of)
@@ -381,6 +383,11 @@ def main():
         tests += k
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step's return values, untimed; the inputs (seeded workload, start tree) are the same on every run
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "n_tests.npy"), np.array([k], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "min_mp.npy"), np.array([_best], dtype=np.float64))
     sched_us = (eng.get_option("sched_ticks") / 100.0, eng.get_option("sched_desc_ticks") / 100.0, eng.get_option("sched_levels"))
     st = eng.stats()
     eng.set_option("plan_cache", 1)

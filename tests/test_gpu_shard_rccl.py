@@ -106,7 +106,7 @@ if rank == 0:
 
 def _gpu_count():
     """GPUs a process started from here can use, asked of a CHILD process: no HIP call and no torch import in the pytest process
-    (a runtime started here at collection time would be running before mpboot_amd.engine exports GPU_MAX_HW_QUEUES; sysfs lists
+    (a runtime started here at collection time would hold the GPU for the whole pytest process; sysfs lists
     the host's GPUs, not the ones this container was given)"""
     probe = ("import torch\nok = 0\nfor i in range(torch.cuda.device_count()):\n    try:\n        torch.cuda.set_device(i); torch.zeros(1, device='cuda'); ok += 1\n"
              "    except Exception:\n        break\nprint(ok)")       # (device_count() can name GPUs of the host this container cannot open)

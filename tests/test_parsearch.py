@@ -102,7 +102,9 @@ infos = [run.round() for _ in range(3)]
 out = {"rank": run.rank, "lens": [_books(o)[0].tolist() for o in eng], "cnt": [_books(o)[1].tolist() for o in eng],
        "ties": [int(o.tie_state()) for o in eng], "adopted": [i["adopted"] for i in infos], "iterations": run.iterations,
        "best": run.best_score, "cands": [s.cands._scores for s in run.searches]}
-print("RESULT " + json.dumps(out), flush=True)
+# one file per rank: two ranks printing long lines into one pipe can interleave them
+with open(os.path.join(os.environ["MPF_OUT"], "result_%d.json" % run.rank), "w") as f:
+    json.dump(out, f)
 if ws > 1:
     dist.destroy_process_group()
 '''
@@ -117,17 +119,19 @@ def _free_port():
 def _run(nproc, tmp_path):
     script = tmp_path / "worker.py"
     script.write_text(WORKER)
-    env = dict(os.environ, MPF_ROOT=ROOT)
+    res_dir = tmp_path / ("results_%d" % nproc)
+    res_dir.mkdir()
+    env = dict(os.environ, MPF_ROOT=ROOT, MPF_OUT=str(res_dir))
     for attempt in range(2):
         cmd = [sys.executable, str(script)] if nproc == 1 else [
             sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
             "--master-port", str(_free_port()), str(script)]
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         # (the port was free when it was picked, not necessarily when the rendezvous bound it: one more try with another)
-        if out.returncode == 0 or nproc == 1 or "RESULT " in out.stdout:
+        if out.returncode == 0 or nproc == 1 or any(res_dir.iterdir()):
             break
     assert out.returncode == 0, out.stderr[-3000:]
-    return sorted((json.loads(l.split("RESULT ", 1)[1]) for l in out.stdout.splitlines() if "RESULT " in l), key=lambda r: r["rank"])
+    return sorted((json.loads(f.read_text()) for f in res_dir.glob("result_*.json")), key=lambda r: r["rank"])
 
 
 def test_two_gloo_ranks_do_what_two_workers_of_one_process_do(tmp_path):

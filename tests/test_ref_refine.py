@@ -1,28 +1,23 @@
 """oracle/_ref/pll_ref_driver `refine` (the reference's PLL parsimony code timed on one bootstrap-refinement replicate,
 bench.py's CPU side of the bootstrap metric) against the oracle: same re-weighted start length, same first-best climb.
-Only where the reference build exists (this container); the GPU box gets the prebuilt driver with the snapshot."""
+The driver's results for these cases are stored in tests/golden/ref_refine.json: the oracle is checked against them everywhere,
+and where the reference build exists the driver is run as well and must still produce them."""
+import json
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import ROOT, load_fixture
+from helpers import GOLDEN, ROOT, load_fixture
 
 DRV = os.path.join(ROOT, "oracle", "_ref", "pll_ref_driver")
 
 
-@pytest.mark.skipif(not os.access(DRV, os.X_OK), reason="reference build (oracle/_ref) not present")
-@pytest.mark.parametrize("name,seed", [("dna_48", 3), ("dna_ambig", 5), ("aa", 7)])
-def test_refine_matches_oracle(tmp_path, name, seed):
+def _driver_refine(tmp_path, fx, codes, w, back):
+    """(start length, final length, moves) of the driver's first-best climb under weights w"""
     from mpboot_amd import synth, trees
-    from oracle import pyoracle as po
-    fx = load_fixture(name)
-    codes = fx["codes_np"]
-    n, P = codes.shape
-    rng = np.random.default_rng(seed)
-    w = rng.multinomial(P, np.ones(P) / P).astype(np.int32)
-    back = np.array(fx["trees"][2]["back"], dtype=np.int32)
+    n = codes.shape[0]
     names = [f"t{i + 1}" for i in range(n)]
     aln = tmp_path / "a.phy"
     table, skip = (synth._DNA_CODE, "U?NOX") if fx["datatype"] == 0 else (synth._AA_CODE, "?*X")
@@ -39,6 +34,23 @@ def test_refine_matches_oracle(tmp_path, name, seed):
     tok = [l.split() for l in out.splitlines() if l.startswith("refined")][0]
     start, final, moves = int(tok[2]), int(tok[4]), int(tok[6])
     assert int([l.split() for l in out.splitlines() if l.startswith("final_check")][0][1]) == final
+    return start, final, moves
+
+
+@pytest.mark.parametrize("name,seed", [("dna_48", 3), ("dna_ambig", 5), ("aa", 7)])
+def test_refine_matches_oracle(tmp_path, name, seed):
+    from oracle import pyoracle as po
+    fx = load_fixture(name)
+    codes = fx["codes_np"]
+    P = codes.shape[1]
+    rng = np.random.default_rng(seed)
+    w = rng.multinomial(P, np.ones(P) / P).astype(np.int32)
+    back = np.array(fx["trees"][2]["back"], dtype=np.int32)
+    with open(os.path.join(GOLDEN, "ref_refine.json")) as f:
+        want = json.load(f)["%s:%d" % (name, seed)]
+    start, final, moves = want["start"], want["final"], want["moves"]
+    if os.access(DRV, os.X_OK):
+        assert _driver_refine(tmp_path, fx, codes, w, back) == (start, final, moves)
     o = po.Oracle(codes, w, datatype=fx["datatype"])
     assert o.score_tree(back) == start
     o.seed_ties(po.TIE_FIRST)

@@ -12,11 +12,9 @@ python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 600 $OUT/bench_default.err
 {
   echo "# independent C3 climbs from random trees on ONE GPU, one engine per host thread (tools/concurrent_climbs.py)"
-  for Q in 4 16; do
-    for M in 0 2; do
-      echo "## GPU_MAX_HW_QUEUES=$Q climb_device=$M climb_tile=4"
-      GPU_MAX_HW_QUEUES=$Q python tools/concurrent_climbs.py --engines 1,4,8,12,16 --opt climb_device=$M --opt climb_tile=4 2>&1 | tail -8
-    done
+  for M in 0 2; do
+    echo "## climb_device=$M climb_tile=4"
+    python tools/concurrent_climbs.py --engines 1,4,8,12,16 --opt climb_device=$M --opt climb_tile=4 2>&1 | tail -8
   done
 } > $OUT/concurrent_climbs.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/climb_trace -- python3 tools/climb_check.py --workload C3 --notrace > $OUT/climb_c3.txt 2> $OUT/climb_trace.err
