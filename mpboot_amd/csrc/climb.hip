@@ -1719,35 +1719,17 @@ template <int KS, int VW, bool GROUPS>
 hipError_t launch_g(hipStream_t st, const ClimbParams &p)
 {
   const size_t lds = lds_bytes<KS, VW>(p.nslots, p.batch_max, false);
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 || attr_dev != dev) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_climb<KS, VW, GROUPS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_dev = dev;
-  }
+  const hipError_t e = lds_opt_in<k_climb<KS, VW, GROUPS>>(160 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_climb<KS, VW, GROUPS>), dim3(p.groups ? p.groups : p.tiles), dim3(Cfg<KS, VW>::NT), lds, st, p);
   return hipGetLastError();
 }
 
 template <int KS, int VW>
-hipError_t launch_t(hipStream_t st, const ClimbParams &p)
-{
-  return p.groups && p.groups < p.tiles ? launch_g<KS, VW, true>(st, p) : launch_g<KS, VW, false>(st, p);
-}
-
-template <int KS, int VW>
 hipError_t launch_many_t(hipStream_t st, const ClimbParams *d_params, int n_climbs, size_t lds)
 {
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 || attr_dev != dev) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_climb_many<KS, VW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_dev = dev;
-  }
+  const hipError_t e = lds_opt_in<k_climb_many<KS, VW>>(160 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_climb_many<KS, VW>), dim3((unsigned)n_climbs), dim3(Cfg<KS, VW>::NT_MANY), lds, st, d_params);
   return hipGetLastError();
 }
@@ -1761,10 +1743,7 @@ int climb_tiles(const Geometry &g, int vw) { return (g.Wp + 16 * vw - 1) / (16 *
 size_t climb_lds_bytes(const Geometry &g, int n_taxa, int vw, int batch_max, bool many, bool word_major)
 {
   const uint32_t ns = slots_of(n_taxa), mb = (uint32_t)batch_max;
-  if (g.S == 4 && word_major && vw == 4) return lds_bytes<4, 1>(ns, mb, many);
-  if (g.S == 4) return vw == 1 ? lds_bytes<1, 1>(ns, mb, many) : vw == 2 ? lds_bytes<1, 2>(ns, mb, many) : vw == 4 ? lds_bytes<1, 4>(ns, mb, many) : lds_bytes<1, 8>(ns, mb, many);
-  if (g.S == 32) return lds_bytes<8, 1>(ns, mb, many);
-  return lds_bytes<5, 1>(ns, mb, many);
+  return dispatch_lane_shape(g.S, vw, word_major && vw == 4, [&](auto KS, auto VW) { return lds_bytes<KS, VW>(ns, mb, many); });
 }
 
 bool climb_supported(const Geometry &g, int n_taxa, int maxtrav, int batch_max)
@@ -1779,33 +1758,19 @@ bool climb_supported(const Geometry &g, int n_taxa, int maxtrav, int batch_max)
 
 hipError_t launch_climb(hipStream_t st, const Geometry &g, int vw, const ClimbParams &p, bool word_major)
 {
-  // (the word-major shape: 64-word tiles, a workgroup per tile)
-  if (g.S == 4 && word_major && vw == 4 && !(p.groups && p.groups < p.tiles)) return launch_g<4, 1, false>(st, p);
-  if (g.S == 4) {
-    if (vw == 1) return launch_t<1, 1>(st, p);
-    if (vw == 2) return launch_t<1, 2>(st, p);
-    if (vw == 8) return launch_t<1, 8>(st, p);
-    return launch_t<1, 4>(st, p);
-  }
-  if (g.S == 32) return launch_t<8, 1>(st, p);           // 32-state data: eight states per lane
-  return launch_t<5, 1>(st, p);
+  // (the word-major shape: 64-word tiles, a workgroup per tile -- grouped climbs take the quad shape on the same tiles)
+  const bool groups = p.groups && p.groups < p.tiles;
+  return dispatch_lane_shape(g.S, vw, word_major && vw == 4 && !groups, [&](auto KS, auto VW) {
+    if constexpr (KS == 4) return launch_g<KS, VW, false>(st, p);
+    else return groups ? launch_g<KS, VW, true>(st, p) : launch_g<KS, VW, false>(st, p);
+  });
 }
 
 hipError_t launch_climb_many(hipStream_t st, const Geometry &g, int vw, const ClimbParams *d_params, int n_climbs, size_t lds, bool word_major)
 {
   if (n_climbs <= 0) return hipSuccess;
-  if (g.S == 4 && word_major) {
-    if (vw != 4) return hipErrorInvalidValue;               // (64-word tiles: a word per lane)
-    return launch_many_t<4, 1>(st, d_params, n_climbs, lds);
-  }
-  if (g.S == 4) {
-    if (vw == 1) return launch_many_t<1, 1>(st, d_params, n_climbs, lds);
-    if (vw == 2) return launch_many_t<1, 2>(st, d_params, n_climbs, lds);
-    if (vw == 8) return launch_many_t<1, 8>(st, d_params, n_climbs, lds);
-    return launch_many_t<1, 4>(st, d_params, n_climbs, lds);
-  }
-  if (g.S == 32) return launch_many_t<8, 1>(st, d_params, n_climbs, lds);
-  return launch_many_t<5, 1>(st, d_params, n_climbs, lds);
+  if (g.S == 4 && word_major && vw != 4) return hipErrorInvalidValue;   // (64-word tiles: a word per lane)
+  return dispatch_lane_shape(g.S, vw, word_major, [&](auto KS, auto VW) { return launch_many_t<KS, VW>(st, d_params, n_climbs, lds); });
 }
 
 }  // namespace mpf

@@ -719,27 +719,21 @@ template <int KS, int VW>
 constexpr bool g_tight() { return (KS == 1 && VW <= 4) || KS == 4; }
 
 template <int KS, int VW>
-const void *g_kernel()
+constexpr auto g_kernel()
 {
   // (one of the two per shape: the other would be compiled for nothing -- and the tight form of the wide shapes spills)
-  if constexpr (g_tight<KS, VW>()) return reinterpret_cast<const void *>(&k_grow_tight<KS, VW>);
-  else return reinterpret_cast<const void *>(&k_grow<KS, VW>);
+  if constexpr (g_tight<KS, VW>()) return &k_grow_tight<KS, VW>;
+  else return &k_grow<KS, VW>;
 }
 
 template <int KS, int VW>
 hipError_t g_launch(hipStream_t st, const GrowParams &p)
 {
   const size_t lds = g_lds_bytes<KS, VW>(p.n);
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 || attr_dev != dev) {
-    hipError_t e = hipFuncSetAttribute(g_kernel<KS, VW>(), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_dev = dev;
-  }
-  if constexpr (g_tight<KS, VW>()) hipLaunchKernelGGL((k_grow_tight<KS, VW>), dim3(p.tiles), dim3(GCfg<KS, VW>::NT), lds, st, p);
-  else hipLaunchKernelGGL((k_grow<KS, VW>), dim3(p.tiles), dim3(GCfg<KS, VW>::NT), lds, st, p);
+  constexpr auto kernel = g_kernel<KS, VW>();
+  const hipError_t e = lds_opt_in<kernel>(160 * 1024);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(p.tiles), dim3(GCfg<KS, VW>::NT), lds, st, p);
   return hipGetLastError();
 }
 
@@ -748,7 +742,7 @@ template <int KS, int VW>
 int g_blocks_per_cu(uint32_t n)
 {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g_kernel<KS, VW>(), GCfg<KS, VW>::NT, g_lds_bytes<KS, VW>(n)) != hipSuccess || nb < 1) nb = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(g_kernel<KS, VW>()), GCfg<KS, VW>::NT, g_lds_bytes<KS, VW>(n)) != hipSuccess || nb < 1) nb = 1;
   return nb;
 }
 
@@ -757,14 +751,18 @@ int g_blocks_per_cu(uint32_t n)
 // vw = 0: the word-major DNA layout (64 words per tile, a lane = one word with its four states)
 int grow_tiles(const Geometry &g, int vw) { return vw == 0 ? (g.Wp + 63) / 64 : (g.Wp + 16 * vw - 1) / (16 * vw); }
 
+// the launch's lane shape <KS, VW>
+template <class F> static decltype(auto) dispatch_grow_shape(const Geometry &g, int vw, F &&f) { return dispatch_lane_shape(g.S, vw, vw == 0, f); }
+
 int grow_waves(const Geometry &g, int vw)
 {
-  if (vw == 0) return 8;
-  const int r = (g.S == 4 ? 1 : g.S == 32 ? 8 : 5) * vw;
-  return r <= 2 ? 16 : 8;
+  return dispatch_grow_shape(g, vw, [](auto KS, auto VW) { return KS * VW <= 2 ? 16 : 8; });
 }
 
-size_t grow_vec_words(const Geometry &g, int vw) { return vw == 0 ? 256 : (size_t)(g.S == 4 ? 1 : g.S == 32 ? 8 : 5) * (size_t)vw * 64; }
+size_t grow_vec_words(const Geometry &g, int vw)
+{
+  return dispatch_grow_shape(g, vw, [](auto KS, auto VW) { return (size_t)(KS * VW) * 64; });
+}
 
 size_t grow_lds_bytes(const Geometry &g, int n_taxa, int vw)
 {
@@ -783,24 +781,12 @@ bool grow_supported(const Geometry &g, int n_taxa)
 
 int grow_blocks_per_cu(const Geometry &g, int n_taxa, int vw)
 {
-  if (g.S == 4 && vw == 0) return g_blocks_per_cu<4, 1>((uint32_t)n_taxa);
-  if (g.S == 4) return vw == 1 ? g_blocks_per_cu<1, 1>((uint32_t)n_taxa) : vw == 2 ? g_blocks_per_cu<1, 2>((uint32_t)n_taxa)
-                       : vw == 8 ? g_blocks_per_cu<1, 8>((uint32_t)n_taxa) : g_blocks_per_cu<1, 4>((uint32_t)n_taxa);
-  if (g.S == 32) return g_blocks_per_cu<8, 1>((uint32_t)n_taxa);
-  return g_blocks_per_cu<5, 1>((uint32_t)n_taxa);
+  return dispatch_grow_shape(g, vw, [&](auto KS, auto VW) { return g_blocks_per_cu<KS, VW>((uint32_t)n_taxa); });
 }
 
 hipError_t launch_grow(hipStream_t st, const Geometry &g, int vw, const GrowParams &p)
 {
-  if (g.S == 4) {
-    if (vw == 0) return g_launch<4, 1>(st, p);        // (p.vec = the word-major copy)
-    if (vw == 1) return g_launch<1, 1>(st, p);
-    if (vw == 2) return g_launch<1, 2>(st, p);
-    if (vw == 8) return g_launch<1, 8>(st, p);
-    return g_launch<1, 4>(st, p);
-  }
-  if (g.S == 32) return g_launch<8, 1>(st, p);
-  return g_launch<5, 1>(st, p);
+  return dispatch_grow_shape(g, vw, [&](auto KS, auto VW) { return g_launch<KS, VW>(st, p); });      // (word-major: p.vec = that copy)
 }
 
 }  // namespace mpf

@@ -882,29 +882,19 @@ hipError_t launch_sched(hipStream_t st, const uint2 *kids, uint32_t n_taxa, uint
   if (sw.nodep && (sw.maxtrav < 1u || sw.maxtrav > 6u)) return hipErrorInvalidValue;
   const size_t lds = sched_lds_bytes(n_taxa, n_taxa + n_ops, sw.nodep != nullptr);
   const uint32_t per = (n_ops + 1023u) / 1024u;
-#define MPF_SCHED(R_)                                                                                                                   \
-  do {                                                                                                                                  \
-    if (lds > 60 * 1024) {                                                                                                              \
-      static thread_local int attr_dev = -1;                                                                                            \
-      int dev = 0;                                                                                                                      \
-      (void)hipGetDevice(&dev);                                                                                                         \
-      if (attr_dev != dev) {                                                                                                            \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sched<R_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        if (e != hipSuccess) return e;                                                                                                  \
-        attr_dev = dev;                                                                                                                 \
-      }                                                                                                                                 \
-    }                                                                                                                                   \
-    hipLaunchKernelGGL((k_sched<R_>), dim3(sw.nodep ? 2 : 1), dim3(1024), lds, st, kids, n_taxa, n_ops, ops, lev_off, n_lev, sw, kids_copy);       \
-  } while (0)
-  if (per <= 1u) MPF_SCHED(1);
-  else if (per <= 2u) MPF_SCHED(2);
-  else if (per <= 3u) MPF_SCHED(3);
-  else if (per <= 4u) MPF_SCHED(4);
-  else if (per <= 6u) MPF_SCHED(6);
-  else if (per <= 8u) MPF_SCHED(8);
-  else MPF_SCHED(16);
-#undef MPF_SCHED
-  return hipGetLastError();
+  auto launch = [&](auto R) {
+    const hipError_t e = lds_opt_in<k_sched<R>>(160 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_sched<R>), dim3(sw.nodep ? 2 : 1), dim3(1024), lds, st, kids, n_taxa, n_ops, ops, lev_off, n_lev, sw, kids_copy);
+    return hipGetLastError();
+  };
+  if (per <= 1u) return launch(int_c<1>());
+  if (per <= 2u) return launch(int_c<2>());
+  if (per <= 3u) return launch(int_c<3>());
+  if (per <= 4u) return launch(int_c<4>());
+  if (per <= 6u) return launch(int_c<6>());
+  if (per <= 8u) return launch(int_c<8>());
+  return launch(int_c<16>());
 }
 
 __global__ __launch_bounds__(256) void k_cntsum(const NvOp *__restrict__ ops, int n_ops, const uint32_t *__restrict__ cntp, uint32_t nslots,
@@ -2349,42 +2339,36 @@ __global__ __launch_bounds__(256) void k_snk_pack(uint32_t *__restrict__ vec, si
 static inline int tiles_of(const Geometry &g) { return (g.Wp + 64 * g.vw - 1) / (64 * g.vw); }
 // weighted mode: elements per state row (patterns, or pattern pairs in the 16-bit packing)
 static inline int snk_elems(const Geometry &g) { return g.snk16 ? g.Wp / 2 : g.Wp; }
-#define MPF_DISPATCH_SNK(FN)                                                          \
-  do {                                                                                \
-    if (g.S == 4) { if (g.snk16) FN(4, true); else FN(4, false); }                    \
-    else if (g.S == 20) { if (g.snk16) FN(20, true); else FN(20, false); }            \
-    else { if (g.snk16) FN(32, true); else FN(32, false); }                           \
-  } while (0)
+
+// Scans beyond the levels that fit registers keep their per-level up-vectors in g.deep_scratch: the batch is cut into launches whose
+// waves (`tiles` per scan, four per workgroup, per_wave scratch words each) fit the area.  launch(s0, ns, grid) issues scans
+// s0 .. s0 + ns - 1.
+template <class F>
+static hipError_t launch_deep(const Geometry &g, size_t per_wave, int tiles, int n_scans, F &&launch)
+{
+  if (!g.deep_scratch) return hipErrorInvalidValue;
+  const long per_launch = (long)(g.deep_scratch_words / per_wave) / tiles;
+  if (per_launch < 1) return hipErrorOutOfMemory;
+  for (long s0 = 0; s0 < n_scans; s0 += per_launch) {
+    const int ns = (int)std::min<long>(per_launch, n_scans - s0);
+    launch(s0, ns, dim3((unsigned)(((long)ns * tiles + 3) / 4)));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 hipError_t launch_pack_tips(hipStream_t st, const Geometry &g, uint32_t *vec, const uint8_t *codes, int n_taxa,
                             int n_patterns, const int32_t *site2ptn, int n_sites, int datatype,
                             const uint32_t *tip_slots)
 {
   dim3 grid((g.Wp + 255) / 256, n_taxa), block(256);          // 4 waves x 64 words per block
-  if (g.S == 4)
-    hipLaunchKernelGGL(k_pack_tips<4>, grid, block, 0, st, vec, codes, n_taxa, n_patterns, site2ptn, n_sites, datatype,
-                       tip_slots, g.Wp, g.shoff ? vec + g.shoff : nullptr);
-  else if (g.S == 20)
-    hipLaunchKernelGGL(k_pack_tips<20>, grid, block, 0, st, vec, codes, n_taxa, n_patterns, site2ptn, n_sites, datatype,
-                       tip_slots, g.Wp, nullptr);
-  else
-    hipLaunchKernelGGL(k_pack_tips<32>, grid, block, 0, st, vec, codes, n_taxa, n_patterns, site2ptn, n_sites, datatype,
-                       tip_slots, g.Wp, nullptr);
+  dispatch_states(g.S, [&](auto S) {
+    hipLaunchKernelGGL((k_pack_tips<S>), grid, block, 0, st, vec, codes, n_taxa, n_patterns, site2ptn, n_sites, datatype,
+                       tip_slots, g.Wp, S == 4 && g.shoff ? vec + g.shoff : nullptr);
+  });
   return hipGetLastError();
 }
-
-#define MPF_DISPATCH_SV(FN, ...)                                                   \
-  do {                                                                             \
-    if (g.S == 4) {                                                                \
-      if (g.vw == 1) { FN(4, 1, __VA_ARGS__); }                                    \
-      else if (g.vw == 2) { FN(4, 2, __VA_ARGS__); }                               \
-      else { FN(4, 4, __VA_ARGS__); }                                              \
-    } else if (g.S == 20) {                                                        \
-      FN(20, 1, __VA_ARGS__);      /* 20 states: one word per lane (engine.cpp, "words_per_lane") */ \
-    } else {                                                                       \
-      FN(32, 1, __VA_ARGS__);      /* 32 states: one word per lane */              \
-    }                                                                              \
-  } while (0)
 
 hipError_t launch_newview(hipStream_t st, const Geometry &g, uint32_t *vec, const NvOp *ops, int n_ops, uint32_t *cntp,
                           uint32_t nslots)
@@ -2396,16 +2380,16 @@ hipError_t launch_newview(hipStream_t st, const Geometry &g, uint32_t *vec, cons
   if (g.sankoff) {
     const int We = snk_elems(g), stiles = (We + 63) / 64;
     dim3 sgrid((unsigned)(((long)n_ops * stiles + 3) / 4));
-#define SNK(S_, PK_) hipLaunchKernelGGL((k_snk_newview<S_, PK_>), sgrid, block, 0, st, vec, g.moff, ops, n_ops, g.cost, cntp, nslots, We, stiles)
-    MPF_DISPATCH_SNK(SNK);
-#undef SNK
+    dispatch_snk(g, [&](auto S, auto PK) {
+      hipLaunchKernelGGL((k_snk_newview<S, PK>), sgrid, block, 0, st, vec, g.moff, ops, n_ops, g.cost, cntp, nslots, We, stiles);
+    });
     return hipGetLastError();
   }
-#define NV(S_, VW_, RED_) hipLaunchKernelGGL((k_newview<S_, VW_, RED_>), grid, block, 0, st, vec, ops, n_ops, cntp, nslots, g.Wp, tiles)
-#define NV2(S_, VW_, dummy) do { if (g.reduce == 0) NV(S_, VW_, 0); else NV(S_, VW_, 1); } while (0)
-  MPF_DISPATCH_SV(NV2, 0);
-#undef NV2
-#undef NV
+  dispatch_sv(g, [&](auto S, auto VW) {
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_newview<S, VW, RED>), grid, block, 0, st, vec, ops, n_ops, cntp, nslots, g.Wp, tiles);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -2422,9 +2406,9 @@ hipError_t launch_newview_levels(hipStream_t st, const Geometry &g, uint32_t *ve
   if (g.sankoff) {
     const int We = snk_elems(g);
     dim3 sgrid((unsigned)((We + 63) / 64));
-#define SNK(S_, PK_) hipLaunchKernelGGL((k_snk_newview_wg<S_, PK_>), sgrid, block, 0, st, vec, g.moff, ops, lev_off, n_lev, g.cost, cntp, nslots, We)
-    MPF_DISPATCH_SNK(SNK);
-#undef SNK
+    dispatch_snk(g, [&](auto S, auto PK) {
+      hipLaunchKernelGGL((k_snk_newview_wg<S, PK>), sgrid, block, 0, st, vec, g.moff, ops, lev_off, n_lev, g.cost, cntp, nslots, We);
+    });
     return hipGetLastError();
   }
   if (g.vw == 1 && g.nv_pipe) {                    // TW lanes per op on TW-word tiles, operands requested a round ahead
@@ -2434,27 +2418,29 @@ hipError_t launch_newview_levels(hipStream_t st, const Geometry &g, uint32_t *ve
     // (a device-planned sweep: one extra 16-wave workgroup per 64 possible walk-plan items, at most as many as fit beside the refresh)
     const unsigned extra = x.wp_desc ? std::min(512u, (2u * x.wp_max_parts + 63u) / 64u) : 0u;
     dim3 qgrid((unsigned)(g.Wp / tw) + extra);
-#define NQ(S_, TW_) hipLaunchKernelGGL((k_newview_wgq<S_, TW_>), qgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, xs)
-    if (g.S == 4) { if (tw == 32) NQ(4, 32); else if (tw == 16) NQ(4, 16); else if (tw == 8) NQ(4, 8); else NQ(4, 4); }
-    else if (g.S == 20) { if (tw == 32) NQ(20, 32); else if (tw == 16) NQ(20, 16); else if (tw == 8) NQ(20, 8); else NQ(20, 4); }
-    else { if (tw == 32) NQ(32, 32); else if (tw == 16) NQ(32, 16); else if (tw == 8) NQ(32, 8); else NQ(32, 4); }
-#undef NQ
+    dispatch_states(g.S, [&](auto S) {
+      auto launch = [&](auto TW) {
+        hipLaunchKernelGGL((k_newview_wgq<S, TW>), qgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, xs);
+      };
+      if (tw == 32) launch(int_c<32>()); else if (tw == 16) launch(int_c<16>()); else if (tw == 8) launch(int_c<8>()); else launch(int_c<4>());
+    });
     return hipGetLastError();
   }
   if (g.vw == 1) {                                 // half a wave per op on 32-word tiles
     dim3 hgrid((unsigned)(g.Wp / 32));
-    if (g.S == 4) hipLaunchKernelGGL((k_newview_wgh<4, 0>), hgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, x);
-    else if (g.S == 20) hipLaunchKernelGGL((k_newview_wgh<20, 0>), hgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, x);
-    else hipLaunchKernelGGL((k_newview_wgh<32, 0>), hgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, x);
+    dispatch_states(g.S, [&](auto S) {
+      hipLaunchKernelGGL((k_newview_wgh<S, 0>), hgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, x);
+    });
     return hipGetLastError();
   }
-#define NW(S_, VW_, RED_) hipLaunchKernelGGL((k_newview_wg<S_, VW_, RED_>), grid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, x)
-#define NW2(S_, VW_, dummy) do { if (g.reduce == 0) NW(S_, VW_, 0); else NW(S_, VW_, 1); } while (0)
   // (several words per lane: DNA only -- wider alphabets run one word per lane and took the branches above)
   if (g.S != 4) return hipErrorInvalidValue;
-  if (g.vw == 2) NW2(4, 2, 0); else NW2(4, 4, 0);
-#undef NW2
-#undef NW
+  dispatch_reduce(g, [&](auto RED) {
+    auto launch = [&](auto VW) {
+      hipLaunchKernelGGL((k_newview_wg<4, VW, RED>), grid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, x);
+    };
+    if (g.vw == 2) launch(int_c<2>()); else launch(int_c<4>());
+  });
   return hipGetLastError();
 }
 
@@ -2466,11 +2452,12 @@ hipError_t launch_newview_chains(hipStream_t st, const Geometry &g, uint32_t *ve
   dim3 grid((unsigned)tiles_of(g));
   RefreshExtra xs = x;
   if (g.shoff && g.S == 4 && g.vw == 1) xs.shadow = vec + g.shoff;
-#define NC(S_, VW_, RED_) hipLaunchKernelGGL((k_newview_chain<S_, VW_, RED_, (S_ * VW_ <= 4 ? 4 : 2)>), grid, dim3(chain_waves<S_, VW_>() * 64), 0, st, vec, ops, wl_off, n_lev, cntp, nslots, g.Wp, cnt, done, n_ops, xs)
-#define NC2(S_, VW_, dummy) do { if (g.reduce == 0) NC(S_, VW_, 0); else NC(S_, VW_, 1); } while (0)
-  MPF_DISPATCH_SV(NC2, 0);
-#undef NC2
-#undef NC
+  dispatch_sv(g, [&](auto S, auto VW) {
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_newview_chain<S, VW, RED, (S * VW <= 4 ? 4 : 2)>), grid, dim3(chain_waves<S, VW>() * 64), 0, st, vec, ops,
+                         wl_off, n_lev, cntp, nslots, g.Wp, cnt, done, n_ops, xs);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -2506,16 +2493,16 @@ hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *ve
   if (g.sankoff) {
     const int We = snk_elems(g), stiles = (We + 63) / 64;
     dim3 sgrid((unsigned)(((long)n_ops * stiles + 3) / 4));
-#define SNK(S_, PK_) hipLaunchKernelGGL((k_snk_evaluate<S_, PK_>), sgrid, block, 0, st, vec, g.moff, ops, n_ops, g.cost, g.pwgt, out, We, stiles)
-    MPF_DISPATCH_SNK(SNK);
-#undef SNK
+    dispatch_snk(g, [&](auto S, auto PK) {
+      hipLaunchKernelGGL((k_snk_evaluate<S, PK>), sgrid, block, 0, st, vec, g.moff, ops, n_ops, g.cost, g.pwgt, out, We, stiles);
+    });
     return hipGetLastError();
   }
-#define EV(S_, VW_, RED_) hipLaunchKernelGGL((k_evaluate<S_, VW_, RED_>), grid, block, 0, st, vec, ops, n_ops, out, g.Wp, tiles)
-#define EV2(S_, VW_, dummy) do { if (g.reduce == 0) EV(S_, VW_, 0); else EV(S_, VW_, 1); } while (0)
-  MPF_DISPATCH_SV(EV2, 0);
-#undef EV2
-#undef EV
+  dispatch_sv(g, [&](auto S, auto VW) {
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_evaluate<S, VW, RED>), grid, block, 0, st, vec, ops, n_ops, out, g.Wp, tiles);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -2532,65 +2519,42 @@ hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, c
     const long waves = (long)n_scans * stiles;
     dim3 sgrid((unsigned)((waves + 3) / 4));
     const bool buf_ok = (unsigned long long)g.moff * 4ull < (1ull << 32);      // each half of the store behind one 32-bit-offset descriptor
-#define SNKSCAN3(S_, D_, PK_, A_) do { if (buf_ok) hipLaunchKernelGGL((k_snk_scan<S_, D_, PK_, A_, true>), sgrid, block, 0, st, vec, g.moff, hdr, n_scans, ops, g.cost, g.pwgt, out, We, stiles, vals, npat, vmax, g.costT); \
-                                       else hipLaunchKernelGGL((k_snk_scan<S_, D_, PK_, A_, false>), sgrid, block, 0, st, vec, g.moff, hdr, n_scans, ops, g.cost, g.pwgt, out, We, stiles, vals, npat, vmax, g.costT); } while (0)
-#define SNKSCAN2(S_, D_, PK_) do { if (g.costT) SNKSCAN3(S_, D_, PK_, true); else SNKSCAN3(S_, D_, PK_, false); } while (0)
-#define SNKSCAN(S_, D_) do { if (g.snk16) SNKSCAN2(S_, D_, true); else SNKSCAN2(S_, D_, false); } while (0)
-    if (max_depth > (g.S == 4 ? kMaxDepth : 6)) {
-      // beyond the levels that fit registers: k_snk_scan_deep, cut into launches whose waves' scratch stays within the area
-      if (!g.deep_scratch) return hipErrorInvalidValue;
+    // (S, PK) x asymmetric cost matrix (costT) x raw-buffer addressing
+    auto dispatch = [&](auto &&f) {
+      dispatch_snk(g, [&](auto S, auto PK) {
+        dispatch_bool(g.costT != nullptr, [&](auto ASYM) { dispatch_bool(buf_ok, [&](auto BUF) { f(S, PK, ASYM, BUF); }); });
+      });
+    };
+    if (max_depth > scan_reg_depth(g.S, true)) {
+      // beyond the levels that fit registers: k_snk_scan_deep
       const int levels = max_depth + 1;
-      const size_t per_wave = (size_t)levels * (size_t)(g.S * 64);
-      long per_launch = (long)(g.deep_scratch_words / per_wave) / stiles;
-      if (per_launch < 1) return hipErrorOutOfMemory;
-      for (long s0 = 0; s0 < n_scans; s0 += per_launch) {
-        const int ns = (int)std::min<long>(per_launch, n_scans - s0);
-        dim3 dgrid((unsigned)(((long)ns * stiles + 3) / 4));
-#define SNKD3(S_, PK_, A_) do { if (buf_ok) hipLaunchKernelGGL((k_snk_scan_deep<S_, PK_, A_, true>), dgrid, block, 0, st, vec, g.moff, hdr + s0, ns, ops, g.cost, g.pwgt, out, We, stiles, vals, npat, vmax, g.costT, g.deep_scratch, levels); \
-                                else hipLaunchKernelGGL((k_snk_scan_deep<S_, PK_, A_, false>), dgrid, block, 0, st, vec, g.moff, hdr + s0, ns, ops, g.cost, g.pwgt, out, We, stiles, vals, npat, vmax, g.costT, g.deep_scratch, levels); } while (0)
-#define SNKD2(S_, PK_) do { if (g.costT) SNKD3(S_, PK_, true); else SNKD3(S_, PK_, false); } while (0)
-#define SNKD(S_) do { if (g.snk16) SNKD2(S_, true); else SNKD2(S_, false); } while (0)
-        if (g.S == 4) SNKD(4); else if (g.S == 20) SNKD(20); else SNKD(32);
-#undef SNKD
-#undef SNKD2
-#undef SNKD3
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
+      return launch_deep(g, (size_t)levels * (size_t)(g.S * 64), stiles, n_scans, [&](long s0, int ns, dim3 dgrid) {
+        dispatch([&](auto S, auto PK, auto ASYM, auto BUF) {
+          hipLaunchKernelGGL((k_snk_scan_deep<S, PK, ASYM, BUF>), dgrid, block, 0, st, vec, g.moff, hdr + s0, ns, ops, g.cost, g.pwgt, out,
+                             We, stiles, vals, npat, vmax, g.costT, g.deep_scratch, levels);
+        });
+      });
     }
-    if (g.S == 4) {
-      if (max_depth <= 6) SNKSCAN(4, 6); else SNKSCAN(4, 12);
-    } else {
-      if (g.S == 20) SNKSCAN(20, 6); else SNKSCAN(32, 6);
-    }
-#undef SNKSCAN
-#undef SNKSCAN2
-#undef SNKSCAN3
+    dispatch([&](auto S, auto PK, auto ASYM, auto BUF) {
+      dispatch_depth<kMaxDepth>(max_depth, [&](auto D) {
+        if constexpr (D <= scan_reg_depth(S, true))
+          hipLaunchKernelGGL((k_snk_scan<S, D, PK, ASYM, BUF>), sgrid, block, 0, st, vec, g.moff, hdr, n_scans, ops, g.cost, g.pwgt, out,
+                             We, stiles, vals, npat, vmax, g.costT);
+      });
+    });
     return hipGetLastError();
   }
   if (max_depth > scan_reg_depth(g.S, false)) {
-    // beyond the levels that fit registers: k_scan_deep, cut into launches whose waves' scratch (levels x one tile each) stays
-    // within scan_deep_scratch_words
-    if (host_out || !g.deep_scratch) return hipErrorInvalidValue;
+    // beyond the levels that fit registers: k_scan_deep, its waves' scratch levels x one tile each
+    if (host_out) return hipErrorInvalidValue;
     const int levels = max_depth + 1;
-    const size_t per_wave = (size_t)levels * (size_t)(g.S * g.vw * 64);
-    long per_launch = (long)(g.deep_scratch_words / per_wave) / tiles;
-    if (per_launch < 1) return hipErrorOutOfMemory;
-    for (long s0 = 0; s0 < n_scans; s0 += per_launch) {
-      const int ns = (int)std::min<long>(per_launch, n_scans - s0);
-      dim3 dgrid((unsigned)(((long)ns * tiles + 3) / 4));
-#define SD(S_, VW_, dummy)                                                                                                     \
-      do {                                                                                                                     \
-        if (g.reduce == 0) hipLaunchKernelGGL((k_scan_deep<S_, VW_, 0>), dgrid, block, 0, st, vec, hdr + s0, ns, ops, out, g.Wp, tiles, g.deep_scratch, levels); \
-        else hipLaunchKernelGGL((k_scan_deep<S_, VW_, 1>), dgrid, block, 0, st, vec, hdr + s0, ns, ops, out, g.Wp, tiles, g.deep_scratch, levels);              \
-      } while (0)
-      MPF_DISPATCH_SV(SD, 0);
-#undef SD
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_deep(g, (size_t)levels * (size_t)(g.S * g.vw * 64), tiles, n_scans, [&](long s0, int ns, dim3 dgrid) {
+      dispatch_sv(g, [&](auto S, auto VW) {
+        dispatch_reduce(g, [&](auto RED) {
+          hipLaunchKernelGGL((k_scan_deep<S, VW, RED>), dgrid, block, 0, st, vec, hdr + s0, ns, ops, out, g.Wp, tiles, g.deep_scratch, levels);
+        });
+      });
+    });
   }
   if (g.map == 0) {
     const long waves = (long)n_scans * tiles;
@@ -2601,16 +2565,14 @@ hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, c
     nblocks = (unsigned)(per_class * 8);
   }
   dim3 grid(nblocks);
-#define SC(S_, VW_, MAXD_, RED_) \
-  hipLaunchKernelGGL((k_scan<S_, VW_, MAXD_, RED_>), grid, block, 0, st, vec, hdr, n_scans, ops, out, g.Wp, tiles, g.map, host_out, n_out, done)
-#define SC2(S_, VW_, dummy)                                                          \
-  do {                                                                               \
-    if (max_depth <= 6) { if (g.reduce == 0) SC(S_, VW_, 6, 0); else SC(S_, VW_, 6, 1); } \
-    else if constexpr (scan_reg_depth(S_, false) > 6) { if (g.reduce == 0) SC(S_, VW_, 12, 0); else SC(S_, VW_, 12, 1); } \
-  } while (0)
-  MPF_DISPATCH_SV(SC2, 0);
-#undef SC2
-#undef SC
+  dispatch_sv(g, [&](auto S, auto VW) {
+    dispatch_depth<kMaxDepth>(max_depth, [&](auto D) {
+      if constexpr (D <= scan_reg_depth(S, false))
+        dispatch_reduce(g, [&](auto RED) {
+          hipLaunchKernelGGL((k_scan<S, VW, D, RED>), grid, block, 0, st, vec, hdr, n_scans, ops, out, g.Wp, tiles, g.map, host_out, n_out, done);
+        });
+    });
+  });
   return hipGetLastError();
 }
 
@@ -2621,91 +2583,57 @@ hipError_t launch_scan_walk(hipStream_t st, const Geometry &g, const uint32_t *v
   if (n_scans <= 0) return hipSuccess;
   const bool split = g.S >= 20;                                    // protein / 32-state data: states split over the wave halves
   const int tiles = split ? (g.Wp + 31) / 32 : (g.big ? (g.Wp + 63) / 64 : tiles_of(g));    // the 64-bit path is one word per lane
+  dim3 block(256);
+  // rows of a wave half (DNA: the four states on the whole wave), and the UFBoot variant
+  auto dispatch = [&](auto &&f) {
+    dispatch_states(g.S, [&](auto S) {
+      dispatch_bool(masks != nullptr, [&](auto MASKS) { f(int_c<S == 4 ? 4 : S / 2>(), bool_c<(S >= 20)>(), MASKS); });
+    });
+  };
   if (max_depth > kWalkMaxDepth) {
-    // 8: the per-depth LDS slots of the walk are sized for it.  Beyond: k_scan_walk_deep, the parked up-vectors in HBM scratch, cut
-    // into launches whose waves' levels fit it (the batch's scans are laid out independently: out_base per scan)
-    if (host_out || !g.deep_scratch) return hipErrorInvalidValue;
+    // 8: the per-depth LDS slots of the walk are sized for it.  Beyond: k_scan_walk_deep, the parked up-vectors in HBM scratch
+    // (the batch's scans are laid out independently: out_base per scan)
+    if (host_out || (g.S != 4 && g.S != 20 && g.S != 32)) return hipErrorInvalidValue;
     const int levels = max_depth;                                  // (slots for depths 1 + REGP .. max_depth - 1)
     const int rows = split ? (g.S / 2) : g.S * (g.big ? 1 : g.vw);
-    const size_t per_wave = (size_t)levels * (size_t)(rows * 64);
-    long per_launch = (long)(g.deep_scratch_words / per_wave) / tiles;
-    if (per_launch < 1) return hipErrorOutOfMemory;
-    for (long s0 = 0; s0 < n_scans; s0 += per_launch) {
-      const int ns = (int)std::min<long>(per_launch, n_scans - s0);
-      dim3 dgrid((unsigned)(((long)ns * tiles + 3) / 4)), dblock(256);
-#define SWD(S_, VW_, SPLIT_, BIG_)                                                                                                          \
-      do {                                                                                                                                  \
-        if (masks) {                                                                                                                        \
-          if (g.reduce == 0) hipLaunchKernelGGL((k_scan_walk_deep<S_, VW_, 0, SPLIT_, true, BIG_>), dgrid, dblock, 0, st, vec, kids, (uint32_t)n_taxa, desc + s0, ns, out, ncand + s0, g.Wp, tiles, masks, info, g.deep_scratch, levels, (uint32_t)s0); \
-          else hipLaunchKernelGGL((k_scan_walk_deep<S_, VW_, 1, SPLIT_, true, BIG_>), dgrid, dblock, 0, st, vec, kids, (uint32_t)n_taxa, desc + s0, ns, out, ncand + s0, g.Wp, tiles, masks, info, g.deep_scratch, levels, (uint32_t)s0); \
-        } else {                                                                                                                            \
-          if (g.reduce == 0) hipLaunchKernelGGL((k_scan_walk_deep<S_, VW_, 0, SPLIT_, false, BIG_>), dgrid, dblock, 0, st, vec, kids, (uint32_t)n_taxa, desc + s0, ns, out, ncand + s0, g.Wp, tiles, masks, info, g.deep_scratch, levels, (uint32_t)s0); \
-          else hipLaunchKernelGGL((k_scan_walk_deep<S_, VW_, 1, SPLIT_, false, BIG_>), dgrid, dblock, 0, st, vec, kids, (uint32_t)n_taxa, desc + s0, ns, out, ncand + s0, g.Wp, tiles, masks, info, g.deep_scratch, levels, (uint32_t)s0); \
-        }                                                                                                                                   \
-      } while (0)
-      if (g.big) {
-        if (g.S == 4) SWD(4, 1, false, true); else if (g.S == 20) SWD(10, 1, true, true); else SWD(16, 1, true, true);
-      } else if (g.S == 4) {
-        if (g.vw == 1) SWD(4, 1, false, false); else SWD(4, 2, false, false);
-      } else if (g.S == 20) SWD(10, 1, true, false);
-      else if (g.S == 32) SWD(16, 1, true, false);
-      else return hipErrorInvalidValue;
-#undef SWD
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_deep(g, (size_t)levels * (size_t)(rows * 64), tiles, n_scans, [&](long s0, int ns, dim3 dgrid) {
+      dispatch([&](auto R, auto SPLIT, auto MASKS) {
+        dispatch_bool(g.big, [&](auto BIG) {
+          dispatch_reduce(g, [&](auto RED) {
+            auto launch = [&](auto VW) {
+              hipLaunchKernelGGL((k_scan_walk_deep<R, VW, RED, SPLIT, MASKS, BIG>), dgrid, block, 0, st, vec, kids, (uint32_t)n_taxa, desc + s0, ns,
+                                 out, ncand + s0, g.Wp, tiles, masks, info, g.deep_scratch, levels, (uint32_t)s0);
+            };
+            if constexpr (!SPLIT && !BIG) { if (g.vw != 1) return launch(int_c<2>()); }
+            launch(int_c<1>());
+          });
+        });
+      });
+    });
   }
   const long waves = (long)n_scans * tiles;
-  dim3 block(256);
   unsigned nblocks;
   if (g.map == 0) nblocks = (unsigned)((waves + 3) / 4);
   else { const long chunk = (waves + 7) / 8; nblocks = (unsigned)(((chunk + 3) / 4) * 8); }
   dim3 grid(nblocks);
-#define SWB(S_, VW_, MAXD_, RED_, SPLIT_, BIG_)                                                                                       \
-  do {                                                                                                                                \
-    if (masks)                                                                                                                        \
-      hipLaunchKernelGGL((k_scan_walk<S_, VW_, MAXD_, RED_, SPLIT_, true, BIG_>), grid, block, 0, st, vec, kids, (uint32_t)n_taxa,    \
-                         desc, n_scans, out, ncand, g.Wp, tiles, g.map, masks, info, host_out, n_out, done);                           \
-    else                                                                                                                              \
-      hipLaunchKernelGGL((k_scan_walk<S_, VW_, MAXD_, RED_, SPLIT_, false, BIG_>), grid, block, 0, st, vec, kids, (uint32_t)n_taxa,   \
-                         desc, n_scans, out, ncand, g.Wp, tiles, g.map, masks, info, host_out, n_out, done);                           \
-  } while (0)
-#define SW(S_, VW_, MAXD_, RED_, SPLIT_) SWB(S_, VW_, MAXD_, RED_, SPLIT_, false)
-#define SW2(S_, VW_, SPLIT_)                                                                                 \
-  do {                                                                                                       \
-    if (max_depth <= 6) { if (g.reduce == 0) SW(S_, VW_, 6, 0, SPLIT_); else SW(S_, VW_, 6, 1, SPLIT_); }    \
-    else { if (g.reduce == 0) SW(S_, VW_, 8, 0, SPLIT_); else SW(S_, VW_, 8, 1, SPLIT_); }                   \
-  } while (0)
-  if (g.big) {
-    // >= 2 GiB of vectors: one code path (one word per lane, DPP reduction), 64-bit addressing
-    if (g.S == 4) { if (max_depth <= 6) SWB(4, 1, 6, 0, false, true); else SWB(4, 1, 8, 0, false, true); }
-    else if (g.S == 20) { if (max_depth <= 6) SWB(10, 1, 6, 0, true, true); else SWB(10, 1, 8, 0, true, true); }
-    else { if (max_depth <= 6) SWB(16, 1, 6, 0, true, true); else SWB(16, 1, 8, 0, true, true); }
-  } else if (g.S == 4 && g.vw == 1 && word_major && g.shoff) {
-    // the vectors from the word-major copy (the caller knows it is current): one 16-byte load per lane and vector
-#define SWM(MAXD_, RED_)                                                                                                              \
-  do {                                                                                                                                \
-    if (masks)                                                                                                                        \
-      hipLaunchKernelGGL((k_scan_walk<4, 1, MAXD_, RED_, false, true, false, true>), grid, block, 0, st, vec + g.shoff, kids,         \
-                         (uint32_t)n_taxa, desc, n_scans, out, ncand, g.Wp, tiles, g.map, masks, info, host_out, n_out, done);         \
-    else                                                                                                                              \
-      hipLaunchKernelGGL((k_scan_walk<4, 1, MAXD_, RED_, false, false, false, true>), grid, block, 0, st, vec + g.shoff, kids,        \
-                         (uint32_t)n_taxa, desc, n_scans, out, ncand, g.Wp, tiles, g.map, masks, info, host_out, n_out, done);         \
-  } while (0)
-    if (max_depth <= 6) { if (g.reduce == 0) SWM(6, 0); else SWM(6, 1); }
-    else { if (g.reduce == 0) SWM(8, 0); else SWM(8, 1); }
-#undef SWM
-  } else if (g.S == 4) {
-    if (g.vw == 1) SW2(4, 1, false); else SW2(4, 2, false);
-  } else if (g.S == 20) {
-    SW2(10, 1, true);
-  } else {
-    SW2(16, 1, true);
-  }
-#undef SW2
-#undef SW
-#undef SWB
+  dispatch([&](auto R, auto SPLIT, auto MASKS) {
+    dispatch_depth<kWalkMaxDepth>(max_depth, [&](auto D) {
+      auto launch = [&](auto VW, auto RED, auto BIG, auto WM) {
+        hipLaunchKernelGGL((k_scan_walk<R, VW, D, RED, SPLIT, MASKS, BIG, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, kids,
+                           (uint32_t)n_taxa, desc, n_scans, out, ncand, g.Wp, tiles, g.map, masks, info, host_out, n_out, done);
+      };
+      // >= 2 GiB of vectors: one code path (one word per lane, DPP reduction), 64-bit addressing
+      if (g.big) return launch(int_c<1>(), int_c<0>(), bool_c<true>(), bool_c<false>());
+      dispatch_reduce(g, [&](auto RED) {
+        if constexpr (!SPLIT) {
+          // the vectors from the word-major copy (the caller knows it is current): one 16-byte load per lane and vector
+          if (g.vw == 1 && word_major && g.shoff) return launch(int_c<1>(), RED, bool_c<false>(), bool_c<true>());
+          if (g.vw != 1) return launch(int_c<2>(), RED, bool_c<false>(), bool_c<false>());
+        }
+        launch(int_c<1>(), RED, bool_c<false>(), bool_c<false>());
+      });
+    });
+  });
   return hipGetLastError();
 }
 
@@ -2809,22 +2737,23 @@ hipError_t launch_scan_prog(hipStream_t st, const Geometry &g, const uint32_t *v
   else { const long chunk = (waves + 7) / 8; nblocks = (unsigned)(chunk * 8); }
   dim3 grid(nblocks);
   const ProgEnt *pg = static_cast<const ProgEnt *>(prog);
-#define SP(VW_, BIG_) hipLaunchKernelGGL((k_scan_prog<4, VW_, BIG_>), grid, block, 0, st, vec, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace)
+  // v: the row-major store, or the word-major copy (the caller knows it is current) for the kernels that read it
+  auto launch = [&](auto kernel, const uint32_t *v) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, v, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace);
+  };
+  const bool wm = word_major && g.shoff && !g.big && vw == 1;
 #ifdef MPF_EXPERIMENTS                     // (wrong results on purpose: never in the production library)
   static const int expr = getenv("MPF_PROG_EXPERIMENT") ? atoi(getenv("MPF_PROG_EXPERIMENT")) : 0;
-  const bool wm = word_major && g.shoff && !g.big && vw == 1;
-  if (expr == 1) hipLaunchKernelGGL((k_scan_prog<4, 1, false, 1>), grid, block, 0, st, vec, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace);
-  else if (expr == 2 && wm) hipLaunchKernelGGL((k_scan_prog<4, 1, false, 2, true>), grid, block, 0, st, vec + g.shoff, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace);
-  else if (expr == 2) hipLaunchKernelGGL((k_scan_prog<4, 1, false, 2>), grid, block, 0, st, vec, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace);
+  if (expr == 1) launch(k_scan_prog<4, 1, false, 1>, vec);
+  else if (expr == 2 && wm) launch(k_scan_prog<4, 1, false, 2, true>, vec + g.shoff);
+  else if (expr == 2) launch(k_scan_prog<4, 1, false, 2>, vec);
   else
 #endif
-  if (g.S == 20) hipLaunchKernelGGL((k_scan_prog<20, 1, false>), grid, block, 0, st, vec, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace);
-  else if (g.big) SP(1, true);
-  else if (vw == 1 && word_major && g.shoff)
-    hipLaunchKernelGGL((k_scan_prog<4, 1, false, 0, true>), grid, block, 0, st, vec + g.shoff, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace);
-  else if (vw == 1) SP(1, false);
-  else SP(2, false);
-#undef SP
+  if (g.S == 20) launch(k_scan_prog<20, 1, false>, vec);
+  else if (g.big) launch(k_scan_prog<4, 1, true>, vec);
+  else if (wm) launch(k_scan_prog<4, 1, false, 0, true>, vec + g.shoff);
+  else if (vw == 1) launch(k_scan_prog<4, 1, false>, vec);
+  else launch(k_scan_prog<4, 2, false>, vec);
   return hipGetLastError();
 }
 
@@ -2836,9 +2765,7 @@ hipError_t launch_site_counts(hipStream_t st, const Geometry &g, const uint32_t 
   const int n_chunks = (n_ops + kPlaneChunk - 1) / kPlaneChunk;
   const long waves = (long)n_chunks * tiles;
   dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-#define SP(S_, VW_, dummy) hipLaunchKernelGGL((k_site_planes<S_, VW_>), grid, block, 0, st, vec, ops, n_ops, planes, g.Wp, tiles)
-  MPF_DISPATCH_SV(SP, 0);
-#undef SP
+  dispatch_sv(g, [&](auto S, auto VW) { hipLaunchKernelGGL((k_site_planes<S, VW>), grid, block, 0, st, vec, ops, n_ops, planes, g.Wp, tiles); });
   hipLaunchKernelGGL(k_pattern_sum, dim3((n_ptn + 255) / 256), dim3(256), 0, st, planes, n_chunks, g.Wp, ptn_first_site,
                      n_ptn, ptn_out);
   return hipGetLastError();
@@ -2855,9 +2782,9 @@ hipError_t launch_sankoff_pattern(hipStream_t st, const Geometry &g, const uint3
 {
   const int We = snk_elems(g);
   dim3 grid((We + 255) / 256), block(256);
-#define SNK(S_, PK_) hipLaunchKernelGGL((k_snk_pattern<S_, PK_>), grid, block, 0, st, vec, g.moff, a, b, g.cost, ptn_out, We, vmax)
-  MPF_DISPATCH_SNK(SNK);
-#undef SNK
+  dispatch_snk(g, [&](auto S, auto PK) {
+    hipLaunchKernelGGL((k_snk_pattern<S, PK>), grid, block, 0, st, vec, g.moff, a, b, g.cost, ptn_out, We, vmax);
+  });
   return hipGetLastError();
 }
 
@@ -2866,9 +2793,10 @@ hipError_t launch_pack_tips_sankoff(hipStream_t st, const Geometry &g, uint32_t 
 {
   const int We = snk_elems(g);
   dim3 grid((We + 255) / 256, n_taxa), block(256);
-#define SNK(S_, PK_) hipLaunchKernelGGL((k_snk_pack<S_, PK_>), grid, block, 0, st, vec, g.moff, codes, n_taxa, n_patterns, inf_index, n_inf, datatype, g.highest_cost, g.cost, We)
-  MPF_DISPATCH_SNK(SNK);
-#undef SNK
+  dispatch_snk(g, [&](auto S, auto PK) {
+    hipLaunchKernelGGL((k_snk_pack<S, PK>), grid, block, 0, st, vec, g.moff, codes, n_taxa, n_patterns, inf_index, n_inf, datatype,
+                       g.highest_cost, g.cost, We);
+  });
   return hipGetLastError();
 }
 

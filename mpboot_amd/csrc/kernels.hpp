@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <type_traits>
 
 namespace mpf {
 
@@ -65,6 +67,73 @@ struct Geometry {
   int snk16 = 0;                    // weighted mode: two 16-bit costs per lane (v_pk_add_u16 / v_pk_min_u16)
   size_t moff = 0;                  // words from a vector to its min-plus transform m(v) (second half of the vector array)
 };
+
+// ---------------------------------------------------------------- launch dispatch
+// Each helper turns one runtime value into a compile-time constant (std::integral_constant, usable as a template argument) and
+// calls f with it; f's result is returned.  A launch function names its kernel and arguments once, inside the innermost lambda.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <bool V> using bool_c = std::integral_constant<bool, V>;
+
+template <class F> decltype(auto) dispatch_bool(bool b, F &&f) { if (b) return f(bool_c<true>()); return f(bool_c<false>()); }
+// state rows: 4 | 20 | 32 (anything else takes the 32-state kernels)
+template <class F> decltype(auto) dispatch_states(int S, F &&f)
+{
+  if (S == 4) return f(int_c<4>());
+  if (S == 20) return f(int_c<20>());
+  return f(int_c<32>());
+}
+// (S, words per lane) of the Fitch kernels: several words per lane (2 | 4) for DNA only; 20 and 32 states run one
+template <class F> decltype(auto) dispatch_sv(const Geometry &g, F &&f)
+{
+  if (g.S == 4) {
+    if (g.vw == 1) return f(int_c<4>(), int_c<1>());
+    if (g.vw == 2) return f(int_c<4>(), int_c<2>());
+    return f(int_c<4>(), int_c<4>());
+  }
+  return dispatch_states(g.S, [&](auto S) { return f(S, int_c<1>()); });
+}
+// (S, two 16-bit costs per lane) of the weighted kernels
+template <class F> decltype(auto) dispatch_snk(const Geometry &g, F &&f)
+{
+  return dispatch_states(g.S, [&](auto S) { return dispatch_bool(g.snk16 != 0, [&](auto PK) { return f(S, PK); }); });
+}
+// wave reduction: 0 = DPP, 1 = ds_bpermute
+template <class F> decltype(auto) dispatch_reduce(const Geometry &g, F &&f) { if (g.reduce == 0) return f(int_c<0>()); return f(int_c<1>()); }
+// depth class of a register-resident scan: 6, or DEEP for longer radii
+template <int DEEP, class F> decltype(auto) dispatch_depth(int max_depth, F &&f) { if (max_depth <= 6) return f(int_c<6>()); return f(int_c<DEEP>()); }
+// lane shape <KS, VW> of the climb and grow kernels (states per lane group, words per lane): DNA <1, vw> (vw 1 | 2 | 4 | 8), DNA in
+// the word-major layout <4, 1> (a lane holds the four states of a word, 64-word tiles), 20 states <5, 1>, 32 states <8, 1>
+template <class F> decltype(auto) dispatch_lane_shape(int S, int vw, bool word_major, F &&f)
+{
+  if (S == 4) {
+    if (word_major) return f(int_c<4>(), int_c<1>());
+    if (vw == 1) return f(int_c<1>(), int_c<1>());
+    if (vw == 2) return f(int_c<1>(), int_c<2>());
+    if (vw == 8) return f(int_c<1>(), int_c<8>());
+    return f(int_c<1>(), int_c<4>());
+  }
+  if (S == 32) return f(int_c<8>(), int_c<1>());
+  return f(int_c<5>(), int_c<1>());
+}
+
+// Opt-in of a kernel to dynamic LDS above 64 KiB: up to max_bytes of LDS per workgroup in all (the runtime refuses a dynamic
+// maximum that leaves no room for the kernel's static LDS).  The attribute belongs to the process and the device, so it is set
+// once per (kernel, device) for the whole process, before the kernel's first launch there (engines on several host threads share
+// a device; engines of one process may sit on different GPUs)
+template <auto Kernel> hipError_t lds_opt_in(int max_bytes)
+{
+  static std::atomic<bool> set[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool tracked = dev >= 0 && dev < 64;
+  if (tracked && set[dev].load(std::memory_order_acquire)) return hipSuccess;
+  hipFuncAttributes fa;
+  hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(Kernel));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes - (int)fa.sharedSizeBytes);
+  if (e == hipSuccess && tracked) set[dev].store(true, std::memory_order_release);
+  return e;
+}
 
 hipError_t launch_pack_tips(hipStream_t st, const Geometry &g, uint32_t *vec, const uint8_t *codes, int n_taxa,
                             int n_patterns, const int32_t *site2ptn, int n_sites, int datatype,

@@ -19,7 +19,6 @@
 #include "ufboot.hpp"
 
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 
 namespace mpf {
@@ -764,16 +763,9 @@ static hipError_t launch_bitgemm_t(hipStream_t st, const uint32_t *masks, int ro
   unsigned gx;
   if (col_blocks <= 8 && 8 % col_blocks == 0) { const int per_x = 8 / col_blocks; gx = (unsigned)(((row_blocks + per_x - 1) / per_x) * 8); }
   else gx = (unsigned)(row_blocks * col_blocks);
-  // > 64 KiB of dynamic LDS needs the opt-in, once per device (engines of one process may sit on different GPUs)
-  static std::atomic<bool> attr_set[64];                  // (engines on several host threads share a device)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
   constexpr size_t lds = gemm_lds<MT, NT, WM, WN, KS, NS>();
-  if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_bitgemm<MT, NT, WM, WN, KS, NS, EXPR, M32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-  }
+  const hipError_t e = lds_opt_in<k_bitgemm<MT, NT, WM, WN, KS, NS, EXPR, M32>>((int)lds);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_bitgemm<MT, NT, WM, WN, KS, NS, EXPR, M32>), dim3(gx, (unsigned)ksplit), dim3(64 * WM * WN), lds, st, masks, Wp, Wt, Bp, C, mult, atomic, row_blocks, per, rowsel, row_limit);
   return hipGetLastError();
 }
