@@ -11,7 +11,12 @@ Metric (BASELINE.json): Fitch site-ops/s = taxa x patterns x SPR-evals/s.
 N > 1: every rank holds the alignment and scans its own start tree
 (independent units, no data-path collective) -> weak scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3]
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything else: the side measurements of the step (planned
+topology, refresh kernels, live PMC traffic), the secondary legs (--legs) and
+the CPU baselines.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--full]
 """
 from __future__ import annotations
 
@@ -84,10 +89,9 @@ def live_traffic(args) -> dict:
         return {}
     tmp = tempfile.mkdtemp(prefix="mpf_traffic_")
     env = dict(os.environ)
-    env["MPF_BENCH_TRAFFIC_CHILD"] = "1"
     env.setdefault("TMPDIR", "/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu", "--bootstrap-replicates", "0",
-             "--ufboot-samples", "0", "--random-start-leg", "0", "--weighted-leg", "0", "--start-trees", "0", "--climb-engines", "0",
+    # (a plain run: the sweep steps alone, no profiler child of its own)
+    child = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1",
              "--workload", args.workload, "--maxtrav", str(args.maxtrav), "--tree-cache", os.path.join(tmp, "tree")]
     for kv in args.opt:
         child += ["--opt", kv]
@@ -204,6 +208,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="C3")
     ap.add_argument("--maxtrav", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, report everything else: the step on a planned topology, the refresh kernels' own "
+                         "time, live PMC traffic (single rank), the secondary legs (--legs) and the CPU baselines (unless --no-cpu)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--start-tree", default="ras", choices=["ras", "random"])
@@ -243,8 +250,8 @@ def main():
     ap.add_argument("--many-c2", type=int, default=512, help="climbs_in_one_launch leg: C2 climbs per call")
     ap.add_argument("--many-c3", type=int, default=256, help="climbs_in_one_launch leg: C3 climbs per call (an engine each: 0.25 GB; 0 = skip)")
     ap.add_argument("--legs", default="all",
-                    help="comma-separated secondary legs to run (default all): ufboot_online (with the refinement of its trees), random_start, concurrent_climbs, start_trees, bb_reference_run, c2_climb, "
-                         "c5_weighted_sweep, c5_fitch, noisy_bootstrap, climbs_in_one_launch; the headline step, its roofline and cpu_baseline always run")
+                    help="--full: comma-separated secondary legs to run (default all): ufboot_online (with the refinement of its trees), random_start, concurrent_climbs, start_trees, bb_reference_run, c2_climb, "
+                         "c5_weighted_sweep, c5_fitch, noisy_bootstrap, climbs_in_one_launch; the headline step, its side measurements and cpu_baseline always run")
     ap.add_argument("--ufboot-samples", type=int, default=1000,
                     help="bootstrap samples of the online UFBoot-MP leg (-bb): one pllOptimizeSprParsimony call with "
                          "saveCurrentTree after every insertion test, timed after the main metric (0 = skip)")
@@ -252,6 +259,8 @@ def main():
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     legs_wanted = set(x.strip() for x in args.legs.split(","))
+    if not args.full and legs_wanted - {"all", "none"}:
+        ap.error("--legs names secondary legs: they run with --full only")
     leg_on = lambda name: "all" in legs_wanted or name in legs_wanted
     # wall clock of the run, leg by leg (what the driver's own clock around this command is made of)
     _laps, _lap_at = [], [time.perf_counter(), "set-up + headline"]
@@ -260,6 +269,15 @@ def main():
         now = time.perf_counter()
         _laps.append((_lap_at[1], now - _lap_at[0]))
         _lap_at[0], _lap_at[1] = now, name
+
+    def print_line(res):
+        _lap("end")
+        agg = {}
+        for k, v in _laps:
+            agg[k] = agg.get(k, 0.0) + v
+        res["bench_wall_s"] = {k: round(v, 2) for k, v in agg.items()}
+        res["bench_wall_s"]["total"] = round(sum(agg.values()), 2)
+        print(json.dumps(res), flush=True)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: this process (which has made NO GPU call and never imports torch)
@@ -277,7 +295,7 @@ def main():
     # (under a profiler this process may hold the GPU already -- the counter tool initialises it before main() -- and must not
     #  start programs any more: the committed figures are quoted then)
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-    if (world == 1 and os.environ.get("MPF_BENCH_DRYRUN") != "1" and os.environ.get("MPF_BENCH_TRAFFIC_CHILD") != "1"
+    if (args.full and world == 1 and os.environ.get("MPF_BENCH_DRYRUN") != "1"
             and os.environ.get("MPF_BENCH_LIVE_TRAFFIC", "1") != "0" and not profiled):
         # before this process makes its first GPU call: the profiler runs are child processes
         LIVE_TRAFFIC.update(live_traffic(args))
@@ -340,7 +358,9 @@ def main():
     for _ in range(8):
         eng.set_tree(back)
         eng.sweep_scan(1, args.maxtrav)
-    # Side numbers first (the same step on a planned topology; the refresh kernels' own time), the headline after them.
+    # Side numbers first (the same step on a planned topology; the refresh kernels' own time), the headline after them.  A plain
+    # run makes the same sweeps and leaves their figures out of its line: the headline has always been timed behind them, and on a
+    # device that has made fewer sweeps the timed steps run about 2 % slower.
     eng.set_option("plan_cache", 1)
     wsteps = max(1, min(20, args.steps))
     for _ in range(3):
@@ -363,12 +383,14 @@ def main():
     torch.cuda.synchronize()
     view_ms = eng.stats()["view_kernel_ms_total"] / vsteps
     eng.set_option("timing", 1)
+    if not args.full:
+        warm_ms = view_ms = None
 
     # The timed steps hand one tree over again and again.  What the engine plans from the topology alone (refresh schedule, scan
     # descriptors, device program) would be planned once and reused -- as it is between bootstrap replicates that share a tree, or
     # after a re-weighting, in a real run -- but a plain search sees a NEW topology after every accepted move, so the headline is
     # timed with that reuse switched off (engine option plan_cache = 0: every step plans from scratch, everything else identical).
-    # The short loop above priced the step with the reuse on; both figures go into the line.
+    # The short loop above priced the step with the reuse on; a --full line carries both figures.
     eng.set_option("plan_cache", 0)
     for _ in range(args.warmup):                 # W untimed warm-up steps, the same kind of step as the timed ones
         eng.set_tree(back)
@@ -436,7 +458,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt_all / args.steps * 1e3,
-            "ms_per_step_same_topology": warm_ms,      # rank 0, untimed side loop: plans of the topology reused (engine option plan_cache = 1)
+            "ms_per_step_same_topology": warm_ms,      # --full, rank 0, untimed side loop: plans of the topology reused (engine option plan_cache = 1)
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -448,8 +470,8 @@ def main():
                        "planning": "every step plans from scratch (engine option plan_cache = 0): the host uploads the topology array, the "
                                    "device makes the refresh schedule, the scan descriptors and the DFS programs (k_sched; the walk plan rides on "
                                    "the refresh launch), recomputes every vector and re-scores every insertion test -- the step of a search that "
-                                   "has just accepted a move.  ms_per_step_same_topology = the same step on a topology the engine has planned "
-                                   "before (a re-weighted or re-evaluated tree)",
+                                   "has just accepted a move.  ms_per_step_same_topology (--full) = the same step on a topology the engine has "
+                                   "planned before (a re-weighted or re-evaluated tree)",
                        "start_tree_score": start_score, "parallelism": f"independent start trees x{world}",
                        # the three rates side by side.  value = effective (n x P x evals/s, as defined);
                        # touched = node-vector operations actually performed x P: per eval one chain step (fitch of the
@@ -487,7 +509,7 @@ def main():
                                  "traffic = rocprofv3 PMC bytes that left the L2s per launch (2 x FETCH_SIZE + WRITE_SIZE, KB; see "
                                  "traffic_source; a committed figure is quoted only while the sources match the profiled build).  survey_6vector_GBps is SURVEY 8(d)'s 6-vectors-per-test figure / kernel time: a "
                                  "labelled side number, not a fraction of anything the kernel moves"},
-            "views": {"newview_ops": st["newview_ops"] / args.steps, "kernel_ms_per_step": view_ms,
+            "views": {"newview_ops": st["newview_ops"] / args.steps, "kernel_ms_per_step": view_ms,      # (--full: the side loop's)
                       "schedule_kernel": {"kernel": "k_sched", "schedule_workgroup_us": sched_us[0], "descriptor_workgroup_us": sched_us[1],
                                           "dependency_levels": sched_us[2],
                                           "what": "one launch in front of the refresh of a NEW topology: refresh schedule (levels, ops in level "
@@ -495,7 +517,7 @@ def main():
                                                   "measured in the kernel (s_memrealtime)"},
                       "launches_per_step": st["view_launches"] / args.steps,
                       # refresh of every directional vector: 2 vector reads + 1 write per op, HBM-bound by nature
-                      "roofline": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
+                      "roofline": None if view_ms is None else {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
                                    "achieved": (st["newview_ops"] / args.steps) * 3 * eng.S * eng.Wp * 4 / (view_ms * 1e-3) / 1e9 if view_ms > 0 else 0.0,
                                    "frac": (st["newview_ops"] / args.steps) * 3 * eng.S * eng.Wp * 4 / (view_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if view_ms > 0 else 0.0,
                                    "traffic": offline_traffic(args.workload, "k_newview") if (LIVE_TRAFFIC or not args.opt) else None}},
@@ -504,6 +526,15 @@ def main():
                                  "sweep_call": st["host_sweep_ms_total"] / args.steps},
         }
         core_res = res
+
+    if not args.full:
+        # a plain run ends with the headline: the secondary legs and the CPU baselines are --full's
+        if rank == 0:
+            print_line(core_res)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
 
     # The secondary legs below exchange data between the ranks.  Should one of them stall (a rank that failed skips a
     # collective the others wait in), the headline line still goes out: after --legs-timeout seconds rank 0 prints it
@@ -1183,13 +1214,7 @@ def main():
                         bbref["gpu_over_cpu_one_core"] = cbr["value"] / (sq["iterations_s"] + (bbref.get("parallel") or {}).get("refinement_s", 0.0))
                 except Exception as exc:
                     bbref["cpu_baseline"] = {"error": repr(exc)}
-        _lap("end")
-        agg = {}
-        for k, v in _laps:
-            agg[k] = agg.get(k, 0.0) + v
-        res["bench_wall_s"] = {k: round(v, 2) for k, v in agg.items()}
-        res["bench_wall_s"]["total"] = round(sum(agg.values()), 2)
-        print(json.dumps(res), flush=True)
+        print_line(res)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -37,3 +37,10 @@ def test_single_rank_needs_no_launcher():
 def test_world_size_must_match_gpus():
     out = run(["--gpus", "2"], WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     assert out.returncode != 0 and "WORLD_SIZE" in (out.stderr + out.stdout)
+
+
+def test_legs_need_full():
+    out = run(["--legs", "c5_fitch"])
+    assert out.returncode != 0 and "--full" in out.stderr
+    out = run(["--full", "--legs", "c5_fitch", "--steps", "2", "--warmup", "0"])
+    assert out.returncode == 0, out.stderr[-2000:]

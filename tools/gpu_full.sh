@@ -1,8 +1,10 @@
 #!/bin/bash
+# The GPU suite and the whole benchmark (bench.py --full): tools/gpu_full.sh <output dir>
 set -u
-mkdir -p gpurun_out/full
-timeout 2400 python -m pytest tests -x -q -m gpu > gpurun_out/full/pytest.log 2>&1
-echo "pytest rc=$?" > gpurun_out/full/rc.txt
-timeout 900 python bench.py > gpurun_out/full/bench.json 2> gpurun_out/full/bench.err
-echo "bench rc=$?" >> gpurun_out/full/rc.txt
-cat gpurun_out/full/rc.txt; tail -n 5 gpurun_out/full/pytest.log; cut -c1-600 gpurun_out/full/bench.json; tail -n 3 gpurun_out/full/bench.err
+OUT=${1:?usage: tools/gpu_full.sh <output dir>}
+mkdir -p $OUT
+timeout 2400 python -m pytest tests -x -q -m gpu > $OUT/pytest.log 2>&1
+echo "pytest rc=$?" > $OUT/rc.txt
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+echo "bench rc=$?" >> $OUT/rc.txt
+cat $OUT/rc.txt; tail -n 5 $OUT/pytest.log; cut -c1-600 $OUT/bench.json; tail -n 3 $OUT/bench.err

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 export MPF_BENCH_LIVE_TRAFFIC=0
 leg () {   # name, bench args
   local NAME=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$NAME -- python3 bench.py --no-cpu --steps 5 --warmup 1 "$@" > $OUT/bench_$NAME.json 2> $OUT/$NAME.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$NAME -- python3 bench.py --full --no-cpu --steps 5 --warmup 1 "$@" > $OUT/bench_$NAME.json 2> $OUT/$NAME.err
   find $OUT/trace_$NAME -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_$NAME.csv \;
   rm -rf $OUT/trace_$NAME
   head -8 $OUT/kernel_stats_$NAME.csv | cut -c1-160

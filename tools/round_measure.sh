@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 python -m pytest tests -m gpu -x -q > $OUT/gputest.txt 2>&1
 tail -3 $OUT/gputest.txt
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 600 $OUT/bench_default.err
 {
   echo "# independent C3 climbs from random trees on ONE GPU, one engine per host thread (tools/concurrent_climbs.py)"
