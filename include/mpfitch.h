@@ -234,6 +234,30 @@ int mpf_make_parsimony_tree(mpf_engine *e, int64_t seed, int32_t spr_dist, uint3
 int mpf_stepwise_addition(mpf_engine *e, int64_t seed, uint32_t *best_per_step /* [n+1] */,
                           int32_t *insert_per_step /* [n+1] */, uint32_t *score);
 
+/* double IQTree::optimizeNNI(int &nni_count, int &nni_steps) (reference iqtree.cpp:2173-2302) in MP mode: the NNI hill climb of
+   -nni_pars (tools.cpp:2378-2382) and of the ratchet's first climb under -hclimb1_nni (iqtree.cpp:2106-2108), with the defaults
+   there (Fitch, nni5 off, leastSquareNNI off).  Every NNI is scored as computeParsimonyBranch scores it (phylotree.cpp:3177-3182,
+   getBestNNIForBran :3807-3980); a step scores the whole tree (evalNNIs, :3144-3159: pre-order from taxon root_taxon, 1-based --
+   IQ-TREE's root, id root_taxon - 1) or, with speednni (tools.cpp:765), the branches around the last step's moves (:2304-2311);
+   positive moves are ordered by std::sort on the length, non-conflicting ones applied together and rolled back when the tree got
+   longer than the best of them.  The tree is modified in place; node number = IQ-TREE id + 1, slot = position in neighbors[].
+   *score = final length (-curScore), *nni_count / *nni_steps as the reference leaves them (nni_steps = max_steps + 1 when the
+   cap is hit; the reference's MAXSTEPS is 50).  MPF_E_UNSUPPORTED on the weighted engine and with a UFBoot tracker attached,
+   MPF_E_STATE without a tree, MPF_E_INVALID for a root_taxon outside 1 .. n.  Options "nni_launches", "nni_rollbacks" and
+   "nni_branches_scored" count scoring launches, rolled-back steps and scored branches (mpf_get_option). */
+int mpf_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
+                     int32_t *nni_steps);
+/* one full evaluation of the current tree (evalNNIs(), iqtree.cpp:3144-3159, with getBestNNIForBran, phylotree.cpp:3807-3980):
+   branch i in the reference's order joins node1[i] and node2[i] (node numbers); len[2i + k] = tree length after its move k (k = 0:
+   node1's first neighbour other than node2 swapped with node2's first other neighbour, k = 1: with its second).  *n = number of
+   inner branches, always set; the arrays are filled when cap >= *n. */
+int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len /* [2 * cap] */,
+                   int32_t *n);
+/* every swap (PhyloTree::doNNI, phylotree.cpp:3715-3742) the last mpf_optimize_nni made, in order, the reverting swaps of a
+   rollback (iqtree.cpp:2271-2272) included: the neighbours in slot1[i] of node1[i] and slot2[i] of node2[i] traded places.
+   Replaying them on the start tree gives the final tree.  *n is always set; the arrays are filled up to cap entries. */
+int mpf_get_nni_moves(const mpf_engine *e, int32_t cap, int32_t *node1, int32_t *slot1, int32_t *node2, int32_t *slot2, int32_t *n);
+
 /* accepted moves of the last mpf_optimize_spr / mpf_make_parsimony_tree: (remove rec, insert rec, length) */
 int mpf_get_moves(const mpf_engine *e, int32_t cap, int32_t *remove_rec, int32_t *insert_rec, uint32_t *score,
                   int32_t *n_moves);

@@ -56,3 +56,24 @@ struct mpf_phylotree_hooks {
 
 void mpfitch_phylotree_install(const mpf_phylotree_hooks *hooks);
 void mpfitch_phylotree_release(void);                     // frees the engines (end of the run / new alignment set)
+
+// ---- the NNI hill climb (IQTree::optimizeNNI in MP mode; INTEGRATION.md "NNI climb").  A table of its own, so that the one above
+// and its users stay as they are.
+//     static void hk_swap(PhyloTree *t, int id1, int slot1, int id2, int slot2)     // PhyloTree::doNNI on the host's tree
+//         { Node *n1 = node_of(t, id1), *n2 = node_of(t, id2); NeighborVec::iterator i1 = n1->neighbors.begin() + slot1,
+//           i2 = n2->neighbors.begin() + slot2; NNIMove m; m.node1 = (PhyloNode *)n1; m.node2 = (PhyloNode *)n2;
+//           m.node1Nei_it = i1; m.node2Nei_it = i2; t->doNNI(m); }
+//     static int  hk_speednni(const PhyloTree *t) { return ((IQTree *)t)->searchinfo.speednni; }
+//     ... mpfitch_phylotree_install_nni(&nni_hooks);
+struct mpf_phylotree_nni_hooks {
+  // the neighbours in neighbors[slot1] of node id1 and neighbors[slot2] of node id2 trade places, the back links of the two
+  // subtree roots follow (PhyloTree::doNNI, phylotree.cpp:3715-3742)
+  void (*swap)(PhyloTree *, int id1, int slot1, int id2, int slot2);
+  // optional (may be NULL = on): searchinfo.speednni (tools.cpp:765)
+  int (*speednni)(const PhyloTree *);
+};
+void mpfitch_phylotree_install_nni(const mpf_phylotree_nni_hooks *hooks);
+// IQTree::optimizeNNI(nni_count, nni_steps) (iqtree.cpp:2173-2302) on the engine: the tree is marshalled as computeParsimony()
+// marshals it, climbed by mpf_optimize_nni from the root leaf (hook root_id, else taxon 0) and the engine's swaps are replayed on
+// the host's tree through the swap hook.  Returns the final length (curScore = -length).
+int mpfitch_optimize_nni(PhyloTree *t, int *nni_count, int *nni_steps);

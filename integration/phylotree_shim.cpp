@@ -153,7 +153,40 @@ int compute(PhyloTree *t, const unsigned int *cost)
   return (int)score;
 }
 
+mpf_phylotree_nni_hooks g_nni;
+bool g_nni_installed = false;
+
 }  // namespace
+
+void mpfitch_phylotree_install_nni(const mpf_phylotree_nni_hooks *hooks)
+{
+  g_nni = *hooks;
+  g_nni_installed = hooks->swap != nullptr;
+}
+
+// IQTree::optimizeNNI (iqtree.cpp:2173-2302), MP mode, MAXSTEPS 50: the climb runs on the engine, its swaps are replayed here
+int mpfitch_optimize_nni(PhyloTree *t, int *nni_count, int *nni_steps)
+{
+  if (!g_nni_installed) { std::fprintf(stderr, "mpfitch phylotree shim: mpfitch_phylotree_install_nni() was not called\n"); std::exit(EXIT_FAILURE); }
+  mpf_engine *e = engine_for(t, nullptr);
+  const int n = g_h.n_taxa(t);
+  std::vector<int32_t> back;
+  marshal_tree(t, n, back);
+  if (mpf_set_tree(e, back.data())) die("mpf_set_tree");
+  const int root = g_h.root_id ? g_h.root_id(t) : 0;
+  if (root < 0 || root >= n) { std::fprintf(stderr, "mpfitch phylotree shim: root %d is not a leaf id\n", root); std::exit(EXIT_FAILURE); }
+  const int speednni = g_nni.speednni ? g_nni.speednni(t) : 1;
+  uint32_t score = 0;
+  int32_t count = 0, steps = 0, k = 0;
+  if (mpf_optimize_nni(e, root + 1, speednni, 50, &score, &count, &steps)) die("mpf_optimize_nni");
+  if (mpf_get_nni_moves(e, 0, nullptr, nullptr, nullptr, nullptr, &k)) die("mpf_get_nni_moves");
+  std::vector<int32_t> n1((size_t)k), s1((size_t)k), n2((size_t)k), s2((size_t)k);
+  if (k && mpf_get_nni_moves(e, k, n1.data(), s1.data(), n2.data(), s2.data(), &k)) die("mpf_get_nni_moves");
+  for (int i = 0; i < k; i++) g_nni.swap(t, n1[(size_t)i] - 1, s1[(size_t)i], n2[(size_t)i] - 1, s2[(size_t)i]);   // node number = id + 1
+  if (nni_count) *nni_count = count;
+  if (nni_steps) *nni_steps = steps;
+  return (int)score;
+}
 
 void mpfitch_phylotree_install(const mpf_phylotree_hooks *hooks)
 {

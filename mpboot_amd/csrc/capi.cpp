@@ -274,6 +274,51 @@ int mpf_stepwise_addition(mpf_engine *e, int64_t seed, uint32_t *best_per_step, 
   return e->eng.stepwise_addition(seed, best_per_step, insert_per_step, score);
 }
 
+// IQTree::optimizeNNI (reference iqtree.cpp:2173-2302), MP mode
+int mpf_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
+                     int32_t *nni_steps)
+{
+  NEED(e);
+  return e->eng.optimize_nni(root_taxon, speednni != 0, max_steps, score, nni_count, nni_steps);
+}
+
+// IQTree::evalNNIs() (iqtree.cpp:3144-3159) with getBestNNIForBran (phylotree.cpp:3807-3980)
+int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> l;
+  const int rc = e->eng.nni_scores(root_taxon, br, l);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !len)) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    len[2 * i] = l[2 * i];
+    len[2 * i + 1] = l[2 * i + 1];
+  }
+  return MPF_OK;
+}
+
+// the PhyloTree::doNNI calls (phylotree.cpp:3715-3742) of the last climb
+int mpf_get_nni_moves(const mpf_engine *e, int32_t cap, int32_t *node1, int32_t *slot1, int32_t *node2, int32_t *slot2, int32_t *n)
+{
+  NEED(e);
+  const auto &lg = e->eng.nni_log();
+  if (n) *n = (int32_t)lg.size();
+  const size_t k = std::min((size_t)std::max(cap, 0), lg.size());
+  for (size_t i = 0; i < k; i++) {
+    if (node1) node1[i] = lg[i].node1;
+    if (slot1) slot1[i] = lg[i].slot1;
+    if (node2) node2[i] = lg[i].node2;
+    if (slot2) slot2[i] = lg[i].slot2;
+  }
+  return MPF_OK;
+}
+
 int mpf_get_moves(const mpf_engine *e, int32_t cap, int32_t *remove_rec, int32_t *insert_rec, uint32_t *score, int32_t *n_moves)
 {
   NEED(e);

@@ -2111,6 +2111,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "grow_device") { grow_device_ = v ? 1 : 0; return MPF_OK; }
   if (key == "grow_tile") { if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8 && v != -1) { set_error("grow_tile: 0 (word-major copy where there is one, else fitted), -1 (fitted quad tiles), 1, 2, 4 or 8"); return MPF_E_INVALID; } grow_vw_ = (int)v; return MPF_OK; }
   if (key == "grow_fault") { grow_fault_ = v; return MPF_OK; }
+  if (key == "nni_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("nni_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } nni_vw_ = (int)v; return MPF_OK; }
   if (key == "max_visits") { max_visits_ = std::max<int64_t>(0, v); return MPF_OK; }
   if (key == "small_batch_max") { small_batch_max_ = (int)std::max<int64_t>(1, std::min<int64_t>(v, 1 << 30)); return MPF_OK; }
   if (key == "ufb_moot") { ufb_moot_ = v ? 1 : 0; return MPF_OK; }
@@ -2209,6 +2210,10 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "grow_device") *v = grow_device_;
   else if (key == "grow_tile") *v = grow_vw_;
   else if (key == "grow_launches") *v = (int64_t)grow_launches_;
+  else if (key == "nni_tile") *v = nni_vw_;
+  else if (key == "nni_launches") *v = (int64_t)nni_launches_;
+  else if (key == "nni_rollbacks") *v = (int64_t)nni_rollbacks_;
+  else if (key == "nni_branches_scored") *v = (int64_t)nni_branches_;
   else if (key == "grow_steps") *v = (int64_t)grow_steps_;
   else if (key == "grow_us") *v = (int64_t)(grow_ms_total_ * 1000.0);
   else if (key == "grow_last_err") *v = grow_last_err_;

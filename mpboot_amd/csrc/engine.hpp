@@ -316,6 +316,14 @@ class Engine {
   int stepwise_addition(int64_t seed, uint32_t *best_per_step, int32_t *insert_per_step, uint32_t *score);
   const std::vector<Move> &moves() const { return moves_; }
 
+  // ---- NNI hill climb (host/nni.cpp; reference IQTree::optimizeNNI, iqtree.cpp:2173-2302, in MP mode)
+  // a move / a logged swap: the neighbours in slot1 of node1 and slot2 of node2 trade places (PhyloTree::doNNI, phylotree.cpp:3715)
+  struct NniSwap { int32_t node1, slot1, node2, slot2; };
+  struct NniBranch { int32_t node1, node2; };    // node numbers (IQ-TREE id + 1)
+  int optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t *score, int32_t *nni_count, int32_t *nni_steps);
+  int nni_scores(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len);   // one full evaluation, len[2 * i + k]
+  const std::vector<NniSwap> &nni_log() const { return nni_log_; }
+
   // ---- online UFBoot-MP bookkeeping (host/ufboot.cpp; reference IQTree::saveCurrentTree, iqtree.cpp:3271-3785)
   int ufboot_attach(int n_samples, const uint16_t *samples, double epsilon, int n_local = -1, const int32_t *sample_ids = nullptr,
                     mpf_ufb_exchange_fn exchange = nullptr, void *exchange_arg = nullptr);
@@ -459,6 +467,21 @@ class Engine {
   void ufb_store_tree(int64_t tree_index, int remove_rec, int insert_rec);
   void ufb_candidate_topology(int remove_rec, int insert_rec, std::vector<int32_t> &bk) const;
   void ufb_flush_pending(const ScanPlan &pl);
+
+  // NNI climb state: the swap log of the last climb, the kernel shape (option "nni_tile") and the counters behind the options
+  // nni_launches / nni_rollbacks / nni_branches_scored
+  struct NniScored { NniSwap mv; uint32_t len; };
+  int nni_check(int root_taxon) const;
+  int nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<NniSwap> *moves);
+  void nni_full_order(int root_taxon, std::vector<NniBranch> &br) const;
+  void nni_swap(const NniSwap &m);
+  std::vector<NniSwap> nni_log_;
+  int nni_vw_ = -1;                              // option "nni_tile": -1 = from the geometry, 0 = word-major copy where current, 1 | 2 | 4 = row-major words per lane
+  uint64_t nni_launches_ = 0, nni_rollbacks_ = 0, nni_branches_ = 0;
+  DevBuf<NniDesc> d_nni_desc_;
+  DevBuf<unsigned long long> d_nni_out_;
+  PinBuf<NniDesc> h_nni_desc_;
+  PinBuf<unsigned long long> h_nni_out_;
 
   int addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *insert_per_step);
   void apply_move(int remove_rec, int insert_rec);

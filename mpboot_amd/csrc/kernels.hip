@@ -937,6 +937,50 @@ __global__ __launch_bounds__(256) void k_evaluate(const uint32_t *__restrict__ v
   if (lane == 0 && tot) atomic_add_u32(out + o.out, tot);
 }
 
+// ---------------------------------------------------------------- NNI scoring (IQTree::optimizeNNI, host/nni.cpp)
+//
+// Branch i joins node1 (subtrees A, B) and node2 (C0, C1).  Move k swaps A with C_k; what it adds to the four subtree scores is
+//   steps(B + C_k) + steps(A + C_{1-k}) + steps((B + C_k) + (A + C_{1-k}))
+// (getBestNNIForBran, reference phylotree.cpp:3807-3980, scored by computeParsimonyBranch at node1--node2).  A wave loads the four
+// vectors of its tile once and keeps both joins in registers; out[i] = move 0's count (low word) | move 1's (high word), one 64-bit
+// atomic per (branch, tile) -- the low word is a tree length and never carries into the high one.
+// WM: `vec` is the word-major copy (Geometry::shoff), one 16-byte load per lane and vector (DNA, one word per lane).
+template <int S, int VW, int RED, bool WM>
+__global__ __launch_bounds__(256) void k_nni_eval(const uint32_t *__restrict__ vec, const NniDesc *__restrict__ desc,
+                                                  int n_br, unsigned long long *__restrict__ out, int Wp, int tiles)
+{
+  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
+  const int lane = threadIdx.x & 63;
+  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  gw = __builtin_amdgcn_readfirstlane(gw);
+  if (gw >= n_br * tiles) return;
+  const int br = gw / tiles, tile = gw - br * tiles;
+  const NniDesc d = desc[br];
+  bool valid;
+  const int w0 = lane_word<VW>(tile, lane, Wp, valid);
+  Tile<S, VW> a, b, c0, c1;
+  if constexpr (WM) {
+    auto ld = [&](Tile<S, VW> &t, uint32_t cid) {
+      const uint4 x = *reinterpret_cast<const uint4 *>(vec + (size_t)cid * (size_t)(4 * Wp) + (size_t)w0 * 4);
+      t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
+    };
+    ld(a, d.a); ld(b, d.b); ld(c0, d.c0); ld(c1, d.c1);
+  } else {
+    load_tile<S, VW>(a, vec, d.a, Wp, w0);
+    load_tile<S, VW>(b, vec, d.b, Wp, w0);
+    load_tile<S, VW>(c0, vec, d.c0, Wp, w0);
+    load_tile<S, VW>(c1, vec, d.c1, Wp, w0);
+  }
+  Tile<S, VW> x, y;
+  uint32_t m0 = fitch<S, VW>(x, b, c0) + fitch<S, VW>(y, a, c1);
+  m0 += empty_count<S, VW>(x, y);
+  uint32_t m1 = fitch<S, VW>(x, b, c1) + fitch<S, VW>(y, a, c0);
+  m1 += empty_count<S, VW>(x, y);
+  const uint32_t t0 = wave_total<RED>(valid ? m0 : 0u), t1 = wave_total<RED>(valid ? m1 : 0u);
+  if (lane == 0 && (t0 | t1))
+    __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---------------------------------------------------------------- K4: per-pattern scores
 //
 // Per-site Fitch length = number of (a, b) joins of the rooted traversal whose state sets do not
@@ -2503,6 +2547,29 @@ hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *ve
       hipLaunchKernelGGL((k_evaluate<S, VW, RED>), grid, block, 0, st, vec, ops, n_ops, out, g.Wp, tiles);
     });
   });
+  return hipGetLastError();
+}
+
+hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
+                           unsigned long long *out, int vw, bool word_major)
+{
+  if (n_br <= 0) return hipSuccess;
+  if (g.sankoff) return hipErrorInvalidValue;
+  const bool wm = word_major && g.S == 4 && g.shoff;
+  if (g.S != 4 || wm) vw = 1;
+  if (vw != 1 && vw != 2 && vw != 4) return hipErrorInvalidValue;
+  const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
+  const long waves = (long)n_br * tiles;
+  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  auto launch = [&](auto S, auto VW, auto WM) {
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_nni_eval<S, VW, RED, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, desc, n_br, out, g.Wp, tiles);
+    });
+  };
+  if (wm) launch(int_c<4>(), int_c<1>(), bool_c<true>());
+  else if (g.S == 4 && vw == 2) launch(int_c<4>(), int_c<2>(), bool_c<false>());
+  else if (g.S == 4 && vw == 4) launch(int_c<4>(), int_c<4>(), bool_c<false>());
+  else dispatch_states(g.S, [&](auto S) { launch(S, int_c<1>(), bool_c<false>()); });
   return hipGetLastError();
 }
 

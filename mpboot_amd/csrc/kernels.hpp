@@ -196,6 +196,13 @@ int newview_tile(const Geometry &g);
 int tiles_for_levels(const Geometry &g);      // tiles (rows of cntp) launch_newview_levels uses: 32-word tiles for one word per lane
 hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *vec, const EvOp *ops, int n_ops,
                            uint32_t *out);
+// NNI scoring: the two moves of every branch (cids of the subtrees A, B at node1 and C0, C1 at node2; move k swaps A with C_k).
+// out[i] (zeroed by the caller) = steps of move 0 | steps of move 1 << 32, the subtrees' own scores not included.
+// vw = words per lane of the row-major store (1 | 2 | 4, DNA; other alphabets run 1); word_major: read DNA from the word-major
+// copy (Geometry::shoff), which the caller knows to be current
+struct NniDesc { uint32_t a, b, c0, c1; };
+hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
+                           unsigned long long *out, int vw, bool word_major);
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,
                        const ScanOp *ops, uint32_t *out, int max_depth,
                        uint32_t *host_out = nullptr, uint32_t n_out = 0, uint32_t *done = nullptr,   // as launch_scan_walk

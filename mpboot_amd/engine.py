@@ -34,6 +34,7 @@ EXPORTS = [
     "mpf_min_pars_score_patterns", "mpf_mst_scores", "mpf_segment_patterns", "mpf_remain_bounds",
     "mpf_cost_matrix_load", "mpf_cost_matrix_triangle_fix",
     "mpf_iq_random_nnis", "mpf_iq_perturb_weights", "mpf_iq_topology_key", "mpf_ufboot_adopt", "mpf_optimize_spr_many", "mpf_optimize_spr_many_round",
+    "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves",
 ]
 
 
@@ -164,6 +165,9 @@ def load_library():
         L.mpf_iq_random_nnis.argtypes = [C.c_int32, vp, C.c_int32, vp, vp]
         L.mpf_iq_perturb_weights.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
         L.mpf_iq_topology_key.argtypes = [C.c_int32, vp, vp]
+        L.mpf_optimize_nni.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+        L.mpf_nni_scores.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.mpf_get_nni_moves.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -551,6 +555,36 @@ class FitchEngine:
         if k.value:
             _chk(L.mpf_get_moves(self.h, k.value, _p(a), _p(b), _p(s), C.byref(k)))
         return a, b, s
+
+    # ---- NNI hill climb (IQTree::optimizeNNI in MP mode: -nni_pars, -hclimb1_nni)
+    def optimize_nni(self, root_taxon: int = 1, speednni: bool = True, max_steps: int = 50):
+        """-> (length, nni_count, nni_steps); the tree is modified in place"""
+        s, cnt, steps = C.c_uint32(), C.c_int32(), C.c_int32()
+        _chk(load_library().mpf_optimize_nni(self.h, root_taxon, int(bool(speednni)), max_steps, C.byref(s), C.byref(cnt),
+                                             C.byref(steps)))
+        return s.value, cnt.value, steps.value
+
+    def nni_scores(self, root_taxon: int = 1):
+        """one full evaluation: (node1[m], node2[m], len[m][2]) for the m inner branches in evalNNIs() order"""
+        L = load_library()
+        n = C.c_int32()
+        _chk(L.mpf_nni_scores(self.h, root_taxon, 0, None, None, None, C.byref(n)))
+        m = n.value
+        a = np.zeros(max(m, 1), dtype=np.int32)
+        b = np.zeros(max(m, 1), dtype=np.int32)
+        ln = np.zeros(2 * max(m, 1), dtype=np.uint32)
+        _chk(L.mpf_nni_scores(self.h, root_taxon, m, _p(a), _p(b), _p(ln), C.byref(n)))
+        return a[:m].copy(), b[:m].copy(), ln[:2 * m].reshape(m, 2).copy()
+
+    def nni_moves(self):
+        """the swaps of the last optimize_nni, reverts included: int32[k][4] rows (node1, slot1, node2, slot2)"""
+        L = load_library()
+        k = C.c_int32()
+        _chk(L.mpf_get_nni_moves(self.h, 0, None, None, None, None, C.byref(k)))
+        cols = [np.zeros(max(k.value, 1), dtype=np.int32) for _ in range(4)]
+        if k.value:
+            _chk(L.mpf_get_nni_moves(self.h, k.value, *[_p(c) for c in cols], C.byref(k)))
+        return np.stack([c[:k.value] for c in cols], axis=1) if k.value else np.zeros((0, 4), dtype=np.int32)
 
     # ---- online UFBoot-MP bookkeeping (IQTree::saveCurrentTree during optimize_spr)
     def ufboot_attach(self, samples, epsilon: float = 0.5, shard=None, exchange=None):
