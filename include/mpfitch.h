@@ -242,9 +242,10 @@ int mpf_stepwise_addition(mpf_engine *e, int64_t seed, uint32_t *best_per_step /
    positive moves are ordered by std::sort on the length, non-conflicting ones applied together and rolled back when the tree got
    longer than the best of them.  The tree is modified in place; node number = IQ-TREE id + 1, slot = position in neighbors[].
    *score = final length (-curScore), *nni_count / *nni_steps as the reference leaves them (nni_steps = max_steps + 1 when the
-   cap is hit; the reference's MAXSTEPS is 50).  MPF_E_UNSUPPORTED on the weighted engine and with a UFBoot tracker attached,
-   MPF_E_STATE without a tree, MPF_E_INVALID for a root_taxon outside 1 .. n.  Options "nni_launches", "nni_rollbacks" and
-   "nni_branches_scored" count scoring launches, rolled-back steps and scored branches (mpf_get_option). */
+   cap is hit; the reference's MAXSTEPS is 50).  MPF_E_UNSUPPORTED on the weighted engine and with a UFBoot tracker attached (the
+   climb under -bb is mpf_ufboot_optimize_nni), MPF_E_STATE without a tree, MPF_E_INVALID for a root_taxon outside 1 .. n.
+   Options "nni_launches", "nni_rollbacks" and "nni_branches_scored" count scoring launches, rolled-back steps and scored
+   branches (mpf_get_option). */
 int mpf_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
                      int32_t *nni_steps);
 /* one full evaluation of the current tree (evalNNIs(), iqtree.cpp:3144-3159, with getBestNNIForBran, phylotree.cpp:3807-3980):
@@ -253,10 +254,33 @@ int mpf_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_
    inner branches, always set; the arrays are filled when cap >= *n. */
 int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len /* [2 * cap] */,
                    int32_t *n);
+/* DIAGNOSTIC, for tests of the kernel alone -- no part of mpboot's flow, and nothing a host should build on: mpf_nni_scores by
+   the mask-writing kernel of the tracked climb (k_nni_eval_masks), with what it writes for the tracker read back per pattern: terms[(3 i + r) * n_patterns + p] = number (0..3) of the three joins at branch i without a common state at
+   pattern p -- r = 0: in the current tree, r = 1 / 2: after move 0 / 1.  Per pattern, length(tree after move k) = length(current
+   tree) - terms[3 i] + terms[3 i + 1 + k].  0 for patterns the engine drops.  Filled when cap >= *n. */
+int mpf_nni_pattern_terms(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len /* [2 * cap] */,
+                          uint8_t *terms /* [3 * cap][n_patterns] */, int32_t *n);
 /* every swap (PhyloTree::doNNI, phylotree.cpp:3715-3742) the last mpf_optimize_nni made, in order, the reverting swaps of a
    rollback (iqtree.cpp:2271-2272) included: the neighbours in slot1[i] of node1[i] and slot2[i] of node2[i] traded places.
    Replaying them on the start tree gives the final tree.  *n is always set; the arrays are filled up to cap entries. */
 int mpf_get_nni_moves(const mpf_engine *e, int32_t cap, int32_t *node1, int32_t *slot1, int32_t *node2, int32_t *slot2, int32_t *n);
+/* The same climb under -bb (save_all_trees == 2), with the UFBoot tracker of mpf_ufboot_attach booking every tree the climb looks
+   at through IQTree::saveCurrentTree, in the reference's order: at the start of every step that is not a rollback step the current
+   tree with curScore (iqtree.cpp:2181-2183), then for every branch the step evaluates, in evaluation order, the tree after move 0
+   and the tree after move 1 with the length optimizeOneBranch returned (getBestNNIForBran, phylotree.cpp:3907-3939) -- all of
+   them, not only the positive ones; nothing in a rollback step.  pllComputePatternParsimony is skipped on this path
+   (iqtree.cpp:3363), _pattern_pars is the booked tree's own row (phylotree.cpp:956-957, :986-987): on a re-weighted (ratchet)
+   climb the length the cut-off test sees and treels_logl records is the booked tree's OWN length on the attach-time weights
+   (iqtree.cpp:3283-3294), and a tree that fails the cut-off closes no gate.  The tracker's tie draws come from the shared stream
+   (mpf_seed_ties / mpf_set_tie_state / mpf_set_rand) in this booking order; the climb itself draws nothing.  Lengths are the
+   engine's: patterns it drops (keep_all_sites 0) count 0.
+   Served: the default update rule, -mulhits, mpf_ufboot_set_cutoff, -cutoff_from_btrees, ratchet booking; under
+   mpf_ufboot_set_ratchet_booking(e, 0) a re-weighted climb runs without booking (the plain climb).  NOT served, MPF_E_UNSUPPORTED:
+   -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, the weighted engine.
+   Arguments, results, swap log (mpf_get_nni_moves) and counters as mpf_optimize_nni; MPF_E_STATE without a tracker or a tree.
+   Read-only option "nni_booked": trees NNI climbs have handed to saveCurrentTree since the attach. */
+int mpf_ufboot_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
+                            int32_t *nni_steps);
 
 /* accepted moves of the last mpf_optimize_spr / mpf_make_parsimony_tree: (remove rec, insert rec, length) */
 int mpf_get_moves(const mpf_engine *e, int32_t cap, int32_t *remove_rec, int32_t *insert_rec, uint32_t *score,

@@ -282,6 +282,14 @@ int mpf_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_
   return e->eng.optimize_nni(root_taxon, speednni != 0, max_steps, score, nni_count, nni_steps);
 }
 
+// IQTree::optimizeNNI with save_all_trees == 2 (-bb): saveCurrentTree at iqtree.cpp:2181-2183 and phylotree.cpp:3907-3939
+int mpf_ufboot_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
+                            int32_t *nni_steps)
+{
+  NEED(e);
+  return e->eng.ufboot_optimize_nni(root_taxon, speednni != 0, max_steps, score, nni_count, nni_steps);
+}
+
 // IQTree::evalNNIs() (iqtree.cpp:3144-3159) with getBestNNIForBran (phylotree.cpp:3807-3980)
 int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len, int32_t *n)
 {
@@ -300,6 +308,29 @@ int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node
     len[2 * i] = l[2 * i];
     len[2 * i + 1] = l[2 * i + 1];
   }
+  return MPF_OK;
+}
+
+// mpf_nni_scores by the mask-writing kernel of the tracked climb, its rows per pattern
+int mpf_nni_pattern_terms(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len, uint8_t *terms, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> l;
+  std::vector<uint8_t> t;
+  const int rc = e->eng.nni_pattern_terms(root_taxon, br, l, t);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !len || !terms)) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    len[2 * i] = l[2 * i];
+    len[2 * i + 1] = l[2 * i + 1];
+  }
+  std::copy(t.begin(), t.end(), terms);
   return MPF_OK;
 }
 

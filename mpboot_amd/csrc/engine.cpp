@@ -2214,6 +2214,7 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "nni_launches") *v = (int64_t)nni_launches_;
   else if (key == "nni_rollbacks") *v = (int64_t)nni_rollbacks_;
   else if (key == "nni_branches_scored") *v = (int64_t)nni_branches_;
+  else if (key == "nni_booked") *v = ufb_ ? (int64_t)ufb_->nni_booked : 0;
   else if (key == "grow_steps") *v = (int64_t)grow_steps_;
   else if (key == "grow_us") *v = (int64_t)(grow_ms_total_ * 1000.0);
   else if (key == "grow_last_err") *v = grow_last_err_;

@@ -157,6 +157,7 @@ struct UfbState : books::Deferred {      // (boot_trees, store, refs, topo_index
   double t_defer = 0;
   const std::vector<ScanPlan> *log_plans = nullptr;
   uint64_t draws = 0, events = 0, gemm_rows = 0, batches = 0, stored = 0;
+  uint64_t nni_booked = 0;                       // trees NNI climbs have handed to saveCurrentTree (read-only option "nni_booked")
   double gemm_ms = 0.0;
   double t_lookup = 0;                           // ... of t_replay: canonical forms for the topology map
   uint64_t lookups = 0;
@@ -323,6 +324,10 @@ class Engine {
   int optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t *score, int32_t *nni_count, int32_t *nni_steps);
   int nni_scores(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len);   // one full evaluation, len[2 * i + k]
   const std::vector<NniSwap> &nni_log() const { return nni_log_; }
+  int nni_pattern_terms(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<uint8_t> &terms);
+  // the same climb under -bb: every tree it looks at is booked by the attached UFBoot tracker (save_all_trees == 2: the current
+  // tree at the start of every scoring step, iqtree.cpp:2181-2183, and both NNIs of every evaluated branch, phylotree.cpp:3937)
+  int ufboot_optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t *score, int32_t *nni_count, int32_t *nni_steps);
 
   // ---- online UFBoot-MP bookkeeping (host/ufboot.cpp; reference IQTree::saveCurrentTree, iqtree.cpp:3271-3785)
   int ufboot_attach(int n_samples, const uint16_t *samples, double epsilon, int n_local = -1, const int32_t *sample_ids = nullptr,
@@ -472,13 +477,19 @@ class Engine {
   // nni_launches / nni_rollbacks / nni_branches_scored
   struct NniScored { NniSwap mv; uint32_t len; };
   int nni_check(int root_taxon) const;
-  int nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<NniSwap> *moves);
+  int nni_check_tree(int root_taxon) const;      // ... without the refusal of a tracker
+  // masks: the mask-writing kernel, its rows into d_nni_planes_
+  int nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<NniSwap> *moves, bool masks = false);
+  int nni_climb(int root_taxon, bool speednni, int max_steps, bool tracked, uint32_t *score, int32_t *nni_count, int32_t *nni_steps);
+  // saveCurrentTree for the 1 + 2 * branches trees of one scoring step (cur = the current tree's length)
+  int nni_book_step(const std::vector<NniBranch> &br, const std::vector<uint32_t> &len, const std::vector<NniSwap> &mv, uint32_t cur);
   void nni_full_order(int root_taxon, std::vector<NniBranch> &br) const;
   void nni_swap(const NniSwap &m);
   std::vector<NniSwap> nni_log_;
   int nni_vw_ = -1;                              // option "nni_tile": -1 = from the geometry, 0 = word-major copy where current, 1 | 2 | 4 = row-major words per lane
   uint64_t nni_launches_ = 0, nni_rollbacks_ = 0, nni_branches_ = 0;
   DevBuf<NniDesc> d_nni_desc_;
+  DevBuf<uint32_t> d_nni_planes_;                // k_nni_eval_masks: [2 planes][3 rows per branch, padded to the product's row tile][Wp]
   DevBuf<unsigned long long> d_nni_out_;
   PinBuf<NniDesc> h_nni_desc_;
   PinBuf<unsigned long long> h_nni_out_;

@@ -981,6 +981,101 @@ __global__ __launch_bounds__(256) void k_nni_eval(const uint32_t *__restrict__ v
     __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// c = fitch(a, b), m = the "no common state" words of the join; returns their popcount
+template <int S, int VW>
+__device__ __forceinline__ uint32_t fitch_mask(Tile<S, VW> &c, const Tile<S, VW> &a, const Tile<S, VW> &b, uint32_t (&m)[VW])
+{
+  uint32_t cost = 0;
+#pragma unroll
+  for (int j = 0; j < VW; j++) {
+    uint32_t any = a.v[0][j] & b.v[0][j];
+#pragma unroll
+    for (int k = 1; k < S; k++) any = b3_andor(a.v[k][j], b.v[k][j], any);
+#pragma unroll
+    for (int k = 0; k < S; k++) c.v[k][j] = b3_fitch(a.v[k][j], b.v[k][j], any);
+    m[j] = ~any;
+    cost += (uint32_t)__builtin_popcount(~any);
+  }
+  return cost;
+}
+
+// one row of VW words per lane: a wave writes 64 * VW consecutive words (dword / dwordx2 / dwordx4 per lane)
+template <int VW>
+__device__ __forceinline__ void store_row(uint32_t *__restrict__ p, const uint32_t (&w)[VW])
+{
+  if constexpr (VW == 1) p[0] = w[0];
+  else if constexpr (VW == 2) *reinterpret_cast<uint2 *>(p) = make_uint2(w[0], w[1]);
+  else *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// The three joins an NNI changes, as a per-site count 0..3 in two bit planes: m0 + m1 + m2 = p0 + 2 * p1
+template <int S, int VW>
+__device__ __forceinline__ uint32_t three_joins(const Tile<S, VW> &p, const Tile<S, VW> &q, const Tile<S, VW> &r, const Tile<S, VW> &s,
+                                                uint32_t (&p0)[VW], uint32_t (&p1)[VW])
+{
+  Tile<S, VW> x, y;
+  uint32_t m0[VW], m1[VW];
+  uint32_t cost = fitch_mask<S, VW>(x, p, q, m0) + fitch_mask<S, VW>(y, r, s, m1);
+#pragma unroll
+  for (int j = 0; j < VW; j++) {
+    uint32_t any = x.v[0][j] & y.v[0][j];
+#pragma unroll
+    for (int k = 1; k < S; k++) any = b3_andor(x.v[k][j], y.v[k][j], any);
+    const uint32_t m2 = ~any;
+    cost += (uint32_t)__builtin_popcount(m2);
+    p0[j] = m0[j] ^ m1[j] ^ m2;
+    p1[j] = (m0[j] & m1[j]) | (m2 & (m0[j] | m1[j]));
+  }
+  return cost;
+}
+
+// k_nni_eval for a tracked climb (IQTree::saveCurrentTree for every evaluated NNI, reference phylotree.cpp:3937): the same loads
+// and the same two counts, and besides them what the UFBoot tracker needs to form per site
+//   pattern_pars(T after move k) = pattern_pars(T) - h + c_k
+// h = m(A, B) + m(C0, C1) + m(A + B, C0 + C1) (the three joins of T at this branch), c_k those of the swapped tree; m = the
+// 1-bit-per-site "no common state" mask of a join.  The per-site Fitch length of an unrooted tree does not depend on the root and
+// these three joins are the only ones an NNI changes.  h and c_k are 0..3: two bit planes each, rows 3 br (h), 3 br + 1 (c_0),
+// 3 br + 2 (c_1) of plane0 / plane1 ([3 n_br][Wp] words, word w = sites 32 w .., as k_join_masks writes its rows).
+template <int S, int VW, int RED, bool WM>
+__global__ __launch_bounds__(256) void k_nni_eval_masks(const uint32_t *__restrict__ vec, const NniDesc *__restrict__ desc,
+                                                        int n_br, unsigned long long *__restrict__ out, int Wp, int tiles,
+                                                        uint32_t *__restrict__ plane0, uint32_t *__restrict__ plane1)
+{
+  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
+  const int lane = threadIdx.x & 63;
+  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  gw = __builtin_amdgcn_readfirstlane(gw);
+  if (gw >= n_br * tiles) return;
+  const int br = gw / tiles, tile = gw - br * tiles;
+  const NniDesc d = desc[br];
+  bool valid;
+  const int w0 = lane_word<VW>(tile, lane, Wp, valid);
+  Tile<S, VW> a, b, c0, c1;
+  if constexpr (WM) {
+    auto ld = [&](Tile<S, VW> &t, uint32_t cid) {
+      const uint4 x = *reinterpret_cast<const uint4 *>(vec + (size_t)cid * (size_t)(4 * Wp) + (size_t)w0 * 4);
+      t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
+    };
+    ld(a, d.a); ld(b, d.b); ld(c0, d.c0); ld(c1, d.c1);
+  } else {
+    load_tile<S, VW>(a, vec, d.a, Wp, w0);
+    load_tile<S, VW>(b, vec, d.b, Wp, w0);
+    load_tile<S, VW>(c0, vec, d.c0, Wp, w0);
+    load_tile<S, VW>(c1, vec, d.c1, Wp, w0);
+  }
+  const size_t row = (size_t)(3 * br) * (size_t)Wp + (size_t)w0;
+  uint32_t p0[VW], p1[VW];
+  (void)three_joins<S, VW>(a, b, c0, c1, p0, p1);
+  if (valid) { store_row<VW>(plane0 + row, p0); store_row<VW>(plane1 + row, p1); }
+  const uint32_t m0 = three_joins<S, VW>(b, c0, a, c1, p0, p1);
+  if (valid) { store_row<VW>(plane0 + row + Wp, p0); store_row<VW>(plane1 + row + Wp, p1); }
+  const uint32_t m1 = three_joins<S, VW>(b, c1, a, c0, p0, p1);
+  if (valid) { store_row<VW>(plane0 + row + 2 * (size_t)Wp, p0); store_row<VW>(plane1 + row + 2 * (size_t)Wp, p1); }
+  const uint32_t t0 = wave_total<RED>(valid ? m0 : 0u), t1 = wave_total<RED>(valid ? m1 : 0u);
+  if (lane == 0 && (t0 | t1))
+    __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---------------------------------------------------------------- K4: per-pattern scores
 //
 // Per-site Fitch length = number of (a, b) joins of the rooted traversal whose state sets do not
@@ -2564,6 +2659,32 @@ hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *ve
   auto launch = [&](auto S, auto VW, auto WM) {
     dispatch_reduce(g, [&](auto RED) {
       hipLaunchKernelGGL((k_nni_eval<S, VW, RED, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, desc, n_br, out, g.Wp, tiles);
+    });
+  };
+  if (wm) launch(int_c<4>(), int_c<1>(), bool_c<true>());
+  else if (g.S == 4 && vw == 2) launch(int_c<4>(), int_c<2>(), bool_c<false>());
+  else if (g.S == 4 && vw == 4) launch(int_c<4>(), int_c<4>(), bool_c<false>());
+  else dispatch_states(g.S, [&](auto S) { launch(S, int_c<1>(), bool_c<false>()); });
+  return hipGetLastError();
+}
+
+// the same shapes as launch_nni_eval; plane0 / plane1: [3 * n_br][Wp] words each (k_nni_eval_masks)
+hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
+                                 unsigned long long *out, int vw, bool word_major, uint32_t *plane0, uint32_t *plane1)
+{
+  if (n_br <= 0) return hipSuccess;
+  if (g.sankoff || !plane0 || !plane1) return hipErrorInvalidValue;
+  const bool wm = word_major && g.S == 4 && g.shoff;
+  if (g.S != 4 || wm) vw = 1;
+  if (vw != 1 && vw != 2 && vw != 4) return hipErrorInvalidValue;
+  if (g.Wp % vw) return hipErrorInvalidValue;
+  const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
+  const long waves = (long)n_br * tiles;
+  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  auto launch = [&](auto S, auto VW, auto WM) {
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_nni_eval_masks<S, VW, RED, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, desc, n_br, out, g.Wp, tiles,
+                         plane0, plane1);
     });
   };
   if (wm) launch(int_c<4>(), int_c<1>(), bool_c<true>());

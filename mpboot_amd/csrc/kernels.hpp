@@ -203,6 +203,11 @@ hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *ve
 struct NniDesc { uint32_t a, b, c0, c1; };
 hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
                            unsigned long long *out, int vw, bool word_major);
+// ... for a tracked climb (k_nni_eval_masks): the same counts, and per branch i the per-site count 0..3 of "no common state" joins
+// among the three joins the NNI changes, as two bit planes: row 3 i = the current tree's three joins (h), rows 3 i + 1 / 3 i + 2 =
+// those of the tree after move 0 / move 1 (c_0, c_1); plane0 / plane1: [3 * n_br][Wp] words, sites in the order of launch_join_masks
+hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
+                                 unsigned long long *out, int vw, bool word_major, uint32_t *plane0, uint32_t *plane1);
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,
                        const ScanOp *ops, uint32_t *out, int max_depth,
                        uint32_t *host_out = nullptr, uint32_t n_out = 0, uint32_t *done = nullptr,   // as launch_scan_walk

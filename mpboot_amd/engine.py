@@ -34,7 +34,7 @@ EXPORTS = [
     "mpf_min_pars_score_patterns", "mpf_mst_scores", "mpf_segment_patterns", "mpf_remain_bounds",
     "mpf_cost_matrix_load", "mpf_cost_matrix_triangle_fix",
     "mpf_iq_random_nnis", "mpf_iq_perturb_weights", "mpf_iq_topology_key", "mpf_ufboot_adopt", "mpf_optimize_spr_many", "mpf_optimize_spr_many_round",
-    "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves",
+    "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves", "mpf_ufboot_optimize_nni", "mpf_nni_pattern_terms",
 ]
 
 
@@ -168,6 +168,8 @@ def load_library():
         L.mpf_optimize_nni.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
         L.mpf_nni_scores.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.mpf_get_nni_moves.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.mpf_ufboot_optimize_nni.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+        L.mpf_nni_pattern_terms.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -576,6 +578,20 @@ class FitchEngine:
         _chk(L.mpf_nni_scores(self.h, root_taxon, m, _p(a), _p(b), _p(ln), C.byref(n)))
         return a[:m].copy(), b[:m].copy(), ln[:2 * m].reshape(m, 2).copy()
 
+    def nni_pattern_terms(self, root_taxon: int = 1):
+        """nni_scores by the mask-writing kernel of the tracked climb: (node1[m], node2[m], len[m][2], terms[m][3][n_patterns]);
+        per pattern, length after move k of branch i = length of the current tree - terms[i][0] + terms[i][1 + k]"""
+        L = load_library()
+        n = C.c_int32()
+        _chk(L.mpf_nni_pattern_terms(self.h, root_taxon, 0, None, None, None, None, C.byref(n)))
+        m = n.value
+        a = np.zeros(max(m, 1), dtype=np.int32)
+        b = np.zeros(max(m, 1), dtype=np.int32)
+        ln = np.zeros(2 * max(m, 1), dtype=np.uint32)
+        t = np.zeros(3 * max(m, 1) * self.P, dtype=np.uint8)
+        _chk(L.mpf_nni_pattern_terms(self.h, root_taxon, m, _p(a), _p(b), _p(ln), _p(t), C.byref(n)))
+        return a[:m].copy(), b[:m].copy(), ln[:2 * m].reshape(m, 2).copy(), t[:3 * m * self.P].reshape(m, 3, self.P).copy()
+
     def nni_moves(self):
         """the swaps of the last optimize_nni, reverts included: int32[k][4] rows (node1, slot1, node2, slot2)"""
         L = load_library()
@@ -616,6 +632,14 @@ class FitchEngine:
         self._ufb_exchange = exchange            # keep the ctypes callback alive as long as the tracker
         _chk(load_library().mpf_ufboot_attach_sharded(self.h, self.ufb_B, len(ids), _p(ids), _p(local), float(epsilon),
                                                       C.cast(exchange, C.c_void_p), None))
+
+    def ufboot_optimize_nni(self, root_taxon: int = 1, speednni: bool = True, max_steps: int = 50):
+        """optimize_nni under -bb: the attached tracker books the current tree of every scoring step and both NNIs of every
+        evaluated branch (mpf_ufboot_optimize_nni) -> (length, nni_count, nni_steps)"""
+        s, cnt, steps = C.c_uint32(), C.c_int32(), C.c_int32()
+        _chk(load_library().mpf_ufboot_optimize_nni(self.h, root_taxon, int(bool(speednni)), max_steps, C.byref(s), C.byref(cnt),
+                                                    C.byref(steps)))
+        return s.value, cnt.value, steps.value
 
     def ufboot_refine_sweep(self, maxtrav: int, tie_seeds=None):
         """Batched bootstrap refinement (mpf_ufboot_refine_sweep): the first sweep of the SPR climb from the CURRENT tree under

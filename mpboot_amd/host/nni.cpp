@@ -10,7 +10,7 @@
 #include <map>
 #include <string>
 
-#include "../csrc/engine.hpp"
+#include "ufboot_common.hpp"
 
 namespace mpf {
 
@@ -30,6 +30,13 @@ int Engine::nni_check(int root_taxon) const
   // (saveCurrentTree from getBestNNIForBran, phylotree.cpp:3937): neither is served
   if (sankoff_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
   if (ufb_) { set_error("NNI climb: not served with a UFBoot tracker attached"); return MPF_E_UNSUPPORTED; }
+  return nni_check_tree(root_taxon);
+}
+
+// ... the part every NNI entry shares, whatever it makes of a tracker
+int Engine::nni_check_tree(int root_taxon) const
+{
+  if (sankoff_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
   if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
   if (root_taxon < 1 || root_taxon > n_) { set_error("NNI climb: root_taxon must be in 1 .. n_taxa"); return MPF_E_INVALID; }
   return MPF_OK;
@@ -54,7 +61,7 @@ void Engine::nni_full_order(int root_taxon, std::vector<NniBranch> &br) const
 // getBestNNIForBran for every branch (phylotree.cpp:3807-3980): a = node1's first neighbour other than node2 in slot order, b the
 // other, c0 / c1 node2's two in slot order; move k swaps a with c_k.  len[2i + k] = length of the tree after move k of branch i,
 // moves[2i + k] = that swap
-int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<NniSwap> *moves)
+int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<NniSwap> *moves, bool masks)
 {
   if (!views_valid_) { int rc = update_views(); if (rc) return rc; }
   const size_t nb = br.size();
@@ -87,7 +94,16 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
   int vw = nni_vw_ > 0 ? nni_vw_ : (nni_vw_ == 0 ? 1 : g_.vw);
   HIPCHK(hipMemcpyAsync(d_nni_desc_.p, h_nni_desc_.p, nb * sizeof(NniDesc), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(d_nni_out_.p, 0, nb * sizeof(unsigned long long), st_));
-  HIPCHK(launch_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm));
+  if (masks) {
+    // tracked climb: the two bit planes of (h, c_0, c_1) per branch, each padded to the product's row tile
+    const size_t rows_p = (size_t)round_up((int)(3 * nb), kUfbRowTile);
+    HIPCHK(d_nni_planes_.reserve(2 * rows_p * (size_t)g_.Wp));
+    // (the padding rows are multiplied along with the others when a product takes every row: zero, as ufb_current_tree_reps keeps its own)
+    for (int bp = 0; bp < 2 && rows_p > 3 * nb; bp++)
+      HIPCHK(hipMemsetAsync(d_nni_planes_.p + ((size_t)bp * rows_p + 3 * nb) * (size_t)g_.Wp, 0, (rows_p - 3 * nb) * (size_t)g_.Wp * sizeof(uint32_t), st_));
+    HIPCHK(launch_nni_eval_masks(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm, d_nni_planes_.p, d_nni_planes_.p + rows_p * (size_t)g_.Wp));
+  } else
+    HIPCHK(launch_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm));
   HIPCHK(hipMemcpyAsync(h_nni_out_.p, d_nni_out_.p, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st_));
   HIPCHK(hipStreamSynchronize(st_));
   for (size_t i = 0; i < nb; i++) {
@@ -128,6 +144,13 @@ int Engine::optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t 
 {
   int rc = nni_check(root_taxon);
   if (rc) return rc;
+  return nni_climb(root_taxon, speednni, max_steps, false, score, nni_count, nni_steps);
+}
+
+// tracked: every tree the climb looks at goes to saveCurrentTree (nni_book_step)
+int Engine::nni_climb(int root_taxon, bool speednni, int max_steps, bool tracked, uint32_t *score, int32_t *nni_count, int32_t *nni_steps)
+{
+  int rc;
   if (max_steps < 0) { set_error("NNI climb: max_steps must be >= 0"); return MPF_E_INVALID; }
   nni_log_.clear();
   uint32_t cur = 0;
@@ -162,8 +185,9 @@ int Engine::optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t 
       br.clear();
       if (speednni && !brans.empty()) for (const auto &kv : brans) br.push_back(kv.second);
       else nni_full_order(root_taxon, br);
-      rc = nni_eval(br, len, &mv);
+      rc = nni_eval(br, len, &mv, tracked);
       if (rc) return rc;
+      if (tracked) { rc = nni_book_step(br, len, mv, cur); if (rc) return rc; }
       plus.clear();
       for (size_t i = 0; i < br.size(); i++) {
         const int k = len[2 * i] < len[2 * i + 1] ? 0 : 1;               // :3971-3975
@@ -192,6 +216,7 @@ int Engine::optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t 
     }
     rc = tree_length(&cur);
     if (rc) return rc;
+    if (tracked) ufb_->rt_valid = false;         // several non-conflicting NNIs are not additive per site: R_T is made again from the tree
     if (cur <= chosen[0].len) {
       count += num_nnis;
       rollback = false;
@@ -207,6 +232,245 @@ int Engine::optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t 
   if (nni_count) *nni_count = count;
   if (nni_steps) *nni_steps = step;
   return MPF_OK;
+}
+
+// one full evaluation by the mask-writing kernel, its rows read back per pattern: terms[(3 i + r) * P + p] = how many of the three
+// joins at branch i have no common state at pattern p -- r = 0 in the current tree (h), r = 1 / 2 after move 0 / 1 (c_0, c_1); 0
+// for a pattern the engine drops
+int Engine::nni_pattern_terms(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<uint8_t> &terms)
+{
+  int rc = nni_check_tree(root_taxon);
+  if (rc) return rc;
+  br.clear();
+  nni_full_order(root_taxon, br);
+  rc = nni_eval(br, len, nullptr, true);
+  if (rc) return rc;
+  const size_t nb = br.size(), Wp = (size_t)g_.Wp, rows_p = (size_t)round_up((int)(3 * nb), kUfbRowTile);
+  terms.assign(3 * nb * (size_t)P_, 0);
+  if (!nb) return MPF_OK;
+  std::vector<uint32_t> h(2 * rows_p * Wp);
+  HIPCHK(hipMemcpy(h.data(), d_nni_planes_.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < 3 * nb; r++)
+    for (int p = 0; p < P_; p++) {
+      const int site = first_site_[(size_t)p];
+      if (site < 0) continue;
+      const size_t w = r * Wp + (size_t)(site >> 5);
+      terms[r * (size_t)P_ + (size_t)p] = (uint8_t)(((h[w] >> (site & 31)) & 1u) + 2u * ((h[rows_p * Wp + w] >> (site & 31)) & 1u));
+    }
+  return MPF_OK;
+}
+
+// ---------------------------------------------------------------- the climb under -bb
+//
+// With save_all_trees == 2 a scoring step of optimizeNNI hands 1 + 2 * branches trees to IQTree::saveCurrentTree, in this order:
+// the current tree (iqtree.cpp:2181-2183), then move 0 and move 1 of every evaluated branch (getBestNNIForBran,
+// phylotree.cpp:3907-3939) -- all of them, not only the positive ones; a rollback step, the applied moves and the rollback
+// itself book nothing.  pllComputePatternParsimony is skipped on this path (iqtree.cpp:3363): _pattern_pars is the booked tree's
+// own row (computeParsimonyBranch has just written it, phylotree.cpp:956-957 / :986-987), so on a ratchet climb the length the
+// cut-off test sees and treels_logl records is the booked tree's OWN length on the original alignment (:3283-3294), and a tree
+// that fails the cut-off closes no gate.
+//
+// k_nni_eval_masks has left per branch the rows h, c_0, c_1 (two bit planes each).  REPS of all candidates in one product,
+// C = plane0 x W + 2 * plane1 x W; candidate (branch i, move k) scores R_T[b] - C[h_i][b] + C[c_ik][b] under sample b.  Index
+// space of the extraction: 0 = the current tree (offered from R_T on the host), 1 + 2 i + k = the candidates in evaluation
+// order, 1 + 2 nb + i = the home slot of branch i (its h row); the events are replayed with the tracker's update rule and the
+// shared tie stream exactly as the SPR climb's are (ufb_one_event, ufb_book_tree).  Under a cut-off only the rows of candidates
+// that pass are multiplied (rowsel); a ratchet climb multiplies every row, since the column of original frequencies is what
+// gives each candidate the length the cut-off test looks at.
+int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<uint32_t> &len, const std::vector<NniSwap> &mv, uint32_t cur)
+{
+  UfbState &u = *ufb_;
+  const uint32_t nb = (uint32_t)br.size(), n_idx = 1u + 3u * nb;
+  const bool ratchet = u.ratchet;
+  const int oc = u.Bl;                             // the column of the original pattern frequencies
+  const size_t Wp = (size_t)g_.Wp;
+  u.nni_booked += 1u + 2u * (uint64_t)nb;
+  u.batches++;
+  const bool have_cut = u.logl_cutoff != 0.0;
+  const double lim = -u.logl_cutoff + 1e-4;        // iqtree.cpp:3343: booked iff  -len > logl_cutoff - 1e-4
+  const bool none_pass = have_cut && lim <= 0.0;
+  const uint32_t mp_max = have_cut ? (none_pass ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
+  if (none_pass) return MPF_OK;
+  const double t0 = now_ms();
+  if (!u.rt_valid) { int rc = ufb_current_tree_reps(); if (rc) return rc; }       // (uses C: in front of the product)
+  UCHK(u.h_rt.reserve((size_t)u.Bp));
+  UCHK(hipMemcpyAsync(u.h_rt.p, u.rt.p, (size_t)(u.Bl + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+  const int mask_rows_p = round_up((int)(3u * nb), kUfbRowTile);
+  const uint32_t *plane[2] = {d_nni_planes_.p, d_nni_planes_.p + (size_t)mask_rows_p * Wp};
+  auto product = [&](int rows_p, const uint32_t *d_sel) -> int {
+    UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
+    bool first = true;
+    for (int pl = 0; pl < u.planes; pl++)
+      for (int bp = 0; bp < 2; bp++, first = false)
+        UCHK(launch_bitgemm(st_, plane[bp], rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, (1 << (7 * pl)) << bp, first ? 0 : 1, d_sel));
+    u.gemm_rows += (uint64_t)rows_p;
+    return MPF_OK;
+  };
+  std::vector<uint32_t> blen(2 * (size_t)nb);      // the length each candidate is booked under
+  bool have_C = false;
+  if (ratchet && nb) {
+    int rc = product(mask_rows_p, nullptr);
+    if (rc) return rc;
+    have_C = true;
+    UCHK(u.d_col.reserve((size_t)mask_rows_p));
+    UCHK(u.h_col.reserve((size_t)mask_rows_p));
+    UCHK(launch_ufb_column(st_, u.C.p, u.Bp, oc, 3u * nb, u.d_col.p));
+    UCHK(hipMemcpyAsync(u.h_col.p, u.d_col.p, (size_t)(3u * nb) * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+  }
+  UCHK(hipStreamSynchronize(st_));
+  u.rt_orig = (uint32_t)u.h_rt.p[oc];
+  for (uint32_t i = 0; i < nb; i++)
+    for (uint32_t k = 0; k < 2; k++)
+      blen[2 * i + k] = ratchet ? (uint32_t)((int64_t)u.rt_orig - (int64_t)u.h_col.p[3 * i] + (int64_t)u.h_col.p[3 * i + 1 + k]) : len[2 * i + k];
+
+  // ---- the replay's tools (as in spr_sweeps_ufboot)
+  std::vector<int32_t> bk;
+  std::string cand_key;
+  auto swapped = [&](uint32_t c, std::vector<int32_t> &t) {
+    t = back_;
+    const NniSwap &m = mv[c];
+    const int p = 3 * m.node1 + m.slot1, q = 3 * m.node2 + m.slot2, rp = t[(size_t)p], rq = t[(size_t)q];
+    t[(size_t)p] = rq; t[(size_t)rq] = p;
+    t[(size_t)q] = rp; t[(size_t)rp] = q;
+  };
+  auto topology_key = [&](uint32_t cand_code) -> const std::string & {
+    if (cand_code == 0xFFFFFFFFu) {
+      if (u.self_key_epoch != (uint64_t)topo_epoch_) { canonical_topology(back_, u.self_key); u.self_key_epoch = (uint64_t)topo_epoch_; }
+      return u.self_key;
+    }
+    swapped(cand_code, bk);
+    canonical_topology(bk, cand_key);
+    return cand_key;
+  };
+  auto lookup_topology = [&](int64_t tree_index, uint32_t cand_code) -> int64_t {
+    u.lookups++;
+    return u.topo_index.emplace(topology_key(cand_code), tree_index).first->second;
+  };
+  const UfbDeferCtx dctx{};
+
+  // ---- the current tree: its own length (ratchet: its length on the original alignment), every sample from R_T
+  {
+    const uint32_t self_len = ratchet ? u.rt_orig : cur;
+    u.cur_logl_now = -(int32_t)self_len;
+    int64_t tree_index = ufb_book_tree(self_len, self_len <= mp_max, 0xFFFFFFFFu, false, topology_key);
+    if (tree_index >= 0) {
+      bool looked_up = false;
+      for (int c2 = 0; c2 < u.Bl; c2++) ufb_one_event((uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2], tree_index, looked_up, 0xFFFFFFFFu, lookup_topology, dctx);
+    }
+  }
+
+  // ---- the candidates that pass: product (unless a ratchet step has it), extraction
+  std::vector<uint8_t> pass(2 * (size_t)nb);
+  uint32_t n_pass = 0;
+  for (size_t c = 0; c < pass.size(); c++) { pass[c] = blen[c] <= mp_max; n_pass += pass[c]; }
+  std::vector<UfbEvent> events;
+  if (n_pass) {
+    const bool compact = have_cut && !ratchet;
+    std::vector<uint32_t> sel_rows;
+    std::vector<uint32_t> crow((size_t)n_idx, 0xFFFFFFFFu);
+    for (uint32_t i = 0; i < nb; i++) {
+      if (!pass[2 * i] && !pass[2 * i + 1]) continue;
+      if (!compact) {
+        crow[1 + 2 * i] = 3 * i + 1; crow[2 + 2 * i] = 3 * i + 2; crow[1 + 2 * nb + i] = 3 * i;
+        continue;
+      }
+      crow[1 + 2 * nb + i] = (uint32_t)sel_rows.size(); sel_rows.push_back(3 * i);
+      for (uint32_t k = 0; k < 2; k++)
+        if (pass[2 * i + k]) { crow[1 + 2 * i + k] = (uint32_t)sel_rows.size(); sel_rows.push_back(3 * i + 1 + k); }
+    }
+    const int rows_p = compact ? round_up((int)sel_rows.size(), kUfbRowTile) : mask_rows_p;
+    // staging: thr[nb] | home[nb] | best[Bp] | crow[n_idx] | cost[n_idx] | (even) info[n_idx] as pairs | sel[rows_p] | event counter
+    const size_t o_home = nb, o_best = 2 * (size_t)nb, o_crow = o_best + (size_t)u.Bp, o_cost = o_crow + n_idx;
+    const size_t o_info = (o_cost + n_idx + 1) & ~(size_t)1, o_sel = o_info + 2 * (size_t)n_idx, o_cnt = o_sel + (compact ? (size_t)rows_p : 0);
+    UCHK(u.h_small.reserve(o_cnt + 4));
+    UCHK(u.thr.reserve(o_cnt + 4));
+    uint32_t *sm = u.h_small.p;
+    std::memset(sm, 0, (o_cnt + 1) * sizeof(uint32_t));           // (padding columns of best: 0 -> never an event; padding rows multiply mask row 0)
+    for (uint32_t i = 0; i < nb; i++) { sm[i] = 1u; sm[o_home + i] = 1u + 2u * nb + i; }     // a candidate takes part iff cost < 1
+    for (int c2 = 0; c2 < u.Bl; c2++) sm[o_best + (size_t)c2] = ufb_event_bound((uint32_t)u.ids[(size_t)c2]);
+    std::memcpy(sm + o_crow, crow.data(), (size_t)n_idx * sizeof(uint32_t));
+    for (uint32_t idx = 0; idx < n_idx; idx++) { sm[o_info + 2 * idx] = 0u; sm[o_info + 2 * idx + 1] = 0xFFFFFFFFu; }      // the current tree, the home slots
+    for (uint32_t c = 0; c < 2 * nb; c++) {
+      sm[o_cost + 1 + c] = pass[c] ? 0u : 1u;
+      sm[o_info + 2 * (1 + c)] = crow[1 + c];
+      sm[o_info + 2 * (1 + c) + 1] = c / 2;
+    }
+    if (compact) std::memcpy(sm + o_sel, sel_rows.data(), sel_rows.size() * sizeof(uint32_t));
+    UCHK(hipMemcpyAsync(u.thr.p, sm, (o_cnt + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+    if (!have_C) { int rc = product(rows_p, compact ? u.thr.p + o_sel : nullptr); if (rc) return rc; }
+    const uint32_t nch = ufb_chunks(n_idx);
+    UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
+    UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
+    if (u.ev.cap == 0) { const size_t c0 = (size_t)std::min<int64_t>(ufb_event_cap_, 1 << 18); UCHK(u.ev.reserve(c0)); }
+    uint32_t *d_evcount = u.thr.p + o_cnt;
+    uint32_t n_ev = 0;
+    for (bool again = false;; again = true) {
+      if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
+      UCHK(launch_ufb_events(st_, reinterpret_cast<const uint2 *>(u.thr.p + o_info), u.thr.p + o_cost, u.thr.p, u.thr.p + o_home, u.thr.p + o_crow, u.C.p,
+                             u.Bp, u.Bl, u.rt.p, u.thr.p + o_best, n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, 0));
+      UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+      UCHK(hipStreamSynchronize(st_));
+      n_ev = u.h_small.p[0];
+      if (n_ev <= u.ev.cap) break;
+      UCHK(u.ev.reserve((size_t)n_ev));              // more events than room: grow and extract again
+    }
+    if (n_ev) {
+      UCHK(u.h_ev.reserve((size_t)n_ev));
+      UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_ev * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
+      UCHK(hipStreamSynchronize(st_));
+      events.assign(u.h_ev.p, u.h_ev.p + n_ev);
+      for (UfbEvent &e : events) e.b = (uint32_t)u.ids[(size_t)e.b];
+      std::vector<UfbEvent> tmp;
+      std::vector<uint32_t> count;
+      sort_events(events, tmp, count, n_idx, (uint32_t)u.B);
+    }
+    u.events += n_ev;
+  }
+  const double t1 = now_ms();
+  u.t_dev += t1 - t0;
+
+  // ---- the candidates in evaluation order, move 0 then move 1
+  size_t ep = 0;
+  for (uint32_t c = 0; c < 2 * nb; c++) {
+    u.cur_logl_now = -(int32_t)blen[c];
+    int64_t tree_index = ufb_book_tree(blen[c], pass[c] != 0, c, false, topology_key);
+    if (tree_index < 0) continue;
+    const uint32_t idx = 1u + c;
+    while (ep < events.size() && events[ep].idx < idx) ep++;
+    bool looked_up = false;
+    for (; ep < events.size() && events[ep].idx == idx; ep++) ufb_one_event(events[ep].b, events[ep].s, tree_index, looked_up, c, lookup_topology, dctx);
+  }
+  // a tree a sample accepted is remembered as (this step's tree, swap) and materialised only if still referenced
+  for (const UfbState::Pending &pe : u.pending) {
+    if (u.refs[(size_t)pe.tree_index] <= 0 || u.store.count(pe.tree_index)) continue;
+    if (pe.cand == 0xFFFFFFFFu) u.store.emplace(pe.tree_index, back_);
+    else { swapped(pe.cand, bk); u.store.emplace(pe.tree_index, bk); }
+    u.stored++;
+  }
+  u.pending.clear();
+  u.t_replay += now_ms() - t1;
+  return MPF_OK;
+}
+
+// IQTree::optimizeNNI under -bb (iqtree.cpp:2173-2302 with save_all_trees == 2)
+int Engine::ufboot_optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t *score, int32_t *nni_count, int32_t *nni_steps)
+{
+  if (sankoff_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
+  if (!ufb_) { set_error("no UFBoot tracker attached"); return MPF_E_STATE; }
+  if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
+  const UfbState &u = *ufb_;
+  if (u.exchange || u.Bl != u.B) { set_error("tracked NNI climb: not served with a sample-sharded tracker"); return MPF_E_UNSUPPORTED; }
+  if (u.store_trees) { set_error("tracked NNI climb: -storetrees is not served"); return MPF_E_UNSUPPORTED; }
+  if (u.topboot) { set_error("tracked NNI climb: -mulhits -topboot is not served"); return MPF_E_UNSUPPORTED; }
+  if (u.distinct) { set_error("tracked NNI climb: -distinct_iter_top_boot is not served"); return MPF_E_UNSUPPORTED; }
+  if (root_taxon < 1 || root_taxon > n_) { set_error("NNI climb: root_taxon must be in 1 .. n_taxa"); return MPF_E_INVALID; }
+  // (suspended: other weights than the attach-time ones under -no_hclimb1_bb, or an attach-time pattern without a site --
+  //  saveCurrentTree is not called, iqtree.cpp:3280: the plain climb)
+  const bool tracked = !u.suspended;
+  if (tracked) ufb_->rt_valid = false;
+  const int rc = nni_climb(root_taxon, speednni, max_steps, tracked, score, nni_count, nni_steps);
+  ufb_->rt_valid = false;
+  return rc;
 }
 
 }  // namespace mpf
