@@ -242,16 +242,37 @@ int mpf_stepwise_addition(mpf_engine *e, int64_t seed, uint32_t *best_per_step /
    positive moves are ordered by std::sort on the length, non-conflicting ones applied together and rolled back when the tree got
    longer than the best of them.  The tree is modified in place; node number = IQ-TREE id + 1, slot = position in neighbors[].
    *score = final length (-curScore), *nni_count / *nni_steps as the reference leaves them (nni_steps = max_steps + 1 when the
-   cap is hit; the reference's MAXSTEPS is 50).  MPF_E_UNSUPPORTED on the weighted engine and with a UFBoot tracker attached (the
-   climb under -bb is mpf_ufboot_optimize_nni), MPF_E_STATE without a tree, MPF_E_INVALID for a root_taxon outside 1 .. n.
+   cap is hit; the reference's MAXSTEPS is 50).  MPF_E_UNSUPPORTED on the weighted engine (unless the option "nni_weighted" is
+   set, see below) and with a UFBoot tracker attached (the climb under -bb is mpf_ufboot_optimize_nni), MPF_E_STATE without a
+   tree, MPF_E_INVALID for a root_taxon outside 1 .. n.
    Options "nni_launches", "nni_rollbacks" and "nni_branches_scored" count scoring launches, rolled-back steps and scored
-   branches (mpf_get_option). */
+   branches (mpf_get_option).
+
+   The weighted engine (mpf_engine_create_sankoff; the reference's -cost m -nni_pars).  Option "nni_weighted" (mpf_set_option,
+   default 0; accepted and without effect on a Fitch engine): with 0 every NNI entry refuses a weighted engine as above, with 1
+   mpf_optimize_nni, mpf_nni_scores and mpf_get_nni_moves are served on it.  Under -cost the search tree is a ParsTree
+   (phyloanalysis.cpp:2200-2203), so what optimizeNNI calls are ParsTree's overrides:
+     - an NNI is scored by ParsTree::computeParsimonyBranch(node1->findNeighbor(node2), node1) (parstree.cpp:439-541): Sankoff,
+       the tree ROOTED AT THE SCORED BRANCH with node2's side as the parent side (the rows of the matrix) and node1's side the
+       transformed one -- length = sum_ptn w * min_i( Y[i] + min_j( X[j] + cost[i][j] ) ), X / Y the views of node1 / node2 after
+       the swap.  With a matrix that is not symmetric this is NOT the length the tree has at the root leaf;
+     - curScore is ParsTree::computeParsimony() (parstree.cpp:101-116), the length at the edge of the leaf root_taxon (what
+       mpf_compute_parsimony_at(e, NULL, root_taxon, ..) returns): *score is that length of the final tree;
+     - no rollback (iqtree.cpp:2258, `if(globalParam->sankoff_cost_file) continue;`): when the tree after a step's NNIs is longer
+       than the best of them promised, the moves STAY, curScore stays the longer length, nni_count does not grow, and the next
+       step goes on from there (with speednni: on the branches around these moves).  The climb may therefore end longer than it
+       started, and with a non-symmetric matrix it often runs into the step cap.  "nni_rollbacks" does not move on this path;
+       read-only option "nni_kept_worse" counts these steps.
+   Still MPF_E_UNSUPPORTED on a weighted engine whatever the option: mpf_ufboot_optimize_nni (the tracked weighted climb),
+   mpf_optimize_nni with a tracker attached, mpf_nni_pattern_terms.
+   With the option "timing" set, read-only option "nni_kernel_ns" accumulates the HIP-event time of the scoring kernels. */
 int mpf_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
                      int32_t *nni_steps);
 /* one full evaluation of the current tree (evalNNIs(), iqtree.cpp:3144-3159, with getBestNNIForBran, phylotree.cpp:3807-3980):
    branch i in the reference's order joins node1[i] and node2[i] (node numbers); len[2i + k] = tree length after its move k (k = 0:
    node1's first neighbour other than node2 swapped with node2's first other neighbour, k = 1: with its second).  *n = number of
-   inner branches, always set; the arrays are filled when cap >= *n. */
+   inner branches, always set; the arrays are filled when cap >= *n.  On a weighted engine under "nni_weighted": the two FULL weighted
+   lengths, each rooted at its branch (node2[i]'s side the parent), as described at mpf_optimize_nni. */
 int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len /* [2 * cap] */,
                    int32_t *n);
 /* DIAGNOSTIC, for tests of the kernel alone -- no part of mpboot's flow, and nothing a host should build on: mpf_nni_scores by

@@ -165,10 +165,16 @@ void mpfitch_phylotree_install_nni(const mpf_phylotree_nni_hooks *hooks)
 }
 
 // IQTree::optimizeNNI (iqtree.cpp:2173-2302), MP mode, MAXSTEPS 50: the climb runs on the engine, its swaps are replayed here
+// (a ParsTree: the return value is ParsTree::computeParsimony() of the final tree, the length at the root leaf)
 int mpfitch_optimize_nni(PhyloTree *t, int *nni_count, int *nni_steps)
 {
   if (!g_nni_installed) { std::fprintf(stderr, "mpfitch phylotree shim: mpfitch_phylotree_install_nni() was not called\n"); std::exit(EXIT_FAILURE); }
-  mpf_engine *e = engine_for(t, nullptr);
+  // A ParsTree (-cost: phyloanalysis.cpp:2200-2203) climbs on the weighted engine under "nni_weighted": NNIs scored by
+  // ParsTree::computeParsimonyBranch, and no rollback (iqtree.cpp:2258).  That rule hangs on -cost being given, not on the matrix,
+  // so unit costs ("-cost e", which computeParsimony below runs on the Fitch engine) take the weighted engine here as well.
+  const unsigned int *cost = g_h.cost_matrix ? g_h.cost_matrix(t) : nullptr;
+  mpf_engine *e = engine_for(t, cost);
+  if (cost && mpf_set_option(e, "nni_weighted", 1)) die("mpf_set_option nni_weighted");
   const int n = g_h.n_taxa(t);
   std::vector<int32_t> back;
   marshal_tree(t, n, back);

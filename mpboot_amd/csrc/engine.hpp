@@ -474,7 +474,7 @@ class Engine {
   void ufb_flush_pending(const ScanPlan &pl);
 
   // NNI climb state: the swap log of the last climb, the kernel shape (option "nni_tile") and the counters behind the options
-  // nni_launches / nni_rollbacks / nni_branches_scored
+  // nni_launches / nni_rollbacks / nni_branches_scored / nni_kept_worse
   struct NniScored { NniSwap mv; uint32_t len; };
   int nni_check(int root_taxon) const;
   int nni_check_tree(int root_taxon) const;      // ... without the refusal of a tracker
@@ -488,6 +488,11 @@ class Engine {
   std::vector<NniSwap> nni_log_;
   int nni_vw_ = -1;                              // option "nni_tile": -1 = from the geometry, 0 = word-major copy where current, 1 | 2 | 4 = row-major words per lane
   uint64_t nni_launches_ = 0, nni_rollbacks_ = 0, nni_branches_ = 0;
+  // option "nni_weighted": the weighted engine serves the plain NNI entries (ParsTree scoring by k_snk_nni_eval, no rollback:
+  // iqtree.cpp:2258); "nni_kept_worse" counts the steps whose moves stayed although the tree came out longer than the best of them
+  int nni_weighted_ = 0;
+  uint64_t nni_kept_worse_ = 0;
+  uint64_t nni_kernel_ns_ = 0;                   // option "timing": HIP-event time of the scoring kernels (read-only option "nni_kernel_ns")
   DevBuf<NniDesc> d_nni_desc_;
   DevBuf<uint32_t> d_nni_planes_;                // k_nni_eval_masks: [2 planes][3 rows per branch, padded to the product's row tile][Wp]
   DevBuf<unsigned long long> d_nni_out_;

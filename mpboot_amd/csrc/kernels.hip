@@ -2190,6 +2190,62 @@ __global__ __launch_bounds__(256) void k_snk_evaluate(const uint32_t *__restrict
   if (lane == 0 && tot) atomic_add_u32(out + o.out, tot);
 }
 
+// NNI scoring on the weighted engine (IQTree::optimizeNNI under -cost; host/nni.cpp).  Under -cost the search tree is a ParsTree
+// (reference phyloanalysis.cpp:2200-2203; parstree.h:13 derives it from IQTree), so the computeParsimonyBranch that
+// getBestNNIForBran reaches through optimizeOneBranch (phylotree.cpp:3907 -> :3177-3181) is ParsTree's override
+// (parstree.cpp:439-541): Sankoff, rooted at the scored branch.
+// Branch i joins node1 (subtrees A, B) and node2 (C0, C1), as in k_nni_eval; move k swaps A with C_k.  With m() the transform:
+//   X = m(B) + m(C_k)       node1's new view    (computePartialParsimony, parstree.cpp:127-300: the sum of the children's transforms)
+//   Y = m(A) + m(C_{1-k})   node2's new view
+//   length = sum_ptn w * min_i( Y[i] + m(X)[i] ),   m(X)[i] = min_j( X[j] + cost[i][j] )
+// which is computeParsimonyBranch(node1->findNeighbor(node2), node1) (parstree.cpp:479-533): dad_branch->partial_pars is the
+// subtree at node2 and enters as it is (the parent side, the ROWS of the matrix), node_branch->partial_pars is the subtree at
+// node1 and is the one transformed.  The stored transforms have that orientation already -- the viewer is the parent, as in
+// computePartialParsimony -- so no transposed matrix appears and the same code serves symmetric and non-symmetric matrices.
+// The four operands are the STORED transforms (the `moff` half), loaded once per (branch, tile); each move costs one transform,
+// m(X), and Y is formed inside the final minimum.  out[i] = move 0's length (low word) | move 1's (high word): FULL lengths (no
+// additive base, see k_snk_scan), one 64-bit atomic per (branch, tile); the low word is a tree length and never carries.
+// 16-bit form: every value formed is at most a sum of the four stored transforms, whose subtrees hold all n tips between them,
+// plus one matrix entry.  A tip's transform is at most the largest cost, a view is the sum of its children's transforms and its
+// own transform adds at most one more entry, so a subtree of t tips stays below 2 t highest_cost and everything here below
+// 2 n highest_cost: inside the engine's condition for the 16-bit form, 3 n highest_cost < 2^16 (Engine::pack) -- no fall-back needed.
+// BUF: the transform half behind one raw buffer (32-bit offsets); otherwise 64-bit pointers per row (a half of 4 GiB and more).
+template <int S, bool PK, bool BUF>
+__global__ __launch_bounds__(256) void k_snk_nni_eval(const uint32_t *__restrict__ vec, size_t moff, const NniDesc *__restrict__ desc,
+                                                      int n_br, const uint32_t *__restrict__ cost, const uint32_t *__restrict__ pwgt,
+                                                      unsigned long long *__restrict__ out, int We, int tiles)
+{
+  typedef SnkT<PK> T;
+  const int lane = threadIdx.x & 63;
+  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  gw = __builtin_amdgcn_readfirstlane(gw);
+  if (gw >= n_br * tiles) return;
+  const int br = gw / tiles, tile = gw - br * tiles;
+  const NniDesc d = desc[br];
+  bool valid;
+  const int e0 = lane_word<1>(tile, lane, We, valid);
+  const uint32_t *mvec = vec + moff;
+  const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void *)mvec, 0, -1, 0x00020000);
+  const uint32_t row_bytes = (uint32_t)We * 4u, voff = (uint32_t)e0 * 4u;
+  auto ldm = [&](Costs<S, PK> &t, uint32_t slot) { if constexpr (BUF) load_costs_b<S, PK>(t, rs_m, slot, row_bytes, voff); else load_costs<S, PK>(t, mvec, slot, We, e0); };
+  Costs<S, PK> ma, mb, mc0, mc1;
+  ldm(ma, d.a); ldm(mb, d.b); ldm(mc0, d.c0); ldm(mc1, d.c1);
+  auto move = [&](const Costs<S, PK> &mck, const Costs<S, PK> &mco) {
+    Costs<S, PK> x, mx;
+#pragma unroll
+    for (int s = 0; s < S; s++) x.v[s] = T::add(mb.v[s], mck.v[s]);
+    mplus_fast<S, PK>(mx, x, cost);
+    typename T::E best = T::inf();
+#pragma unroll
+    for (int s = 0; s < S; s++) best = T::mn(best, T::add(T::add(ma.v[s], mco.v[s]), mx.v[s]));
+    return best;
+  };
+  const typename T::E b0 = move(mc0, mc1), b1 = move(mc1, mc0);
+  const uint32_t t0 = wave_total<0>(valid ? T::wsum(b0, pwgt, e0) : 0u), t1 = wave_total<0>(valid ? T::wsum(b1, pwgt, e0) : 0u);
+  if (lane == 0 && (t0 | t1))
+    __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // SPR / stepwise scan over a host-planned program (same ops as k_scan).  With m() the min-plus transform:
 //   CHAIN : U[d] = m(U[d-1]) + m(vec[sib]);  test: out += sum_ptn w * min_s(m(U[d])[s] + m(vec[own])[s] + m(S)[s])
 //   JOIN  : out += sum_ptn w * min_s(m(vec[own])[s] + m(vec[sib])[s] + m(S)[s])
@@ -2691,6 +2747,22 @@ hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32
   else if (g.S == 4 && vw == 2) launch(int_c<4>(), int_c<2>(), bool_c<false>());
   else if (g.S == 4 && vw == 4) launch(int_c<4>(), int_c<4>(), bool_c<false>());
   else dispatch_states(g.S, [&](auto S) { launch(S, int_c<1>(), bool_c<false>()); });
+  return hipGetLastError();
+}
+
+hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
+                               unsigned long long *out, bool wide_addr)
+{
+  if (n_br <= 0) return hipSuccess;
+  if (!g.sankoff || !g.moff) return hipErrorInvalidValue;
+  const int We = snk_elems(g), tiles = (We + 63) / 64;
+  dim3 grid((unsigned)(((long)n_br * tiles + 3) / 4)), block(256);
+  const bool buf_ok = !wide_addr && (unsigned long long)g.moff * 4ull < (1ull << 32);      // the transform half behind one 32-bit-offset descriptor
+  dispatch_snk(g, [&](auto S, auto PK) {
+    dispatch_bool(buf_ok, [&](auto BUF) {
+      hipLaunchKernelGGL((k_snk_nni_eval<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles);
+    });
+  });
   return hipGetLastError();
 }
 

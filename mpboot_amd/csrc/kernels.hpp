@@ -208,6 +208,11 @@ hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *ve
 // those of the tree after move 0 / move 1 (c_0, c_1); plane0 / plane1: [3 * n_br][Wp] words, sites in the order of launch_join_masks
 hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
                                  unsigned long long *out, int vw, bool word_major, uint32_t *plane0, uint32_t *plane1);
+// ... on the weighted engine (k_snk_nni_eval): the same descriptors; out[i] = the FULL weighted length after move 0 | after move 1
+// << 32, rooted at the branch with node2's side as the parent (ParsTree::computeParsimonyBranch) -- nothing to add on the host.
+// wide_addr: 64-bit pointers per row whatever the size of the store (what a transform half of 4 GiB and more takes by itself)
+hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
+                               unsigned long long *out, bool wide_addr = false);
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,
                        const ScanOp *ops, uint32_t *out, int max_depth,
                        uint32_t *host_out = nullptr, uint32_t n_out = 0, uint32_t *done = nullptr,   // as launch_scan_walk

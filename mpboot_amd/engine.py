@@ -560,14 +560,22 @@ class FitchEngine:
 
     # ---- NNI hill climb (IQTree::optimizeNNI in MP mode: -nni_pars, -hclimb1_nni)
     def optimize_nni(self, root_taxon: int = 1, speednni: bool = True, max_steps: int = 50):
-        """-> (length, nni_count, nni_steps); the tree is modified in place"""
+        """-> (length, nni_count, nni_steps); the tree is modified in place.
+
+        A weighted engine (cost=...) serves this after set_option("nni_weighted", 1) only (default 0: MpfError -6, as before):
+        the reference's -cost m -nni_pars, where the tree is a ParsTree -- every NNI scored by Sankoff rooted at its branch
+        (node2's side the parent, ParsTree::computeParsimonyBranch), the tree's own length taken at the leaf root_taxon
+        (ParsTree::computeParsimony), and NO rollback (iqtree.cpp:2258): a step that left the tree longer than its best NNI
+        promised keeps its moves and is not counted; get_option("nni_kept_worse") counts such steps.  Not served there: a
+        tracker attached, ufboot_optimize_nni, nni_pattern_terms."""
         s, cnt, steps = C.c_uint32(), C.c_int32(), C.c_int32()
         _chk(load_library().mpf_optimize_nni(self.h, root_taxon, int(bool(speednni)), max_steps, C.byref(s), C.byref(cnt),
                                              C.byref(steps)))
         return s.value, cnt.value, steps.value
 
     def nni_scores(self, root_taxon: int = 1):
-        """one full evaluation: (node1[m], node2[m], len[m][2]) for the m inner branches in evalNNIs() order"""
+        """one full evaluation: (node1[m], node2[m], len[m][2]) for the m inner branches in evalNNIs() order; on a weighted engine
+        under set_option("nni_weighted", 1) the two full weighted lengths, each rooted at its branch with node2's side the parent"""
         L = load_library()
         n = C.c_int32()
         _chk(L.mpf_nni_scores(self.h, root_taxon, 0, None, None, None, C.byref(n)))

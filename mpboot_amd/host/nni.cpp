@@ -26,9 +26,9 @@ namespace mpf {
 
 int Engine::nni_check(int root_taxon) const
 {
-  // the weighted climb skips the rollback (iqtree.cpp:2258) and an attached tracker would have to book every NNI
-  // (saveCurrentTree from getBestNNIForBran, phylotree.cpp:3937): neither is served
-  if (sankoff_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
+  // the weighted climb (ParsTree scoring, no rollback: iqtree.cpp:2258) is served under the option "nni_weighted" only; an attached
+  // tracker would have to book every NNI (saveCurrentTree from getBestNNIForBran, phylotree.cpp:3937): the plain entries refuse it
+  if (sankoff_ && !nni_weighted_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
   if (ufb_) { set_error("NNI climb: not served with a UFBoot tracker attached"); return MPF_E_UNSUPPORTED; }
   return nni_check_tree(root_taxon);
 }
@@ -36,7 +36,7 @@ int Engine::nni_check(int root_taxon) const
 // ... the part every NNI entry shares, whatever it makes of a tracker
 int Engine::nni_check_tree(int root_taxon) const
 {
-  if (sankoff_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
+  if (sankoff_ && !nni_weighted_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
   if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
   if (root_taxon < 1 || root_taxon > n_) { set_error("NNI climb: root_taxon must be in 1 .. n_taxa"); return MPF_E_INVALID; }
   return MPF_OK;
@@ -84,7 +84,7 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
     if (k1 != 2 || k2 != 2 || v1 <= n_ || v2 <= n_) { set_error("NNI climb: a scored branch is not an inner branch"); return MPF_E_STATE; }
     const int ra = back_[3 * v1 + s1[0]], rb = back_[3 * v1 + s1[1]], rc0 = back_[3 * v2 + s2[0]], rc1 = back_[3 * v2 + s2[1]];
     h_nni_desc_.p[i] = NniDesc{slot(ra), slot(rb), slot(rc0), slot(rc1)};
-    base[i] = score(ra) + score(rb) + score(rc0) + score(rc1);
+    base[i] = sankoff_ ? 0u : score(ra) + score(rb) + score(rc0) + score(rc1);      // weighted: the kernel returns full lengths
     if (moves) {
       (*moves)[2 * i] = NniSwap{v1, s1[0], v2, s2[0]};
       (*moves)[2 * i + 1] = NniSwap{v1, s1[0], v2, s2[1]};
@@ -94,7 +94,12 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
   int vw = nni_vw_ > 0 ? nni_vw_ : (nni_vw_ == 0 ? 1 : g_.vw);
   HIPCHK(hipMemcpyAsync(d_nni_desc_.p, h_nni_desc_.p, nb * sizeof(NniDesc), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(d_nni_out_.p, 0, nb * sizeof(unsigned long long), st_));
-  if (masks) {
+  if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
+  if (sankoff_) {
+    // ParsTree::computeParsimonyBranch(node1->findNeighbor(node2), node1) for both moves of every branch (k_snk_nni_eval)
+    if (masks) { set_error("NNI climb: the tracked climb is not served on the weighted engine"); return MPF_E_UNSUPPORTED; }
+    HIPCHK(launch_snk_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, force_big_ != 0));
+  } else if (masks) {
     // tracked climb: the two bit planes of (h, c_0, c_1) per branch, each padded to the product's row tile
     const size_t rows_p = (size_t)round_up((int)(3 * nb), kUfbRowTile);
     HIPCHK(d_nni_planes_.reserve(2 * rows_p * (size_t)g_.Wp));
@@ -104,8 +109,11 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
     HIPCHK(launch_nni_eval_masks(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm, d_nni_planes_.p, d_nni_planes_.p + rows_p * (size_t)g_.Wp));
   } else
     HIPCHK(launch_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm));
+  if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
   HIPCHK(hipMemcpyAsync(h_nni_out_.p, d_nni_out_.p, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st_));
   HIPCHK(hipStreamSynchronize(st_));
+  float ms = 0.f;
+  if (timing_ && hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) nni_kernel_ns_ += (uint64_t)((double)ms * 1e6);
   for (size_t i = 0; i < nb; i++) {
     const unsigned long long o = h_nni_out_.p[i];
     len[2 * i] = base[i] + (uint32_t)(o & 0xFFFFFFFFull);
@@ -153,6 +161,9 @@ int Engine::nni_climb(int root_taxon, bool speednni, int max_steps, bool tracked
   int rc;
   if (max_steps < 0) { set_error("NNI climb: max_steps must be >= 0"); return MPF_E_INVALID; }
   nni_log_.clear();
+  // weighted: curScore is ParsTree::computeParsimony(), the length at the edge of IQ-TREE's root leaf (parstree.cpp:101-116) --
+  // with a matrix that is not symmetric the length depends on that edge
+  StartGuard at_root(*this, sankoff_ ? root_taxon : 0);
   uint32_t cur = 0;
   rc = tree_length(&cur);
   if (rc) return rc;
@@ -220,6 +231,10 @@ int Engine::nni_climb(int root_taxon, bool speednni, int max_steps, bool tracked
     if (cur <= chosen[0].len) {
       count += num_nnis;
       rollback = false;
+    } else if (sankoff_) {
+      // iqtree.cpp:2258, `if(globalParam->sankoff_cost_file) continue;`: no rollback under -cost -- the moves stay, curScore stays
+      // the worse length, nni_count does not grow, and the next step scores the speednni set just built from these moves
+      nni_kept_worse_++;
     } else {
       for (int i = 0; i < num_nnis; i++) nni_swap(chosen[(size_t)i].mv);
       rollback = true;
@@ -239,6 +254,7 @@ int Engine::nni_climb(int root_taxon, bool speednni, int max_steps, bool tracked
 // for a pattern the engine drops
 int Engine::nni_pattern_terms(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<uint8_t> &terms)
 {
+  if (sankoff_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }   // (the mask rows are Fitch joins)
   int rc = nni_check_tree(root_taxon);
   if (rc) return rc;
   br.clear();
