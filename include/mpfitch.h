@@ -263,8 +263,8 @@ int mpf_stepwise_addition(mpf_engine *e, int64_t seed, uint32_t *best_per_step /
        step goes on from there (with speednni: on the branches around these moves).  The climb may therefore end longer than it
        started, and with a non-symmetric matrix it often runs into the step cap.  "nni_rollbacks" does not move on this path;
        read-only option "nni_kept_worse" counts these steps.
-   Still MPF_E_UNSUPPORTED on a weighted engine whatever the option: mpf_ufboot_optimize_nni (the tracked weighted climb),
-   mpf_optimize_nni with a tracker attached, mpf_nni_pattern_terms.
+   Still MPF_E_UNSUPPORTED on a weighted engine under this option alone: mpf_ufboot_optimize_nni (served under the further option
+   "nni_weighted_tracked", see there), mpf_optimize_nni with a tracker attached, mpf_nni_pattern_terms.
    With the option "timing" set, read-only option "nni_kernel_ns" accumulates the HIP-event time of the scoring kernels. */
 int mpf_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
                      int32_t *nni_steps);
@@ -281,6 +281,16 @@ int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node
    tree) - terms[3 i] + terms[3 i + 1 + k].  0 for patterns the engine drops.  Filled when cap >= *n. */
 int mpf_nni_pattern_terms(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len /* [2 * cap] */,
                           uint8_t *terms /* [3 * cap][n_patterns] */, int32_t *n);
+/* DIAGNOSTIC, the weighted counterpart of mpf_nni_pattern_terms (same sizing protocol, same standing): mpf_nni_scores by the
+   row-writing kernel of the tracked weighted climb (k_snk_nni_eval_vals), with what it writes for the tracker read back per
+   ORIGINAL pattern as 16-bit values, rows[r * n_patterns + p]: r = 0 the current tree at the edge of the leaf root_taxon (the row
+   ParsTree::computeParsimony() writes, parstree.cpp:101-116), r = 1 + 2 i + k the tree after move k of branch i rooted at that
+   branch with node2[i]'s side the parent (the minima ParsTree::computeParsimonyBranch writes to _pattern_pars, parstree.cpp:460-461,
+   :482-529).  sum_p weight[p] * rows[r][p] is the row's length (len[2 i + k] for a candidate).  0 for patterns the engine drops.
+   rows is filled when cap >= *n ([1 + 2 * cap][n_patterns]).  Weighted engines under "nni_weighted" and "nni_weighted_tracked"
+   only; MPF_E_UNSUPPORTED on a Fitch engine. */
+int mpf_nni_pattern_lengths(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len /* [2 * cap] */,
+                            uint16_t *rows /* [1 + 2 * cap][n_patterns] */, int32_t *n);
 /* every swap (PhyloTree::doNNI, phylotree.cpp:3715-3742) the last mpf_optimize_nni made, in order, the reverting swaps of a
    rollback (iqtree.cpp:2271-2272) included: the neighbours in slot1[i] of node1[i] and slot2[i] of node2[i] traded places.
    Replaying them on the start tree gives the final tree.  *n is always set; the arrays are filled up to cap entries. */
@@ -297,9 +307,26 @@ int mpf_get_nni_moves(const mpf_engine *e, int32_t cap, int32_t *node1, int32_t 
    engine's: patterns it drops (keep_all_sites 0) count 0.
    Served: the default update rule, -mulhits, mpf_ufboot_set_cutoff, -cutoff_from_btrees, ratchet booking; under
    mpf_ufboot_set_ratchet_booking(e, 0) a re-weighted climb runs without booking (the plain climb).  NOT served, MPF_E_UNSUPPORTED:
-   -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, the weighted engine.
+   -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, the weighted engine (but see below).
    Arguments, results, swap log (mpf_get_nni_moves) and counters as mpf_optimize_nni; MPF_E_STATE without a tracker or a tree.
-   Read-only option "nni_booked": trees NNI climbs have handed to saveCurrentTree since the attach. */
+   Read-only option "nni_booked": trees NNI climbs have handed to saveCurrentTree since the attach.
+
+   The weighted engine (-cost m -nni_pars -bb, and -hclimb1_nni under -cost -bb).  Option "nni_weighted_tracked" (mpf_set_option,
+   default 0; accepted and without effect on a Fitch engine): with 0 this entry refuses a weighted engine as above, with 1 -- and
+   "nni_weighted" 1 -- it is served there.  The climb is the weighted one of mpf_optimize_nni (ParsTree scoring, NO rollback,
+   iqtree.cpp:2258: a kept-worse step is followed by an ordinary scoring step, which books the current tree under the longer
+   curScore); the trees booked and their order are those above (iqtree.cpp:2181-2183, phylotree.cpp:3907-3939).  _pattern_pars is
+   again the booked tree's own row, since pllComputePatternParsimony is skipped (iqtree.cpp:3363):
+     - a candidate's: the per-pattern minima min_i( Y[i] + m(X)[i] ) ParsTree::computeParsimonyBranch has just written
+       (parstree.cpp:460-461, :482-529), the tree rooted at the scored branch with node2's side the parent;
+     - the current tree's: the row ParsTree::computeParsimony() wrote at the edge of the leaf root_taxon (parstree.cpp:101-116,
+       reached through optimizeAllBranches, phylotree.cpp:3255-3259).  At the FIRST step the reference's _pattern_pars is whatever
+       the host's last computeParsimonyBranch left; the engine books the root-leaf row there too.  A host whose last evaluation
+       before the call was at another edge differs for that one call, and only under a matrix that is not symmetric.
+   On a ratchet climb (iqtree.cpp:3283-3294) the length the cut-off test sees and treels_logl records is that row times the
+   attach-time weights; a tree that fails the cut-off closes no gate.  Served and refused tracker forms as above; mpf_optimize_nni
+   with a tracker attached and mpf_nni_pattern_terms stay MPF_E_UNSUPPORTED.  Whatever mpf_ufboot_attach demands of a weighted
+   engine is the only condition on the costs. */
 int mpf_ufboot_optimize_nni(mpf_engine *e, int32_t root_taxon, int32_t speednni, int32_t max_steps, uint32_t *score, int32_t *nni_count,
                             int32_t *nni_steps);
 

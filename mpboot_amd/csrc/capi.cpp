@@ -334,6 +334,29 @@ int mpf_nni_pattern_terms(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_
   return MPF_OK;
 }
 
+// ... by the row-writing kernel of the tracked weighted climb, its rows per pattern
+int mpf_nni_pattern_lengths(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len, uint16_t *rows, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> l;
+  std::vector<uint16_t> r;
+  const int rc = e->eng.nni_pattern_lengths(root_taxon, br, l, r);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (!rows || (*n && (!node1 || !node2 || !len))) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    len[2 * i] = l[2 * i];
+    len[2 * i + 1] = l[2 * i + 1];
+  }
+  std::copy(r.begin(), r.end(), rows);
+  return MPF_OK;
+}
+
 // the PhyloTree::doNNI calls (phylotree.cpp:3715-3742) of the last climb
 int mpf_get_nni_moves(const mpf_engine *e, int32_t cap, int32_t *node1, int32_t *slot1, int32_t *node2, int32_t *slot2, int32_t *n)
 {

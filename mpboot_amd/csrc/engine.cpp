@@ -2113,6 +2113,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "grow_fault") { grow_fault_ = v; return MPF_OK; }
   if (key == "nni_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("nni_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } nni_vw_ = (int)v; return MPF_OK; }
   if (key == "nni_weighted") { nni_weighted_ = v ? 1 : 0; return MPF_OK; }     // the -cost NNI climb (host/nni.cpp); no effect on a Fitch engine
+  if (key == "nni_weighted_tracked") { nni_weighted_tracked_ = v ? 1 : 0; return MPF_OK; }   // ... under -bb; no effect on a Fitch engine
   if (key == "max_visits") { max_visits_ = std::max<int64_t>(0, v); return MPF_OK; }
   if (key == "small_batch_max") { small_batch_max_ = (int)std::max<int64_t>(1, std::min<int64_t>(v, 1 << 30)); return MPF_OK; }
   if (key == "ufb_moot") { ufb_moot_ = v ? 1 : 0; return MPF_OK; }
@@ -2216,6 +2217,7 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "nni_rollbacks") *v = (int64_t)nni_rollbacks_;
   else if (key == "nni_branches_scored") *v = (int64_t)nni_branches_;
   else if (key == "nni_weighted") *v = nni_weighted_;
+  else if (key == "nni_weighted_tracked") *v = nni_weighted_tracked_;
   else if (key == "nni_kept_worse") *v = (int64_t)nni_kept_worse_;
   else if (key == "nni_kernel_ns") *v = (int64_t)nni_kernel_ns_;
   else if (key == "nni_booked") *v = ufb_ ? (int64_t)ufb_->nni_booked : 0;

@@ -325,6 +325,9 @@ class Engine {
   int nni_scores(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len);   // one full evaluation, len[2 * i + k]
   const std::vector<NniSwap> &nni_log() const { return nni_log_; }
   int nni_pattern_terms(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<uint8_t> &terms);
+  // the weighted counterpart (k_snk_nni_eval_vals): rows[(1 + 2 i + k) * P + p] = the per-pattern length of the tree after move k of
+  // branch i at pattern p, rows[p] = the current tree's at root_taxon's edge; 0 for a pattern the engine drops
+  int nni_pattern_lengths(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<uint16_t> &rows);
   // the same climb under -bb: every tree it looks at is booked by the attached UFBoot tracker (save_all_trees == 2: the current
   // tree at the start of every scoring step, iqtree.cpp:2181-2183, and both NNIs of every evaluated branch, phylotree.cpp:3937)
   int ufboot_optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t *score, int32_t *nni_count, int32_t *nni_steps);
@@ -478,11 +481,17 @@ class Engine {
   struct NniScored { NniSwap mv; uint32_t len; };
   int nni_check(int root_taxon) const;
   int nni_check_tree(int root_taxon) const;      // ... without the refusal of a tracker
-  // masks: the mask-writing kernel, its rows into d_nni_planes_
+  // masks: the mask-writing kernel, its rows into d_nni_planes_ (weighted engine: the rows of per-pattern lengths into d_nni_vals_)
   int nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<NniSwap> *moves, bool masks = false);
   int nni_climb(int root_taxon, bool speednni, int max_steps, bool tracked, uint32_t *score, int32_t *nni_count, int32_t *nni_steps);
   // saveCurrentTree for the 1 + 2 * branches trees of one scoring step (cur = the current tree's length)
   int nni_book_step(const std::vector<NniBranch> &br, const std::vector<uint32_t> &len, const std::vector<NniSwap> &mv, uint32_t cur);
+  int nni_book_step_snk(const std::vector<NniBranch> &br, const std::vector<uint32_t> &len, const std::vector<NniSwap> &mv, uint32_t cur);
+  struct NniReplay;                              // the host replay the two steps share
+  template <class Product>
+  int nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home, const std::vector<uint32_t> &part, const std::vector<uint32_t> &crow,
+                         const std::vector<uint8_t> &pass, const std::vector<uint32_t> *sel_rows, int rows_p, bool have_C, Product product,
+                         std::vector<UfbEvent> &events);
   void nni_full_order(int root_taxon, std::vector<NniBranch> &br) const;
   void nni_swap(const NniSwap &m);
   std::vector<NniSwap> nni_log_;
@@ -492,9 +501,15 @@ class Engine {
   // iqtree.cpp:2258); "nni_kept_worse" counts the steps whose moves stayed although the tree came out longer than the best of them
   int nni_weighted_ = 0;
   uint64_t nni_kept_worse_ = 0;
+  // option "nni_weighted_tracked" (with "nni_weighted"): mpf_ufboot_optimize_nni and mpf_nni_pattern_lengths are served on the weighted
+  // engine (k_snk_nni_eval_vals, nni_book_step_snk); 0: refused as before
+  int nni_weighted_tracked_ = 0;
   uint64_t nni_kernel_ns_ = 0;                   // option "timing": HIP-event time of the scoring kernels (read-only option "nni_kernel_ns")
   DevBuf<NniDesc> d_nni_desc_;
   DevBuf<uint32_t> d_nni_planes_;                // k_nni_eval_masks: [2 planes][3 rows per branch, padded to the product's row tile][Wp]
+  DevBuf<uint16_t> d_nni_vals_;                  // k_snk_nni_eval_vals: [2 rows per branch + the current tree's][Wp] per-pattern lengths
+  DevBuf<uint32_t> d_nni_vmax_;                  // ... the largest of them (atomic max)
+  PinBuf<uint32_t> h_nni_vmax_;
   DevBuf<unsigned long long> d_nni_out_;
   PinBuf<NniDesc> h_nni_desc_;
   PinBuf<unsigned long long> h_nni_out_;

@@ -2210,10 +2210,14 @@ __global__ __launch_bounds__(256) void k_snk_evaluate(const uint32_t *__restrict
 // own transform adds at most one more entry, so a subtree of t tips stays below 2 t highest_cost and everything here below
 // 2 n highest_cost: inside the engine's condition for the 16-bit form, 3 n highest_cost < 2^16 (Engine::pack) -- no fall-back needed.
 // BUF: the transform half behind one raw buffer (32-bit offsets); otherwise 64-bit pointers per row (a half of 4 GiB and more).
-template <int S, bool PK, bool BUF>
-__global__ __launch_bounds__(256) void k_snk_nni_eval(const uint32_t *__restrict__ vec, size_t moff, const NniDesc *__restrict__ desc,
-                                                      int n_br, const uint32_t *__restrict__ cost, const uint32_t *__restrict__ pwgt,
-                                                      unsigned long long *__restrict__ out, int We, int tiles)
+// VALS (the tracked climb, k_snk_nni_eval_vals): the per-pattern minima b0 / b1 -- the rows ParsTree::computeParsimonyBranch leaves
+// in _pattern_pars for the two swapped trees (parstree.cpp:460-461, :482-529) -- go to rows 2 br and 2 br + 1 of vals[][npat] as
+// 16-bit values, in the element layout of k_snk_scan's rows (k_vals_planes reads both alike), one atomicMax per wave into vmax.
+template <int S, bool PK, bool BUF, bool VALS>
+__device__ __forceinline__ void snk_nni_eval_body(const uint32_t *__restrict__ vec, size_t moff, const NniDesc *__restrict__ desc,
+                                                  int n_br, const uint32_t *__restrict__ cost, const uint32_t *__restrict__ pwgt,
+                                                  unsigned long long *__restrict__ out, int We, int tiles,
+                                                  uint16_t *__restrict__ vals, uint32_t npat, uint32_t *__restrict__ vmax)
 {
   typedef SnkT<PK> T;
   const int lane = threadIdx.x & 63;
@@ -2244,6 +2248,41 @@ __global__ __launch_bounds__(256) void k_snk_nni_eval(const uint32_t *__restrict
   const uint32_t t0 = wave_total<0>(valid ? T::wsum(b0, pwgt, e0) : 0u), t1 = wave_total<0>(valid ? T::wsum(b1, pwgt, e0) : 0u);
   if (lane == 0 && (t0 | t1))
     __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (VALS) {
+    uint32_t m = 0;
+    if (valid) {
+      uint16_t *r0 = vals + (size_t)(2 * br) * npat, *r1 = r0 + npat;
+      if constexpr (PK) {
+        *reinterpret_cast<us2 *>(r0 + 2 * e0) = b0;
+        *reinterpret_cast<us2 *>(r1 + 2 * e0) = b1;
+        m = max(max((uint32_t)b0.x, (uint32_t)b0.y), max((uint32_t)b1.x, (uint32_t)b1.y));
+      } else {
+        r0[e0] = (uint16_t)b0;
+        r1[e0] = (uint16_t)b1;
+        m = max((uint32_t)b0, (uint32_t)b1);
+      }
+    }
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, sh, 64));
+    if (lane == 0 && m) atomicMax(vmax, m);
+  }
+}
+
+template <int S, bool PK, bool BUF>
+__global__ __launch_bounds__(256) void k_snk_nni_eval(const uint32_t *__restrict__ vec, size_t moff, const NniDesc *__restrict__ desc,
+                                                      int n_br, const uint32_t *__restrict__ cost, const uint32_t *__restrict__ pwgt,
+                                                      unsigned long long *__restrict__ out, int We, int tiles)
+{
+  snk_nni_eval_body<S, PK, BUF, false>(vec, moff, desc, n_br, cost, pwgt, out, We, tiles, nullptr, 0u, nullptr);
+}
+
+template <int S, bool PK, bool BUF>
+__global__ __launch_bounds__(256) void k_snk_nni_eval_vals(const uint32_t *__restrict__ vec, size_t moff, const NniDesc *__restrict__ desc,
+                                                           int n_br, const uint32_t *__restrict__ cost, const uint32_t *__restrict__ pwgt,
+                                                           unsigned long long *__restrict__ out, int We, int tiles,
+                                                           uint16_t *__restrict__ vals, uint32_t npat, uint32_t *__restrict__ vmax)
+{
+  snk_nni_eval_body<S, PK, BUF, true>(vec, moff, desc, n_br, cost, pwgt, out, We, tiles, vals, npat, vmax);
 }
 
 // SPR / stepwise scan over a host-planned program (same ops as k_scan).  With m() the min-plus transform:
@@ -2751,16 +2790,20 @@ hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32
 }
 
 hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
-                               unsigned long long *out, bool wide_addr)
+                               unsigned long long *out, bool wide_addr, uint16_t *vals, uint32_t *vmax)
 {
   if (n_br <= 0) return hipSuccess;
-  if (!g.sankoff || !g.moff) return hipErrorInvalidValue;
+  if (!g.sankoff || !g.moff || (vals != nullptr) != (vmax != nullptr)) return hipErrorInvalidValue;
   const int We = snk_elems(g), tiles = (We + 63) / 64;
   dim3 grid((unsigned)(((long)n_br * tiles + 3) / 4)), block(256);
   const bool buf_ok = !wide_addr && (unsigned long long)g.moff * 4ull < (1ull << 32);      // the transform half behind one 32-bit-offset descriptor
   dispatch_snk(g, [&](auto S, auto PK) {
     dispatch_bool(buf_ok, [&](auto BUF) {
-      hipLaunchKernelGGL((k_snk_nni_eval<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles);
+      if (vals)
+        hipLaunchKernelGGL((k_snk_nni_eval_vals<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles, vals,
+                           (uint32_t)g.Wp, vmax);
+      else
+        hipLaunchKernelGGL((k_snk_nni_eval<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles);
     });
   });
   return hipGetLastError();

@@ -211,8 +211,10 @@ hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32
 // ... on the weighted engine (k_snk_nni_eval): the same descriptors; out[i] = the FULL weighted length after move 0 | after move 1
 // << 32, rooted at the branch with node2's side as the parent (ParsTree::computeParsimonyBranch) -- nothing to add on the host.
 // wide_addr: 64-bit pointers per row whatever the size of the store (what a transform half of 4 GiB and more takes by itself)
+// vals / vmax (both or neither; the tracked climb, k_snk_nni_eval_vals): rows 2 i and 2 i + 1 of vals[][g.Wp] take the per-pattern
+// lengths of the trees after move 0 / move 1 of branch i, 16 bits each, laid out as launch_scan's vals rows; *vmax the largest of them
 hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
-                               unsigned long long *out, bool wide_addr = false);
+                               unsigned long long *out, bool wide_addr = false, uint16_t *vals = nullptr, uint32_t *vmax = nullptr);
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,
                        const ScanOp *ops, uint32_t *out, int max_depth,
                        uint32_t *host_out = nullptr, uint32_t n_out = 0, uint32_t *done = nullptr,   // as launch_scan_walk

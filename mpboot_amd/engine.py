@@ -34,7 +34,7 @@ EXPORTS = [
     "mpf_min_pars_score_patterns", "mpf_mst_scores", "mpf_segment_patterns", "mpf_remain_bounds",
     "mpf_cost_matrix_load", "mpf_cost_matrix_triangle_fix",
     "mpf_iq_random_nnis", "mpf_iq_perturb_weights", "mpf_iq_topology_key", "mpf_ufboot_adopt", "mpf_optimize_spr_many", "mpf_optimize_spr_many_round",
-    "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves", "mpf_ufboot_optimize_nni", "mpf_nni_pattern_terms",
+    "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves", "mpf_ufboot_optimize_nni", "mpf_nni_pattern_terms", "mpf_nni_pattern_lengths",
 ]
 
 
@@ -170,6 +170,7 @@ def load_library():
         L.mpf_get_nni_moves.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_ufboot_optimize_nni.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
         L.mpf_nni_pattern_terms.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+        L.mpf_nni_pattern_lengths.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -567,7 +568,7 @@ class FitchEngine:
         (node2's side the parent, ParsTree::computeParsimonyBranch), the tree's own length taken at the leaf root_taxon
         (ParsTree::computeParsimony), and NO rollback (iqtree.cpp:2258): a step that left the tree longer than its best NNI
         promised keeps its moves and is not counted; get_option("nni_kept_worse") counts such steps.  Not served there: a
-        tracker attached, ufboot_optimize_nni, nni_pattern_terms."""
+        tracker attached, nni_pattern_terms, and -- unless set_option("nni_weighted_tracked", 1) as well -- ufboot_optimize_nni."""
         s, cnt, steps = C.c_uint32(), C.c_int32(), C.c_int32()
         _chk(load_library().mpf_optimize_nni(self.h, root_taxon, int(bool(speednni)), max_steps, C.byref(s), C.byref(cnt),
                                              C.byref(steps)))
@@ -599,6 +600,22 @@ class FitchEngine:
         t = np.zeros(3 * max(m, 1) * self.P, dtype=np.uint8)
         _chk(L.mpf_nni_pattern_terms(self.h, root_taxon, m, _p(a), _p(b), _p(ln), _p(t), C.byref(n)))
         return a[:m].copy(), b[:m].copy(), ln[:2 * m].reshape(m, 2).copy(), t[:3 * m * self.P].reshape(m, 3, self.P).copy()
+
+    def nni_pattern_lengths(self, root_taxon: int = 1):
+        """nni_scores by the row-writing kernel of the tracked weighted climb (set_option("nni_weighted", 1) and
+        set_option("nni_weighted_tracked", 1); refused on a Fitch engine): (node1[m], node2[m], len[m][2],
+        rows[1 + 2 m][n_patterns] uint16) -- row 0 the current tree's per-pattern lengths at root_taxon's edge, row 1 + 2 i + k those
+        of the tree after move k of branch i, rooted at that branch with node2's side the parent"""
+        L = load_library()
+        n = C.c_int32()
+        _chk(L.mpf_nni_pattern_lengths(self.h, root_taxon, -1, None, None, None, None, C.byref(n)))
+        m = n.value
+        a = np.zeros(max(m, 1), dtype=np.int32)
+        b = np.zeros(max(m, 1), dtype=np.int32)
+        ln = np.zeros(2 * max(m, 1), dtype=np.uint32)
+        r = np.zeros((1 + 2 * m) * self.P, dtype=np.uint16)
+        _chk(L.mpf_nni_pattern_lengths(self.h, root_taxon, m, _p(a), _p(b), _p(ln), _p(r), C.byref(n)))
+        return a[:m].copy(), b[:m].copy(), ln[:2 * m].reshape(m, 2).copy(), r.reshape(1 + 2 * m, self.P)
 
     def nni_moves(self):
         """the swaps of the last optimize_nni, reverts included: int32[k][4] rows (node1, slot1, node2, slot2)"""
@@ -643,7 +660,9 @@ class FitchEngine:
 
     def ufboot_optimize_nni(self, root_taxon: int = 1, speednni: bool = True, max_steps: int = 50):
         """optimize_nni under -bb: the attached tracker books the current tree of every scoring step and both NNIs of every
-        evaluated branch (mpf_ufboot_optimize_nni) -> (length, nni_count, nni_steps)"""
+        evaluated branch (mpf_ufboot_optimize_nni) -> (length, nni_count, nni_steps).  A weighted engine serves it after
+        set_option("nni_weighted", 1) and set_option("nni_weighted_tracked", 1) (defaults 0: MpfError -6): every booked tree with
+        its own row of per-pattern lengths -- a candidate's at its branch, the current tree's at the leaf root_taxon"""
         s, cnt, steps = C.c_uint32(), C.c_int32(), C.c_int32()
         _chk(load_library().mpf_ufboot_optimize_nni(self.h, root_taxon, int(bool(speednni)), max_steps, C.byref(s), C.byref(cnt),
                                                     C.byref(steps)))

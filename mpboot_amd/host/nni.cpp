@@ -67,11 +67,12 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
   const size_t nb = br.size();
   len.assign(2 * nb, 0u);
   if (moves) moves->assign(2 * nb, NniSwap{0, 0, 0, 0});
-  if (!nb) return MPF_OK;
-  HIPCHK(h_nni_desc_.reserve(nb));
-  HIPCHK(d_nni_desc_.reserve(nb));
-  HIPCHK(h_nni_out_.reserve(nb));
-  HIPCHK(d_nni_out_.reserve(nb));
+  const bool snk_rows = sankoff_ && masks;         // (the current tree's row is made even when no branch is scored)
+  if (!nb && !snk_rows) return MPF_OK;
+  HIPCHK(h_nni_desc_.reserve(std::max<size_t>(nb, 1)));
+  HIPCHK(d_nni_desc_.reserve(std::max<size_t>(nb, 1)));
+  HIPCHK(h_nni_out_.reserve(std::max<size_t>(nb, 1)));
+  HIPCHK(d_nni_out_.reserve(std::max<size_t>(nb, 1)));
   std::vector<uint32_t> base(nb);
   auto score = [&](int r) { return tip(r) ? 0u : sc_[r]; };
   for (size_t i = 0; i < nb; i++) {
@@ -92,12 +93,23 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
   }
   bool wm = nni_vw_ <= 0 && g_.S == 4 && g_.shoff && shadow_ok_;
   int vw = nni_vw_ > 0 ? nni_vw_ : (nni_vw_ == 0 ? 1 : g_.vw);
-  HIPCHK(hipMemcpyAsync(d_nni_desc_.p, h_nni_desc_.p, nb * sizeof(NniDesc), hipMemcpyHostToDevice, st_));
-  HIPCHK(hipMemsetAsync(d_nni_out_.p, 0, nb * sizeof(unsigned long long), st_));
+  if (nb) {
+    HIPCHK(hipMemcpyAsync(d_nni_desc_.p, h_nni_desc_.p, nb * sizeof(NniDesc), hipMemcpyHostToDevice, st_));
+    HIPCHK(hipMemsetAsync(d_nni_out_.p, 0, nb * sizeof(unsigned long long), st_));
+  }
+  if (snk_rows) {
+    if (!nni_weighted_tracked_) { set_error("NNI climb: the tracked climb is not served on the weighted engine"); return MPF_E_UNSUPPORTED; }
+    HIPCHK(d_nni_vals_.reserve((2 * nb + 1) * (size_t)g_.Wp));
+    HIPCHK(d_nni_vmax_.reserve(4));
+    HIPCHK(h_nni_vmax_.reserve(4));
+    HIPCHK(hipMemsetAsync(d_nni_vmax_.p, 0, sizeof(uint32_t), st_));
+  }
   if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
-  if (sankoff_) {
+  if (snk_rows) {
+    // tracked climb: the same lengths, and the rows _pattern_pars holds when each tree is booked (k_snk_nni_eval_vals)
+    HIPCHK(launch_snk_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, force_big_ != 0, d_nni_vals_.p, d_nni_vmax_.p));
+  } else if (sankoff_) {
     // ParsTree::computeParsimonyBranch(node1->findNeighbor(node2), node1) for both moves of every branch (k_snk_nni_eval)
-    if (masks) { set_error("NNI climb: the tracked climb is not served on the weighted engine"); return MPF_E_UNSUPPORTED; }
     HIPCHK(launch_snk_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, force_big_ != 0));
   } else if (masks) {
     // tracked climb: the two bit planes of (h, c_0, c_1) per branch, each padded to the product's row tile
@@ -110,7 +122,13 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
   } else
     HIPCHK(launch_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm));
   if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
-  HIPCHK(hipMemcpyAsync(h_nni_out_.p, d_nni_out_.p, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st_));
+  if (snk_rows) {
+    // row 2 nb: the current tree at the root leaf's edge, the rest of the tree the parent -- what ParsTree::computeParsimony() wrote
+    // (parstree.cpp:101-116) and the row whose weighted sum is tree_length() under the caller's StartGuard
+    HIPCHK(launch_sankoff_pattern(st_, g_, d_vec_, slot(back_[start_]), slot(start_), d_nni_vals_.p + 2 * nb * (size_t)g_.Wp, d_nni_vmax_.p));
+    HIPCHK(hipMemcpyAsync(h_nni_vmax_.p, d_nni_vmax_.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+  }
+  if (nb) HIPCHK(hipMemcpyAsync(h_nni_out_.p, d_nni_out_.p, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st_));
   HIPCHK(hipStreamSynchronize(st_));
   float ms = 0.f;
   if (timing_ && hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) nni_kernel_ns_ += (uint64_t)((double)ms * 1e6);
@@ -119,7 +137,7 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
     len[2 * i] = base[i] + (uint32_t)(o & 0xFFFFFFFFull);
     len[2 * i + 1] = base[i] + (uint32_t)(o >> 32);
   }
-  nni_launches_++;
+  if (nb) nni_launches_++;
   nni_branches_ += nb;
   return MPF_OK;
 }
@@ -198,7 +216,7 @@ int Engine::nni_climb(int root_taxon, bool speednni, int max_steps, bool tracked
       else nni_full_order(root_taxon, br);
       rc = nni_eval(br, len, &mv, tracked);
       if (rc) return rc;
-      if (tracked) { rc = nni_book_step(br, len, mv, cur); if (rc) return rc; }
+      if (tracked) { rc = sankoff_ ? nni_book_step_snk(br, len, mv, cur) : nni_book_step(br, len, mv, cur); if (rc) return rc; }
       plus.clear();
       for (size_t i = 0; i < br.size(); i++) {
         const int k = len[2 * i] < len[2 * i + 1] ? 0 : 1;               // :3971-3975
@@ -276,6 +294,162 @@ int Engine::nni_pattern_terms(int root_taxon, std::vector<NniBranch> &br, std::v
   return MPF_OK;
 }
 
+// the weighted counterpart: one full evaluation by k_snk_nni_eval_vals, its rows read back per pattern
+int Engine::nni_pattern_lengths(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &len, std::vector<uint16_t> &rows)
+{
+  if (!sankoff_) { set_error("NNI pattern lengths: weighted engines only (a Fitch engine has mpf_nni_pattern_terms)"); return MPF_E_UNSUPPORTED; }
+  if (!nni_weighted_ || !nni_weighted_tracked_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
+  int rc = nni_check_tree(root_taxon);
+  if (rc) return rc;
+  StartGuard at_root(*this, root_taxon);           // (the current tree's row is the one at this leaf's edge)
+  br.clear();
+  nni_full_order(root_taxon, br);
+  rc = nni_eval(br, len, nullptr, true);
+  if (rc) return rc;
+  const size_t nb = br.size(), Wp = (size_t)g_.Wp;
+  rows.assign((1 + 2 * nb) * (size_t)P_, 0);
+  std::vector<uint16_t> h((2 * nb + 1) * Wp);
+  HIPCHK(hipMemcpy(h.data(), d_nni_vals_.p, h.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  for (int p = 0; p < P_; p++) {
+    const int j = first_site_[(size_t)p];          // (weighted engine: the pattern's place among the kept ones)
+    if (j < 0) continue;
+    rows[(size_t)p] = h[2 * nb * Wp + (size_t)j];
+    for (size_t c = 0; c < 2 * nb; c++) rows[(1 + c) * (size_t)P_ + (size_t)p] = h[c * Wp + (size_t)j];
+  }
+  return MPF_OK;
+}
+
+// ---- what the two booking steps share: the replay of one step's 1 + 2 nb trees in the reference's order (as in spr_sweeps_ufboot)
+struct Engine::NniReplay {
+  Engine &e;
+  UfbState &u;
+  const std::vector<NniSwap> &mv;
+  std::vector<int32_t> bk;
+  std::string cand_key;
+  const UfbDeferCtx dctx{};
+
+  NniReplay(Engine &eng, const std::vector<NniSwap> &moves) : e(eng), u(*eng.ufb_), mv(moves) {}
+  // the tree after candidate c's swap
+  void swapped(uint32_t c, std::vector<int32_t> &t) const
+  {
+    t = e.back_;
+    const NniSwap &m = mv[c];
+    const int p = 3 * m.node1 + m.slot1, q = 3 * m.node2 + m.slot2, rp = t[(size_t)p], rq = t[(size_t)q];
+    t[(size_t)p] = rq; t[(size_t)rq] = p;
+    t[(size_t)q] = rp; t[(size_t)rp] = q;
+  }
+  const std::string &topology_key(uint32_t cand_code)
+  {
+    if (cand_code == 0xFFFFFFFFu) {
+      if (u.self_key_epoch != (uint64_t)e.topo_epoch_) { e.canonical_topology(e.back_, u.self_key); u.self_key_epoch = (uint64_t)e.topo_epoch_; }
+      return u.self_key;
+    }
+    swapped(cand_code, bk);
+    e.canonical_topology(bk, cand_key);
+    return cand_key;
+  }
+  int64_t lookup_topology(int64_t tree_index, uint32_t cand_code)
+  {
+    u.lookups++;
+    return u.topo_index.emplace(topology_key(cand_code), tree_index).first->second;
+  }
+  // the current tree under self_len, every sample offered R_T (u.h_rt) on the host
+  void book_self(uint32_t self_len, bool pass)
+  {
+    u.cur_logl_now = -(int32_t)self_len;
+    int64_t tree_index = e.ufb_book_tree(self_len, pass, 0xFFFFFFFFu, false, [&](uint32_t cc) -> const std::string & { return topology_key(cc); });
+    if (tree_index < 0) return;
+    bool looked_up = false;
+    for (int c2 = 0; c2 < u.Bl; c2++)
+      e.ufb_one_event((uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2], tree_index, looked_up, 0xFFFFFFFFu,
+                      [&](int64_t ti, uint32_t cc) { return lookup_topology(ti, cc); }, dctx);
+  }
+  // the candidates in evaluation order, move 0 then move 1 (candidate c has output index 1 + c); then the trees some sample took
+  void book_candidates(const std::vector<uint32_t> &blen, const std::vector<uint8_t> &pass, const std::vector<UfbEvent> &events)
+  {
+    size_t ep = 0;
+    for (uint32_t c = 0; c < (uint32_t)blen.size(); c++) {
+      u.cur_logl_now = -(int32_t)blen[c];
+      int64_t tree_index = e.ufb_book_tree(blen[c], pass[c] != 0, c, false, [&](uint32_t cc) -> const std::string & { return topology_key(cc); });
+      if (tree_index < 0) continue;
+      const uint32_t idx = 1u + c;
+      while (ep < events.size() && events[ep].idx < idx) ep++;
+      bool looked_up = false;
+      for (; ep < events.size() && events[ep].idx == idx; ep++)
+        e.ufb_one_event(events[ep].b, events[ep].s, tree_index, looked_up, c, [&](int64_t ti, uint32_t cc) { return lookup_topology(ti, cc); }, dctx);
+    }
+    // a tree a sample accepted is remembered as (this step's tree, swap) and materialised only if still referenced
+    for (const UfbState::Pending &pe : u.pending) {
+      if (u.refs[(size_t)pe.tree_index] <= 0 || u.store.count(pe.tree_index)) continue;
+      if (pe.cand == 0xFFFFFFFFu) u.store.emplace(pe.tree_index, e.back_);
+      else { swapped(pe.cand, bk); u.store.emplace(pe.tree_index, bk); }
+      u.stored++;
+    }
+    u.pending.clear();
+  }
+};
+
+// One step's event extraction.  Output indices: 0 = the current tree (offered on the host), 1 + c = candidate c, behind them the
+// home slots; part[idx] = the part of a candidate (0xFFFFFFFF: no candidate), home[part] = its home slot, crow[idx] = the row of C
+// an index reads (0xFFFFFFFF: none), pass[c]: candidate c takes part.  sel_rows (or nullptr): the mask rows a compact product
+// multiplies, handed to product(rows_p, device copy) -- which runs here unless the caller has C already.  events: in replay order.
+// staging: thr[n_parts] | home[n_parts] | best[Bp] | crow[n_idx] | cost[n_idx] | (even) info[n_idx] as pairs | sel[rows_p] | event counter
+template <class Product>
+int Engine::nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home, const std::vector<uint32_t> &part, const std::vector<uint32_t> &crow,
+                               const std::vector<uint8_t> &pass, const std::vector<uint32_t> *sel_rows, int rows_p, bool have_C, Product product,
+                               std::vector<UfbEvent> &events)
+{
+  UfbState &u = *ufb_;
+  const size_t n_parts = home.size();
+  const size_t o_home = n_parts, o_best = 2 * n_parts, o_crow = o_best + (size_t)u.Bp, o_cost = o_crow + n_idx;
+  const size_t o_info = (o_cost + n_idx + 1) & ~(size_t)1, o_sel = o_info + 2 * (size_t)n_idx, o_cnt = o_sel + (sel_rows ? (size_t)rows_p : 0);
+  UCHK(u.h_small.reserve(o_cnt + 4));
+  UCHK(u.thr.reserve(o_cnt + 4));
+  uint32_t *sm = u.h_small.p;
+  std::memset(sm, 0, (o_cnt + 1) * sizeof(uint32_t));           // (padding columns of best: 0 -> never an event; padding rows multiply mask row 0)
+  for (size_t i = 0; i < n_parts; i++) { sm[i] = 1u; sm[o_home + i] = home[i]; }            // a candidate takes part iff cost < 1
+  for (int c2 = 0; c2 < u.Bl; c2++) sm[o_best + (size_t)c2] = ufb_event_bound((uint32_t)u.ids[(size_t)c2]);
+  std::memcpy(sm + o_crow, crow.data(), (size_t)n_idx * sizeof(uint32_t));
+  for (uint32_t idx = 0; idx < n_idx; idx++) { sm[o_info + 2 * idx] = 0u; sm[o_info + 2 * idx + 1] = 0xFFFFFFFFu; }      // the current tree, the home slots
+  for (uint32_t c = 0; c < (uint32_t)pass.size(); c++) {
+    sm[o_cost + 1 + c] = pass[c] ? 0u : 1u;
+    sm[o_info + 2 * (1 + c)] = crow[1 + c];
+    sm[o_info + 2 * (1 + c) + 1] = part[1 + c];
+  }
+  if (sel_rows) std::memcpy(sm + o_sel, sel_rows->data(), sel_rows->size() * sizeof(uint32_t));
+  UCHK(hipMemcpyAsync(u.thr.p, sm, (o_cnt + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+  if (!have_C) { int rc = product(rows_p, sel_rows ? u.thr.p + o_sel : nullptr); if (rc) return rc; }
+  const uint32_t nch = ufb_chunks(n_idx);
+  UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
+  UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
+  if (u.ev.cap == 0) { const size_t c0 = (size_t)std::min<int64_t>(ufb_event_cap_, 1 << 18); UCHK(u.ev.reserve(c0)); }
+  uint32_t *d_evcount = u.thr.p + o_cnt;
+  uint32_t n_ev = 0;
+  for (bool again = false;; again = true) {
+    if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
+    UCHK(launch_ufb_events(st_, reinterpret_cast<const uint2 *>(u.thr.p + o_info), u.thr.p + o_cost, u.thr.p, u.thr.p + o_home, u.thr.p + o_crow, u.C.p,
+                           u.Bp, u.Bl, u.rt.p, u.thr.p + o_best, n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, 0));
+    UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+    UCHK(hipStreamSynchronize(st_));
+    n_ev = u.h_small.p[0];
+    if (n_ev <= u.ev.cap) break;
+    UCHK(u.ev.reserve((size_t)n_ev));              // more events than room: grow and extract again
+  }
+  events.clear();
+  if (n_ev) {
+    UCHK(u.h_ev.reserve((size_t)n_ev));
+    UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_ev * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
+    UCHK(hipStreamSynchronize(st_));
+    events.assign(u.h_ev.p, u.h_ev.p + n_ev);
+    for (UfbEvent &e : events) e.b = (uint32_t)u.ids[(size_t)e.b];
+    std::vector<UfbEvent> tmp;
+    std::vector<uint32_t> count;
+    sort_events(events, tmp, count, n_idx, (uint32_t)u.B);
+  }
+  u.events += n_ev;
+  return MPF_OK;
+}
+
 // ---------------------------------------------------------------- the climb under -bb
 //
 // With save_all_trees == 2 a scoring step of optimizeNNI hands 1 + 2 * branches trees to IQTree::saveCurrentTree, in this order:
@@ -338,42 +512,11 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
   for (uint32_t i = 0; i < nb; i++)
     for (uint32_t k = 0; k < 2; k++)
       blen[2 * i + k] = ratchet ? (uint32_t)((int64_t)u.rt_orig - (int64_t)u.h_col.p[3 * i] + (int64_t)u.h_col.p[3 * i + 1 + k]) : len[2 * i + k];
-
-  // ---- the replay's tools (as in spr_sweeps_ufboot)
-  std::vector<int32_t> bk;
-  std::string cand_key;
-  auto swapped = [&](uint32_t c, std::vector<int32_t> &t) {
-    t = back_;
-    const NniSwap &m = mv[c];
-    const int p = 3 * m.node1 + m.slot1, q = 3 * m.node2 + m.slot2, rp = t[(size_t)p], rq = t[(size_t)q];
-    t[(size_t)p] = rq; t[(size_t)rq] = p;
-    t[(size_t)q] = rp; t[(size_t)rp] = q;
-  };
-  auto topology_key = [&](uint32_t cand_code) -> const std::string & {
-    if (cand_code == 0xFFFFFFFFu) {
-      if (u.self_key_epoch != (uint64_t)topo_epoch_) { canonical_topology(back_, u.self_key); u.self_key_epoch = (uint64_t)topo_epoch_; }
-      return u.self_key;
-    }
-    swapped(cand_code, bk);
-    canonical_topology(bk, cand_key);
-    return cand_key;
-  };
-  auto lookup_topology = [&](int64_t tree_index, uint32_t cand_code) -> int64_t {
-    u.lookups++;
-    return u.topo_index.emplace(topology_key(cand_code), tree_index).first->second;
-  };
-  const UfbDeferCtx dctx{};
+  NniReplay replay(*this, mv);
 
   // ---- the current tree: its own length (ratchet: its length on the original alignment), every sample from R_T
-  {
-    const uint32_t self_len = ratchet ? u.rt_orig : cur;
-    u.cur_logl_now = -(int32_t)self_len;
-    int64_t tree_index = ufb_book_tree(self_len, self_len <= mp_max, 0xFFFFFFFFu, false, topology_key);
-    if (tree_index >= 0) {
-      bool looked_up = false;
-      for (int c2 = 0; c2 < u.Bl; c2++) ufb_one_event((uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2], tree_index, looked_up, 0xFFFFFFFFu, lookup_topology, dctx);
-    }
-  }
+  const uint32_t self_len = ratchet ? u.rt_orig : cur;
+  replay.book_self(self_len, self_len <= mp_max);
 
   // ---- the candidates that pass: product (unless a ratchet step has it), extraction
   std::vector<uint8_t> pass(2 * (size_t)nb);
@@ -382,9 +525,11 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
   std::vector<UfbEvent> events;
   if (n_pass) {
     const bool compact = have_cut && !ratchet;
-    std::vector<uint32_t> sel_rows;
+    std::vector<uint32_t> sel_rows, home(nb), part((size_t)n_idx, 0xFFFFFFFFu);
     std::vector<uint32_t> crow((size_t)n_idx, 0xFFFFFFFFu);
     for (uint32_t i = 0; i < nb; i++) {
+      home[i] = 1u + 2u * nb + i;
+      part[1 + 2 * i] = part[2 + 2 * i] = i;
       if (!pass[2 * i] && !pass[2 * i + 1]) continue;
       if (!compact) {
         crow[1 + 2 * i] = 3 * i + 1; crow[2 + 2 * i] = 3 * i + 2; crow[1 + 2 * nb + i] = 3 * i;
@@ -395,75 +540,115 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
         if (pass[2 * i + k]) { crow[1 + 2 * i + k] = (uint32_t)sel_rows.size(); sel_rows.push_back(3 * i + 1 + k); }
     }
     const int rows_p = compact ? round_up((int)sel_rows.size(), kUfbRowTile) : mask_rows_p;
-    // staging: thr[nb] | home[nb] | best[Bp] | crow[n_idx] | cost[n_idx] | (even) info[n_idx] as pairs | sel[rows_p] | event counter
-    const size_t o_home = nb, o_best = 2 * (size_t)nb, o_crow = o_best + (size_t)u.Bp, o_cost = o_crow + n_idx;
-    const size_t o_info = (o_cost + n_idx + 1) & ~(size_t)1, o_sel = o_info + 2 * (size_t)n_idx, o_cnt = o_sel + (compact ? (size_t)rows_p : 0);
-    UCHK(u.h_small.reserve(o_cnt + 4));
-    UCHK(u.thr.reserve(o_cnt + 4));
-    uint32_t *sm = u.h_small.p;
-    std::memset(sm, 0, (o_cnt + 1) * sizeof(uint32_t));           // (padding columns of best: 0 -> never an event; padding rows multiply mask row 0)
-    for (uint32_t i = 0; i < nb; i++) { sm[i] = 1u; sm[o_home + i] = 1u + 2u * nb + i; }     // a candidate takes part iff cost < 1
-    for (int c2 = 0; c2 < u.Bl; c2++) sm[o_best + (size_t)c2] = ufb_event_bound((uint32_t)u.ids[(size_t)c2]);
-    std::memcpy(sm + o_crow, crow.data(), (size_t)n_idx * sizeof(uint32_t));
-    for (uint32_t idx = 0; idx < n_idx; idx++) { sm[o_info + 2 * idx] = 0u; sm[o_info + 2 * idx + 1] = 0xFFFFFFFFu; }      // the current tree, the home slots
-    for (uint32_t c = 0; c < 2 * nb; c++) {
-      sm[o_cost + 1 + c] = pass[c] ? 0u : 1u;
-      sm[o_info + 2 * (1 + c)] = crow[1 + c];
-      sm[o_info + 2 * (1 + c) + 1] = c / 2;
-    }
-    if (compact) std::memcpy(sm + o_sel, sel_rows.data(), sel_rows.size() * sizeof(uint32_t));
-    UCHK(hipMemcpyAsync(u.thr.p, sm, (o_cnt + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
-    if (!have_C) { int rc = product(rows_p, compact ? u.thr.p + o_sel : nullptr); if (rc) return rc; }
-    const uint32_t nch = ufb_chunks(n_idx);
-    UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
-    UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
-    if (u.ev.cap == 0) { const size_t c0 = (size_t)std::min<int64_t>(ufb_event_cap_, 1 << 18); UCHK(u.ev.reserve(c0)); }
-    uint32_t *d_evcount = u.thr.p + o_cnt;
-    uint32_t n_ev = 0;
-    for (bool again = false;; again = true) {
-      if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
-      UCHK(launch_ufb_events(st_, reinterpret_cast<const uint2 *>(u.thr.p + o_info), u.thr.p + o_cost, u.thr.p, u.thr.p + o_home, u.thr.p + o_crow, u.C.p,
-                             u.Bp, u.Bl, u.rt.p, u.thr.p + o_best, n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, 0));
-      UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-      UCHK(hipStreamSynchronize(st_));
-      n_ev = u.h_small.p[0];
-      if (n_ev <= u.ev.cap) break;
-      UCHK(u.ev.reserve((size_t)n_ev));              // more events than room: grow and extract again
-    }
-    if (n_ev) {
-      UCHK(u.h_ev.reserve((size_t)n_ev));
-      UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_ev * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-      UCHK(hipStreamSynchronize(st_));
-      events.assign(u.h_ev.p, u.h_ev.p + n_ev);
-      for (UfbEvent &e : events) e.b = (uint32_t)u.ids[(size_t)e.b];
-      std::vector<UfbEvent> tmp;
-      std::vector<uint32_t> count;
-      sort_events(events, tmp, count, n_idx, (uint32_t)u.B);
-    }
-    u.events += n_ev;
+    int rc = nni_extract_events(n_idx, home, part, crow, pass, compact ? &sel_rows : nullptr, rows_p, have_C, product, events);
+    if (rc) return rc;
   }
   const double t1 = now_ms();
   u.t_dev += t1 - t0;
+  replay.book_candidates(blen, pass, events);
+  u.t_replay += now_ms() - t1;
+  return MPF_OK;
+}
 
-  // ---- the candidates in evaluation order, move 0 then move 1
-  size_t ep = 0;
+// ---------------------------------------------------------------- ... on the weighted engine (-cost m -nni_pars -bb)
+//
+// The same 1 + 2 nb trees in the same order; no rollback steps (iqtree.cpp:2258), so a kept-worse step is followed by an ordinary
+// scoring step that books the current tree under the longer curScore.  _pattern_pars of a candidate is the row of per-pattern minima
+// ParsTree::computeParsimonyBranch has just written (parstree.cpp:460-461, :482-529), of the current tree the row
+// ParsTree::computeParsimony() wrote at the root leaf's edge (:101-116): nni_eval has left them as rows 2 i + k and 2 nb of
+// d_nni_vals_, 16 bits per pattern.  The chain is spr_sweeps_ufboot_snk's: K = bits of the largest value, k_vals_planes, K runs of
+// k_bitgemm per weight plane.  A tree's score under sample b is its OWN product row -- R_T is the current tree's row (launch_colsum
+// of one row) and the home row of every candidate, so that R_T - C[home] + C[c] = C[c]; there is no ufb_current_tree_reps pass and no
+// join mask.  Output indices: 0 = the current tree, 1 + c = candidate c, 1 + 2 nb = the one home slot.
+int Engine::nni_book_step_snk(const std::vector<NniBranch> &br, const std::vector<uint32_t> &len, const std::vector<NniSwap> &mv, uint32_t cur)
+{
+  UfbState &u = *ufb_;
+  const uint32_t nb = (uint32_t)br.size(), n_idx = 2u + 2u * nb, R = 2u * nb;       // R: the current tree's row of vals
+  const bool ratchet = u.ratchet;
+  const int oc = u.Bl;
+  const uint32_t npat = (uint32_t)g_.Wp;
+  u.nni_booked += 1u + 2u * (uint64_t)nb;
+  u.batches++;
+  const bool have_cut = u.logl_cutoff != 0.0;
+  const double lim = -u.logl_cutoff + 1e-4;        // iqtree.cpp:3343
+  const bool none_pass = have_cut && lim <= 0.0;
+  const uint32_t mp_max = have_cut ? (none_pass ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
+  if (none_pass) return MPF_OK;
+  std::vector<uint32_t> blen(len.begin(), len.begin() + 2 * (size_t)nb);
+  std::vector<uint8_t> pass(2 * (size_t)nb);
+  uint32_t n_pass = 0;
+  if (!ratchet) {
+    for (size_t c = 0; c < pass.size(); c++) { pass[c] = blen[c] <= mp_max; n_pass += pass[c]; }
+    if (!n_pass && cur > mp_max) return MPF_OK;    // nothing of this step is booked: nothing to multiply
+  }
+  const double t0 = now_ms();
+  // ---- K from vmax (nni_eval has waited for it), the bit planes of all 2 nb + 1 rows
+  int K = 1;
+  while (K < 16 && (h_nni_vmax_.p[0] >> K)) K++;
+  const uint32_t rows = 2u * nb + 1u;
+  const int plane_rows_p = round_up((int)rows, kUfbRowTile);
+  const size_t plane_words = (size_t)plane_rows_p * (size_t)u.Wp_s;
+  UCHK(u.bitp.reserve((size_t)K * plane_words));
+  UCHK(hipMemsetAsync(u.bitp.p, 0, (size_t)K * plane_words * sizeof(uint32_t), st_));
+  for (uint32_t r0 = 0; r0 < rows; r0 += 32768u)                  // (grid.y limit)
+    UCHK(launch_vals_planes(st_, d_nni_vals_.p + (size_t)r0 * npat, std::min(32768u, rows - r0), npat, K, u.bitp.p + (size_t)r0 * u.Wp_s,
+                            (uint32_t)plane_rows_p, (uint32_t)u.Wp_s));
+  uint32_t cur_row = R;                            // the current tree's row of C
+  bool timed = false;
+  auto product = [&](int rows_p, const uint32_t *d_sel) -> int {
+    UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
+    if (timing_) { UCHK(hipEventRecord(ev2_, st_)); timed = true; }
+    bool first = true;
+    for (int k = 0; k < K; k++)
+      for (int pl = 0; pl < u.planes; pl++, first = false)
+        UCHK(launch_bitgemm(st_, u.bitp.p + (size_t)k * plane_words, rows_p, u.Wp_s, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p,
+                            (1 << k) << (7 * pl), first ? 0 : 1, d_sel));
+    if (timing_) UCHK(hipEventRecord(ev3_, st_));
+    u.gemm_rows += (uint64_t)rows_p * (uint64_t)K;
+    UCHK(u.rt.reserve((size_t)u.Bp));
+    UCHK(launch_colsum(st_, u.C.p + (size_t)cur_row * u.Bp, 1, u.Bp, u.rt.p));       // R_T = the current tree's own row
+    UCHK(u.h_rt.reserve((size_t)u.Bp));
+    UCHK(hipMemcpyAsync(u.h_rt.p, u.rt.p, (size_t)(u.Bl + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+    return MPF_OK;
+  };
+  bool have_C = false;
+  uint32_t self_len = cur;
+  if (ratchet) {
+    // every row: the column of original frequencies gives each tree the length it is booked under (iqtree.cpp:3283-3294)
+    int rc = product(plane_rows_p, nullptr);
+    if (rc) return rc;
+    have_C = true;
+    UCHK(u.d_col.reserve((size_t)plane_rows_p));
+    UCHK(u.h_col.reserve((size_t)plane_rows_p));
+    UCHK(launch_ufb_column(st_, u.C.p, u.Bp, oc, rows, u.d_col.p));
+    UCHK(hipMemcpyAsync(u.h_col.p, u.d_col.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+    UCHK(hipStreamSynchronize(st_));
+    u.rt_orig = self_len = (uint32_t)u.h_col.p[R];
+    for (size_t c = 0; c < pass.size(); c++) { blen[c] = (uint32_t)u.h_col.p[c]; pass[c] = blen[c] <= mp_max; n_pass += pass[c]; }
+  }
+  // ---- product of the rows that are booked (unless a ratchet step has it), extraction
+  const bool compact = have_cut && !ratchet;
+  std::vector<uint32_t> sel_rows, home(1, 1u + 2u * nb), part((size_t)n_idx, 0xFFFFFFFFu), crow((size_t)n_idx, 0xFFFFFFFFu);
   for (uint32_t c = 0; c < 2 * nb; c++) {
-    u.cur_logl_now = -(int32_t)blen[c];
-    int64_t tree_index = ufb_book_tree(blen[c], pass[c] != 0, c, false, topology_key);
-    if (tree_index < 0) continue;
-    const uint32_t idx = 1u + c;
-    while (ep < events.size() && events[ep].idx < idx) ep++;
-    bool looked_up = false;
-    for (; ep < events.size() && events[ep].idx == idx; ep++) ufb_one_event(events[ep].b, events[ep].s, tree_index, looked_up, c, lookup_topology, dctx);
+    part[1 + c] = 0u;
+    if (!compact) crow[1 + c] = c;
+    else if (pass[c]) { crow[1 + c] = (uint32_t)sel_rows.size(); sel_rows.push_back(c); }
   }
-  // a tree a sample accepted is remembered as (this step's tree, swap) and materialised only if still referenced
-  for (const UfbState::Pending &pe : u.pending) {
-    if (u.refs[(size_t)pe.tree_index] <= 0 || u.store.count(pe.tree_index)) continue;
-    if (pe.cand == 0xFFFFFFFFu) u.store.emplace(pe.tree_index, back_);
-    else { swapped(pe.cand, bk); u.store.emplace(pe.tree_index, bk); }
-    u.stored++;
-  }
-  u.pending.clear();
+  if (compact) { cur_row = (uint32_t)sel_rows.size(); sel_rows.push_back(R); }
+  crow[1 + 2 * nb] = cur_row;
+  const int rows_p = compact ? round_up((int)sel_rows.size(), kUfbRowTile) : plane_rows_p;
+  std::vector<UfbEvent> events;
+  int rc = nni_extract_events(n_idx, home, part, crow, pass, compact ? &sel_rows : nullptr, rows_p, have_C, product, events);
+  if (rc) return rc;
+  if (!ratchet) u.rt_orig = (uint32_t)u.h_rt.p[oc];
+  float ms = 0.f;
+  if (timed && hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) u.gemm_ms += ms;
+  const double t1 = now_ms();
+  u.t_dev += t1 - t0;
+  // ---- host replay: the current tree (every sample from R_T), then the candidates
+  NniReplay replay(*this, mv);
+  replay.book_self(self_len, self_len <= mp_max);
+  replay.book_candidates(blen, pass, events);
   u.t_replay += now_ms() - t1;
   return MPF_OK;
 }
@@ -471,7 +656,7 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
 // IQTree::optimizeNNI under -bb (iqtree.cpp:2173-2302 with save_all_trees == 2)
 int Engine::ufboot_optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t *score, int32_t *nni_count, int32_t *nni_steps)
 {
-  if (sankoff_) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
+  if (sankoff_ && !(nni_weighted_ && nni_weighted_tracked_)) { set_error("NNI climb: Fitch engines only (the -cost climb is not served)"); return MPF_E_UNSUPPORTED; }
   if (!ufb_) { set_error("no UFBoot tracker attached"); return MPF_E_STATE; }
   if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
   const UfbState &u = *ufb_;
