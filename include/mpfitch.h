@@ -295,6 +295,45 @@ int mpf_nni_pattern_lengths(mpf_engine *e, int32_t root_taxon, int32_t cap, int3
    rollback (iqtree.cpp:2271-2272) included: the neighbours in slot1[i] of node1[i] and slot2[i] of node2[i] traded places.
    Replaying them on the start tree gives the final tree.  *n is always set; the arrays are filled up to cap entries. */
 int mpf_get_nni_moves(const mpf_engine *e, int32_t cap, int32_t *node1, int32_t *slot1, int32_t *node2, int32_t *slot2, int32_t *n);
+
+/* ---- parsimony branch lengths: PhyloTree::fixNegativeBranch (phylotree.cpp:3597-3633), which an MP run calls on the first start
+   tree (phyloanalysis.cpp:1180; :1153 for the IQ-TREE start tree), on each further initial candidate (:1336), on the consensus tree
+   (:2280) and under -parsbran (:1501).  It calls computeParsimonyBranch(.., &branch_subst) once per branch; here every branch of
+   the current (complete, bifurcating) tree is scored by ONE launch on the directional vectors the engine keeps (k_branch_subst /
+   k_snk_branch_eval), after a refresh of whatever is stale.
+
+   Branch order: fixNegativeBranch(force, node = root, dad = NULL) is a pre-order walk from the root leaf root_taxon that takes
+   the neighbours other than dad in neighbors[] slot order; each branch is met once, from its root side.  That is the order of
+   mpf_nni_scores with the pendant branches included: 2 n_taxa - 3 entries, node1[i] the end nearer the root leaf, node2[i] the
+   other end (node numbers).
+
+   subst[i] is what the reference's computeParsimonyBranch stores in *branch_subst at that call:
+     - Fitch engine (PhyloTree::computeParsimonyBranch, phylotree.cpp:938-1047): the sum over patterns of frequency x [the state
+       sets of the two sides have no state in common], taken before the two subtree scores are added (:1041-1044); the leaf swap
+       (:945-953) does not change it.  The sum runs over the patterns the engine KEEPS under the weights in force (after
+       mpf_set_weights: the new ones).  An engine made with keep_all_sites = 1 counts uninformative patterns too, as IQ-TREE
+       does; an engine that drops uninformative patterns counts the kept ones only -- a dropped pattern with k > 1 singleton
+       states puts its changes on pendant branches in IQ-TREE's count and on none here;
+     - weighted engine (ParsTree::computeParsimonyBranch, parstree.cpp:439-541): *branch_subst = tree_pars (:534-535), the FULL
+       weighted length of the tree rooted at that branch, not a per-branch count:
+         sum_ptn w * min_i( min_j( node_branch[j] + cost[i][j] ) + dad_branch[i] )
+       For an inner node2[i], dad_branch is the subtree at node2 (enters as it is) and node_branch the rest of the tree (the
+       transformed side); for a leaf node2[i] the swap at :449-457 makes the leaf the transformed side.  With a symmetric matrix
+       every branch gives the one tree length; with a non-symmetric one the branches differ.
+   *n = 2 n_taxa - 3, always set; the arrays are filled when cap >= *n (the sizing protocol of mpf_nni_scores).
+   MPF_E_STATE without a tree or on a partial tree (a stepwise addition under way); an attached UFBoot tracker does not matter --
+   nothing is booked, no topology changes.  Options: "brlen_tile" (-1 | 0 | 1 | 2 | 4, the kernel shape, as "nni_tile"), read-only
+   "brlen_launches", and under "timing" read-only "brlen_kernel_ns" (HIP-event time of the kernel). */
+int mpf_branch_substitutions(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *subst,
+                             int32_t *n);
+/* the lengths fixNegativeBranch(force = true) gives those branches (phylotree.cpp:3608-3614), in double precision on the host, with
+   N = n_sites (the caller's getAlnNSite()) and S the alignment's number of states:
+     bl = subst > 0 ? subst / N : 1 / N;  z = S / (S - 1);  x = 1 - z bl;  if (x > 0) bl = -log(x) / z;  if (bl < 1e-6) bl = 1e-6
+   (MIN_BRANCH_LEN, phylotree.h:35).  unit_cost_parstree != 0 on a Fitch engine: the tree is a ParsTree under -cost fitch | e, which
+   scores on the Fitch engine but takes ParsTree's rule -- every branch's subst is the tree's Fitch length.  Ignored on a weighted
+   engine.  Same order, sizing protocol and errors as mpf_branch_substitutions. */
+int mpf_branch_lengths(mpf_engine *e, int32_t root_taxon, int32_t n_sites, int32_t unit_cost_parstree, int32_t cap, int32_t *node1,
+                       int32_t *node2, double *length /* [cap] */, int32_t *n);
 /* The same climb under -bb (save_all_trees == 2), with the UFBoot tracker of mpf_ufboot_attach booking every tree the climb looks
    at through IQTree::saveCurrentTree, in the reference's order: at the start of every step that is not a rollback step the current
    tree with curScore (iqtree.cpp:2181-2183), then for every branch the step evaluates, in evaluation order, the tree after move 0

@@ -77,3 +77,26 @@ void mpfitch_phylotree_install_nni(const mpf_phylotree_nni_hooks *hooks);
 // marshals it, climbed by mpf_optimize_nni from the root leaf (hook root_id, else taxon 0) and the engine's swaps are replayed on
 // the host's tree through the swap hook.  Returns the final length (curScore = -length).
 int mpfitch_optimize_nni(PhyloTree *t, int *nni_count, int *nni_steps);
+
+// ---- parsimony branch lengths (PhyloTree::fixNegativeBranch, phylotree.cpp:3597-3633; INTEGRATION.md "Branch lengths").  A third
+// table of its own, so that the two above and their users stay as they are.
+//     static int    hk_nsites(const PhyloTree *t) { return ((PhyloTree *)t)->getAlnNSite(); }
+//     static double hk_getlen(const PhyloTree *t, int id1, int id2) { return node_of(t, id1)->findNeighbor(node_of(t, id2))->length; }
+//     static void   hk_setlen(PhyloTree *t, int id1, int id2, double len)
+//         { Node *a = node_of(t, id1), *b = node_of(t, id2); a->findNeighbor(b)->length = len; b->findNeighbor(a)->length = len; }
+//     static int    hk_parstree(const PhyloTree *t) { return dynamic_cast<const ParsTree *>(t) != NULL; }
+//     ... mpfitch_phylotree_install_brlen(&brlen_hooks);
+struct mpf_phylotree_brlen_hooks {
+  int (*n_sites)(const PhyloTree *);                               // getAlnNSite()
+  double (*get_length)(const PhyloTree *, int id1, int id2);       // the length on the neighbour of id1 that points to id2
+  void (*set_length)(PhyloTree *, int id1, int id2, double len);   // BOTH directions of the branch (phylotree.cpp:3619, :3623)
+  // optional (may be NULL = "a tree with a cost matrix"): the tree is a ParsTree, whose computeParsimonyBranch hands back the
+  // tree's length as branch_subst (parstree.cpp:534-535) -- under -cost fitch | e too, where the scoring runs on the Fitch engine
+  int (*is_parstree)(const PhyloTree *);
+};
+void mpfitch_phylotree_install_brlen(const mpf_phylotree_brlen_hooks *hooks);
+// PhyloTree::fixNegativeBranch(force) from the root on the engine: the tree is marshalled as computeParsimony() marshals it (the
+// cached engine is reused), every branch's length comes from ONE mpf_branch_lengths call (walk from the root leaf: hook root_id,
+// else taxon 0) and is written through set_length.  force == 0: only branches whose current length is negative are rewritten;
+// then any length <= 0 becomes 1e-6 (:3626-3629).  Returns the number of rewritten branches.  Bifurcating trees only.
+int mpfitch_fix_negative_branch(PhyloTree *t, int force);

@@ -194,6 +194,57 @@ int mpfitch_optimize_nni(PhyloTree *t, int *nni_count, int *nni_steps)
   return (int)score;
 }
 
+static mpf_phylotree_brlen_hooks g_brlen;
+static bool g_brlen_installed = false;
+
+void mpfitch_phylotree_install_brlen(const mpf_phylotree_brlen_hooks *hooks)
+{
+  g_brlen = *hooks;
+  g_brlen_installed = hooks->n_sites && hooks->get_length && hooks->set_length;
+}
+
+// int PhyloTree::fixNegativeBranch(bool force, Node *node = NULL, Node *dad = NULL) (phylotree.cpp:3597-3633) called from the root
+// -- _ZN9PhyloTree17fixNegativeBranchEbP4NodeS1_ in a mpboot build; served: phyloanalysis.cpp:1153, :1180, :1336, :1501.  The
+// consensus tree (:2280) may be multifurcating: marshal_tree refuses it, the host keeps its own code for that call.
+int mpfitch_fix_negative_branch(PhyloTree *t, int force)
+{
+  if (!g_brlen_installed) { std::fprintf(stderr, "mpfitch phylotree shim: mpfitch_phylotree_install_brlen() was not called\n"); std::exit(EXIT_FAILURE); }
+  const unsigned int *cost = g_h.cost_matrix ? g_h.cost_matrix(t) : nullptr;
+  // ParsTree's rule (branch_subst = the tree's length) hangs on the class, not on the matrix; unit costs score on the Fitch engine
+  const int parstree = g_brlen.is_parstree ? (g_brlen.is_parstree(t) ? 1 : 0) : (cost ? 1 : 0);
+  if (cost) {
+    const int S = g_h.is_protein(t) ? 20 : 4;
+    bool unit = true;
+    for (int i = 0; i < S && unit; i++)
+      for (int j = 0; j < S; j++)
+        if (cost[i * S + j] != (i == j ? 0u : 1u)) { unit = false; break; }
+    if (unit) cost = nullptr;
+  }
+  mpf_engine *e = engine_for(t, cost);
+  const int n = g_h.n_taxa(t);
+  std::vector<int32_t> back;
+  marshal_tree(t, n, back);
+  if (mpf_set_tree(e, back.data())) die("mpf_set_tree");
+  const int root = g_h.root_id ? g_h.root_id(t) : 0;
+  if (root < 0 || root >= n) { std::fprintf(stderr, "mpfitch phylotree shim: root %d is not a leaf id\n", root); std::exit(EXIT_FAILURE); }
+  int32_t m = 2 * n - 3, k = 0;
+  std::vector<int32_t> n1((size_t)m), n2((size_t)m);
+  std::vector<double> len((size_t)m);
+  if (mpf_branch_lengths(e, root + 1, g_brlen.n_sites(t), parstree, m, n1.data(), n2.data(), len.data(), &k) || k != m) die("mpf_branch_lengths");
+  int fixed = 0;
+  for (int i = 0; i < m; i++) {
+    const int a = n1[(size_t)i] - 1, b = n2[(size_t)i] - 1;         // node number = id + 1
+    double cur = g_brlen.get_length(t, a, b);
+    if (cur < 0.0 || force) {
+      cur = len[(size_t)i];
+      g_brlen.set_length(t, a, b, cur);
+      fixed++;
+    }
+    if (cur <= 0.0) g_brlen.set_length(t, a, b, 1e-6);              // MIN_BRANCH_LEN (:3626-3629)
+  }
+  return fixed;
+}
+
 void mpfitch_phylotree_install(const mpf_phylotree_hooks *hooks)
 {
   g_h = *hooks;

@@ -311,6 +311,63 @@ int mpf_nni_scores(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node
   return MPF_OK;
 }
 
+// PhyloTree::fixNegativeBranch's branch_subst for every branch of the current tree (host/brlen.cpp)
+int mpf_branch_substitutions(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *subst, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> s;
+  const int rc = e->eng.branch_substitutions(root_taxon, br, s);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !subst)) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    subst[i] = s[i];
+  }
+  return MPF_OK;
+}
+
+// ... and the lengths fixNegativeBranch(force = true) makes of them (phylotree.cpp:3608-3614), in double precision on the host
+int mpf_branch_lengths(mpf_engine *e, int32_t root_taxon, int32_t n_sites, int32_t unit_cost_parstree, int32_t cap, int32_t *node1,
+                       int32_t *node2, double *length, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  if (n_sites < 1) { set_error("mpf_branch_lengths: n_sites must be positive"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> s;
+  int rc = e->eng.branch_substitutions(root_taxon, br, s);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !length)) { set_error("null output"); return MPF_E_INVALID; }
+  if (unit_cost_parstree && !e->eng.weighted()) {
+    // a ParsTree under -cost fitch | e runs on the Fitch engine, but its computeParsimonyBranch is the override that hands back
+    // tree_pars (parstree.cpp:534-535): every branch takes the length of the tree
+    uint32_t len = 0;
+    rc = e->eng.tree_length(&len);
+    if (rc) return rc;
+    std::fill(s.begin(), s.end(), len);
+  }
+  const int S = e->eng.S();
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    const int branch_subst = (int)s[i];
+    double branch_length = (branch_subst > 0) ? ((double)branch_subst / n_sites) : (1.0 / n_sites);
+    const double z = (double)S / (S - 1);
+    const double x = 1.0 - (z * branch_length);
+    if (x > 0) branch_length = -std::log(x) / z;
+    if (branch_length < 1e-6) branch_length = 1e-6;      // MIN_BRANCH_LEN (phylotree.h:35)
+    length[i] = branch_length;
+  }
+  return MPF_OK;
+}
+
 // mpf_nni_scores by the mask-writing kernel of the tracked climb, its rows per pattern
 int mpf_nni_pattern_terms(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len, uint8_t *terms, int32_t *n)
 {

@@ -2110,8 +2110,10 @@ int Engine::set_option(const std::string &key, int64_t v)
   }
   if (key == "grow_device") { grow_device_ = v ? 1 : 0; return MPF_OK; }
   if (key == "grow_tile") { if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8 && v != -1) { set_error("grow_tile: 0 (word-major copy where there is one, else fitted), -1 (fitted quad tiles), 1, 2, 4 or 8"); return MPF_E_INVALID; } grow_vw_ = (int)v; return MPF_OK; }
+  if (key == "grow_max_tips") { grow_max_tips_ = v < 0 ? 0 : (int)std::min<int64_t>(v, 1 << 30); return MPF_OK; }
   if (key == "grow_fault") { grow_fault_ = v; return MPF_OK; }
   if (key == "nni_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("nni_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } nni_vw_ = (int)v; return MPF_OK; }
+  if (key == "brlen_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("brlen_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } brlen_vw_ = (int)v; return MPF_OK; }
   if (key == "nni_weighted") { nni_weighted_ = v ? 1 : 0; return MPF_OK; }     // the -cost NNI climb (host/nni.cpp); no effect on a Fitch engine
   if (key == "nni_weighted_tracked") { nni_weighted_tracked_ = v ? 1 : 0; return MPF_OK; }   // ... under -bb; no effect on a Fitch engine
   if (key == "max_visits") { max_visits_ = std::max<int64_t>(0, v); return MPF_OK; }
@@ -2220,6 +2222,9 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "nni_weighted_tracked") *v = nni_weighted_tracked_;
   else if (key == "nni_kept_worse") *v = (int64_t)nni_kept_worse_;
   else if (key == "nni_kernel_ns") *v = (int64_t)nni_kernel_ns_;
+  else if (key == "brlen_tile") *v = brlen_vw_;
+  else if (key == "brlen_launches") *v = (int64_t)brlen_launches_;
+  else if (key == "brlen_kernel_ns") *v = (int64_t)brlen_kernel_ns_;
   else if (key == "nni_booked") *v = ufb_ ? (int64_t)ufb_->nni_booked : 0;
   else if (key == "grow_steps") *v = (int64_t)grow_steps_;
   else if (key == "grow_us") *v = (int64_t)(grow_ms_total_ * 1000.0);

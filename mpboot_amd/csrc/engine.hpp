@@ -332,6 +332,14 @@ class Engine {
   // tree at the start of every scoring step, iqtree.cpp:2181-2183, and both NNIs of every evaluated branch, phylotree.cpp:3937)
   int ufboot_optimize_nni(int root_taxon, bool speednni, int max_steps, uint32_t *score, int32_t *nni_count, int32_t *nni_steps);
 
+  // ---- parsimony branch lengths (host/brlen.cpp; reference PhyloTree::fixNegativeBranch, phylotree.cpp:3597-3633): br[i] = branch i
+  // of the pre-order walk from the leaf root_taxon, node1 the end nearer that leaf; subst[i] = what computeParsimonyBranch hands
+  // back as branch_subst there (Fitch engine: the weighted count of patterns whose two sides share no state; weighted engine: the
+  // full length of the tree rooted at the branch).  One launch for all 2n - 3 branches; books nothing, changes no topology
+  int branch_substitutions(int root_taxon, std::vector<NniBranch> &br, std::vector<uint32_t> &subst);
+  void branch_order(int root_taxon, std::vector<NniBranch> &br) const;
+  bool weighted() const { return sankoff_; }     // made with a cost matrix (mpf_engine_create_sankoff)
+
   // ---- online UFBoot-MP bookkeeping (host/ufboot.cpp; reference IQTree::saveCurrentTree, iqtree.cpp:3271-3785)
   int ufboot_attach(int n_samples, const uint16_t *samples, double epsilon, int n_local = -1, const int32_t *sample_ids = nullptr,
                     mpf_ufb_exchange_fn exchange = nullptr, void *exchange_arg = nullptr);
@@ -514,6 +522,15 @@ class Engine {
   PinBuf<NniDesc> h_nni_desc_;
   PinBuf<unsigned long long> h_nni_out_;
 
+  // parsimony branch lengths: the kernel shape (option "brlen_tile", as nni_tile), the counters behind the read-only options
+  // brlen_launches / brlen_kernel_ns (the latter under the option "timing")
+  int brlen_vw_ = -1;
+  uint64_t brlen_launches_ = 0, brlen_kernel_ns_ = 0;
+  DevBuf<BranchDesc> d_br_desc_;
+  PinBuf<BranchDesc> h_br_desc_;
+  DevBuf<uint32_t> d_br_out_;
+  PinBuf<uint32_t> h_br_out_;
+
   int addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *insert_per_step);
   void apply_move(int remove_rec, int insert_rec);
 
@@ -571,6 +588,7 @@ private:
   } gd_;
   int grow_device_ = 1;                          // option "grow_device": 0 = the host's loop (one refresh + one scan + one round trip per taxon)
   int grow_vw_ = -1;                             // option "grow_tile": words per lane group of k_grow's quad tiles (-1 = fitted: at most 32 workgroups; 0 = the word-major DNA layout)
+  int grow_max_tips_ = 0;                        // option "grow_max_tips" (tests): the host's addition loop stops at this many tips -- the tree stays partial (0 = no limit)
   int64_t grow_fault_ = 0;                       // tests: fault injected into the next k_grow launch
   uint64_t grow_launches_ = 0, grow_steps_ = 0;
   double grow_ms_total_ = 0;

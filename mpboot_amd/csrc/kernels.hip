@@ -981,6 +981,43 @@ __global__ __launch_bounds__(256) void k_nni_eval(const uint32_t *__restrict__ v
     __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---------------------------------------------------------------- parsimony branch lengths (PhyloTree::fixNegativeBranch, host/brlen.cpp)
+//
+// branch_subst of PhyloTree::computeParsimonyBranch (reference phylotree.cpp:938-1047) for every branch of the tree at once: the
+// number of sites at which the two sides of branch i (the directional vectors desc[i].a and desc[i].b, a tip's own vector for a
+// pendant branch) have no state in common -- k_evaluate's count, so a pattern weighs what the packing in force gives it.  A wave
+// per (branch, tile): two vector loads, out[i] (zeroed by the caller) takes one atomic add per (branch, tile).  Addresses are
+// 64-bit throughout (a store of 2 GiB and more, Geometry::big, takes the same code).
+// WM: `vec` is the word-major copy (Geometry::shoff), one 16-byte load per lane and vector (DNA, one word per lane).
+template <int S, int VW, int RED, bool WM>
+__global__ __launch_bounds__(256) void k_branch_subst(const uint32_t *__restrict__ vec, const BranchDesc *__restrict__ desc,
+                                                      int n_br, uint32_t *__restrict__ out, int Wp, int tiles)
+{
+  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
+  const int lane = threadIdx.x & 63;
+  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  gw = __builtin_amdgcn_readfirstlane(gw);
+  if (gw >= n_br * tiles) return;
+  const int br = gw / tiles, tile = gw - br * tiles;
+  const BranchDesc d = desc[br];
+  bool valid;
+  const int w0 = lane_word<VW>(tile, lane, Wp, valid);
+  Tile<S, VW> a, b;
+  if constexpr (WM) {
+    auto ld = [&](Tile<S, VW> &t, uint32_t cid) {
+      const uint4 x = *reinterpret_cast<const uint4 *>(vec + (size_t)cid * (size_t)(4 * Wp) + (size_t)w0 * 4);
+      t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
+    };
+    ld(a, d.a); ld(b, d.b);
+  } else {
+    load_tile<S, VW>(a, vec, d.a, Wp, w0);
+    load_tile<S, VW>(b, vec, d.b, Wp, w0);
+  }
+  const uint32_t cost = empty_count<S, VW>(a, b);
+  const uint32_t tot = wave_total<RED>(valid ? cost : 0u);
+  if (lane == 0 && tot) atomic_add_u32(out + br, tot);
+}
+
 // c = fitch(a, b), m = the "no common state" words of the join; returns their popcount
 template <int S, int VW>
 __device__ __forceinline__ uint32_t fitch_mask(Tile<S, VW> &c, const Tile<S, VW> &a, const Tile<S, VW> &b, uint32_t (&m)[VW])
@@ -2285,6 +2322,50 @@ __global__ __launch_bounds__(256) void k_snk_nni_eval_vals(const uint32_t *__res
   snk_nni_eval_body<S, PK, BUF, true>(vec, moff, desc, n_br, cost, pwgt, out, We, tiles, vals, npat, vmax);
 }
 
+// Parsimony branch lengths on the weighted engine (PhyloTree::fixNegativeBranch on a ParsTree; host/brlen.cpp).  What
+// ParsTree::computeParsimonyBranch hands back as branch_subst is tree_pars (reference parstree.cpp:534-535): the full weighted
+// length of the tree rooted at the branch,
+//   out[i] = sum_ptn w * min_x( vec[desc[i].a][x] + m(vec[desc[i].b])[x] )
+// desc[i].a the side that enters as it is (dad_branch, the rows of the matrix), desc[i].b the transformed side (node_branch) --
+// k_snk_evaluate's join with one output per branch.  The stored transforms have the viewer as the parent, which is the
+// orientation of min_j(node_branch[j] + cost[i][j]) (see k_snk_nni_eval), so nothing is transformed here: two vector loads, S
+// add / min pairs, one atomic per (branch, tile).  16-bit form: a sum of a view and a transform of the two sides of ONE branch
+// -- all n tips between them -- is among the values k_snk_nni_eval forms: no further condition on the costs.
+// BUF: each half of the store behind one raw buffer (32-bit offsets); otherwise 64-bit pointers per row.
+template <int S, bool PK, bool BUF>
+__global__ __launch_bounds__(256) void k_snk_branch_eval(const uint32_t *__restrict__ vec, size_t moff, const BranchDesc *__restrict__ desc,
+                                                         int n_br, const uint32_t *__restrict__ pwgt, uint32_t *__restrict__ out,
+                                                         int We, int tiles)
+{
+  typedef SnkT<PK> T;
+  const int lane = threadIdx.x & 63;
+  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  gw = __builtin_amdgcn_readfirstlane(gw);
+  if (gw >= n_br * tiles) return;
+  const int br = gw / tiles, tile = gw - br * tiles;
+  const BranchDesc d = desc[br];
+  bool valid;
+  const int e0 = lane_word<1>(tile, lane, We, valid);
+  const uint32_t *mvec = vec + moff;
+  const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc((void *)vec, 0, -1, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void *)mvec, 0, -1, 0x00020000);
+  const uint32_t row_bytes = (uint32_t)We * 4u, voff = (uint32_t)e0 * 4u;
+  Costs<S, PK> a, mb;
+  if constexpr (BUF) {
+    load_costs_b<S, PK>(a, rs_v, d.a, row_bytes, voff);
+    load_costs_b<S, PK>(mb, rs_m, d.b, row_bytes, voff);
+  } else {
+    load_costs<S, PK>(a, vec, d.a, We, e0);
+    load_costs<S, PK>(mb, mvec, d.b, We, e0);
+  }
+  typename T::E best = T::inf();
+#pragma unroll
+  for (int x = 0; x < S; x++) best = T::mn(best, T::add(a.v[x], mb.v[x]));
+  const uint32_t c = valid ? T::wsum(best, pwgt, e0) : 0u;
+  const uint32_t tot = wave_total<0>(c);
+  if (lane == 0 && tot) atomic_add_u32(out + br, tot);
+}
+
 // SPR / stepwise scan over a host-planned program (same ops as k_scan).  With m() the min-plus transform:
 //   CHAIN : U[d] = m(U[d-1]) + m(vec[sib]);  test: out += sum_ptn w * min_s(m(U[d])[s] + m(vec[own])[s] + m(S)[s])
 //   JOIN  : out += sum_ptn w * min_s(m(vec[own])[s] + m(vec[sib])[s] + m(S)[s])
@@ -2804,6 +2885,47 @@ hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t
                            (uint32_t)g.Wp, vmax);
       else
         hipLaunchKernelGGL((k_snk_nni_eval<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles);
+    });
+  });
+  return hipGetLastError();
+}
+
+// the shapes of launch_nni_eval (k_branch_subst)
+hipError_t launch_branch_subst(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
+                               uint32_t *out, int vw, bool word_major)
+{
+  if (n_br <= 0) return hipSuccess;
+  if (g.sankoff) return hipErrorInvalidValue;
+  const bool wm = word_major && g.S == 4 && g.shoff;
+  if (g.S != 4 || wm) vw = 1;
+  if (vw != 1 && vw != 2 && vw != 4) return hipErrorInvalidValue;
+  if (g.Wp % vw) return hipErrorInvalidValue;
+  const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
+  const long waves = (long)n_br * tiles;
+  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  auto launch = [&](auto S, auto VW, auto WM) {
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_branch_subst<S, VW, RED, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, desc, n_br, out, g.Wp, tiles);
+    });
+  };
+  if (wm) launch(int_c<4>(), int_c<1>(), bool_c<true>());
+  else if (g.S == 4 && vw == 2) launch(int_c<4>(), int_c<2>(), bool_c<false>());
+  else if (g.S == 4 && vw == 4) launch(int_c<4>(), int_c<4>(), bool_c<false>());
+  else dispatch_states(g.S, [&](auto S) { launch(S, int_c<1>(), bool_c<false>()); });
+  return hipGetLastError();
+}
+
+hipError_t launch_snk_branch_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
+                                  uint32_t *out, bool wide_addr)
+{
+  if (n_br <= 0) return hipSuccess;
+  if (!g.sankoff || !g.moff) return hipErrorInvalidValue;
+  const int We = snk_elems(g), tiles = (We + 63) / 64;
+  dim3 grid((unsigned)(((long)n_br * tiles + 3) / 4)), block(256);
+  const bool buf_ok = !wide_addr && (unsigned long long)g.moff * 4ull < (1ull << 32);      // each half behind one 32-bit-offset descriptor
+  dispatch_snk(g, [&](auto S, auto PK) {
+    dispatch_bool(buf_ok, [&](auto BUF) {
+      hipLaunchKernelGGL((k_snk_branch_eval<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.pwgt, out, We, tiles);
     });
   });
   return hipGetLastError();

@@ -215,6 +215,17 @@ hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32
 // lengths of the trees after move 0 / move 1 of branch i, 16 bits each, laid out as launch_scan's vals rows; *vmax the largest of them
 hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
                                unsigned long long *out, bool wide_addr = false, uint16_t *vals = nullptr, uint32_t *vmax = nullptr);
+// Parsimony branch lengths: every branch of the tree in one launch (cids of the two directional vectors of the branch; a tip's own
+// vector at a pendant branch).  out[i] (zeroed by the caller) = number of sites whose two state sets have nothing in common
+// (k_branch_subst; vw / word_major as launch_nni_eval)
+struct BranchDesc { uint32_t a, b; };
+hipError_t launch_branch_subst(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
+                               uint32_t *out, int vw, bool word_major);
+// ... on the weighted engine (k_snk_branch_eval): out[i] = the FULL weighted length of the tree rooted at branch i, a = the side
+// that enters as it is (the parent side, the rows of the matrix), b = the side whose stored transform is read
+// (ParsTree::computeParsimonyBranch's dad_branch / node_branch).  wide_addr as launch_snk_nni_eval
+hipError_t launch_snk_branch_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
+                                  uint32_t *out, bool wide_addr = false);
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,
                        const ScanOp *ops, uint32_t *out, int max_depth,
                        uint32_t *host_out = nullptr, uint32_t n_out = 0, uint32_t *done = nullptr,   // as launch_scan_walk

@@ -35,6 +35,7 @@ EXPORTS = [
     "mpf_cost_matrix_load", "mpf_cost_matrix_triangle_fix",
     "mpf_iq_random_nnis", "mpf_iq_perturb_weights", "mpf_iq_topology_key", "mpf_ufboot_adopt", "mpf_optimize_spr_many", "mpf_optimize_spr_many_round",
     "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves", "mpf_ufboot_optimize_nni", "mpf_nni_pattern_terms", "mpf_nni_pattern_lengths",
+    "mpf_branch_substitutions", "mpf_branch_lengths",
 ]
 
 
@@ -171,6 +172,8 @@ def load_library():
         L.mpf_ufboot_optimize_nni.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
         L.mpf_nni_pattern_terms.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_nni_pattern_lengths.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+        L.mpf_branch_substitutions.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.mpf_branch_lengths.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -586,6 +589,35 @@ class FitchEngine:
         ln = np.zeros(2 * max(m, 1), dtype=np.uint32)
         _chk(L.mpf_nni_scores(self.h, root_taxon, m, _p(a), _p(b), _p(ln), C.byref(n)))
         return a[:m].copy(), b[:m].copy(), ln[:2 * m].reshape(m, 2).copy()
+
+    # ---- parsimony branch lengths (PhyloTree::fixNegativeBranch)
+    def branch_substitutions(self, root_taxon: int = 1):
+        """(node1[m], node2[m], subst[m]) for the m = 2 n - 3 branches of the current tree in fixNegativeBranch's order (pre-order
+        from the leaf root_taxon, neighbours in slot order, node1 the end nearer that leaf): what computeParsimonyBranch hands back
+        as branch_subst -- on a Fitch engine the weighted count of kept patterns whose two sides share no state, on a weighted
+        engine (cost=...) the full length of the tree rooted at the branch (ParsTree's rule).  One kernel launch for all branches."""
+        m = 2 * self.n - 3
+        n = C.c_int32()
+        a = np.zeros(m, dtype=np.int32)
+        b = np.zeros(m, dtype=np.int32)
+        s = np.zeros(m, dtype=np.uint32)
+        _chk(load_library().mpf_branch_substitutions(self.h, root_taxon, m, _p(a), _p(b), _p(s), C.byref(n)))
+        assert n.value == m
+        return a, b, s
+
+    def branch_lengths(self, n_sites: int, root_taxon: int = 1, unit_cost_parstree: bool = False):
+        """(node1[m], node2[m], length[m] float64): the lengths fixNegativeBranch(force=True) gives the branches, from
+        branch_substitutions, n_sites (the alignment's site count) and the number of states; unit_cost_parstree: a ParsTree under
+        -cost fitch | e -- every branch takes the tree's Fitch length as its count (no effect on a weighted engine)"""
+        m = 2 * self.n - 3
+        n = C.c_int32()
+        a = np.zeros(m, dtype=np.int32)
+        b = np.zeros(m, dtype=np.int32)
+        ln = np.zeros(m, dtype=np.float64)
+        _chk(load_library().mpf_branch_lengths(self.h, root_taxon, int(n_sites), int(bool(unit_cost_parstree)), m, _p(a), _p(b), _p(ln),
+                                               C.byref(n)))
+        assert n.value == m
+        return a, b, ln
 
     def nni_pattern_terms(self, root_taxon: int = 1):
         """nni_scores by the mask-writing kernel of the tracked climb: (node1[m], node2[m], len[m][2], terms[m][3][n_patterns]);

@@ -290,13 +290,14 @@ int Engine::addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *inser
     if (rc) return rc;
   }
   // the whole loop below as ONE persistent kernel (k_grow, csrc/grow.hip) where it applies: same insertions, same draws
-  if (grow_device_ && !rand_fn_ && !sankoff_ && grow_supported(g_, n_)) {
+  if (grow_device_ && !grow_max_tips_ && !rand_fn_ && !sankoff_ && grow_supported(g_, n_)) {
     bool done = false;
     int rc = grow_segment(perm, len, best_per_step, insert_per_step, &done);
     if (rc) return rc;
     if (done) return MPF_OK;
   }
-  while (ntips_ < n) {
+  const int stop = grow_max_tips_ > 0 ? std::min(n, std::max(3, grow_max_tips_)) : n;      // (test aid: a tree left partial)
+  while (ntips_ < stop) {
     best_ = (uint32_t)INT_MAX;
     const int nextsp = ++ntips_;
     const int p = nodep_[perm[nextsp]];
