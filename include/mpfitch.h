@@ -334,6 +334,44 @@ int mpf_branch_substitutions(mpf_engine *e, int32_t root_taxon, int32_t cap, int
    engine.  Same order, sizing protocol and errors as mpf_branch_substitutions. */
 int mpf_branch_lengths(mpf_engine *e, int32_t root_taxon, int32_t n_sites, int32_t unit_cost_parstree, int32_t cap, int32_t *node1,
                        int32_t *node2, double *length /* [cap] */, int32_t *n);
+/* Multifurcating trees.  Every -bb run of the reference ends on one: computeConsensusTree writes the bootstrap consensus, the host
+   reads it back, calls fixNegativeBranch(true) and optimizeAllBranches() -- in MP mode computeParsimony() -- and prints "Parsimony
+   score of consensus tree" (phyloanalysis.cpp:2263-2307); user trees with polytomies reach -comppars, -wspars-user-tree and
+   -parsbran alike.  back[] (three records per inner node) cannot hold such a tree, so it is handed over as CSR neighbour lists:
+   tips are nodes 1 .. n_taxa, inner node i (0-based) is node n_taxa + 1 + i, its neighbours are nbr[first[i] .. first[i + 1]) in
+   the host's neighbors[] order, entries are node numbers; 1 <= n_inner <= n_taxa - 2.  MPF_E_INVALID with a message unless every
+   inner degree is at least 3, adjacency is symmetric, every tip occurs exactly once, there are n_taxa + n_inner - 1 edges and the
+   tree is connected.
+
+   The rules at a node of degree > 3 are the reference's generic ones, not the bifurcating rule on some binary resolution:
+     - Fitch engine (PhyloTree::computePartialParsimony, phylotree.cpp:869-931; the DNA and protein fast paths take degree 3 only,
+       :708, :781): a node's set is the AND of all its children's sets; where that is empty it is the OR of all of them and ONE
+       step is counted, whatever the degree.  This is not the length of a hard polytomy (it undercounts), and it depends on the
+       root leaf; it is what the reference prints.  The reference's is_const skip (:845, :900) is not applied: see INTEGRATION;
+     - weighted engine (ParsTree::computePartialParsimony, parstree.cpp:191-214): a node's cost row is the sum over all children
+       of the child's min-plus transform.
+   A tree whose inner nodes all have degree 3 gives, bit for bit, what mpf_compute_parsimony_at / mpf_branch_substitutions /
+   mpf_branch_lengths give for the same tree.  The calls are stateless towards the engine's own tree: mpf_get_tree, mpf_score_tree
+   and mpf_branch_substitutions give afterwards what they gave before (the engine's vectors are made again on the next call that
+   needs them), and an attached UFBoot tracker books nothing.  No current tree is needed.
+
+   mpf_polytomy_parsimony: computeParsimony() at the root leaf, computeParsimonyBranch(root->neighbors[0], root)
+   (phylotree.cpp:1049-1061, :938-1047; parstree.cpp:439-541): the length, and _pattern_pars with 0 for dropped patterns as
+   mpf_compute_parsimony_at returns them.  On a weighted engine with a non-symmetric matrix the orientation is the one
+   mpf_compute_parsimony_at documents (the rest of the tree as the parent side). */
+int mpf_polytomy_parsimony(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, uint32_t *score,
+                           uint16_t *pattern_pars /* [P] or NULL */);
+/* fixNegativeBranch (phylotree.cpp:3597-3633) on such a tree: the contract of mpf_branch_substitutions and mpf_branch_lengths -- the
+   walk (pre-order from the root leaf, neighbours in list order, node1 the root side), the meaning of subst on each engine, the leaf
+   swap, the sizing protocol, the length formula and unit_cost_parstree -- with *n = n_taxa + n_inner - 1 and the two sides of a
+   branch made by the k-ary rule above (all directed views of the tree: ONE launch of k_poly_views / k_poly_snk_views, then the one
+   branch launch).  Options: "poly_tile" (0 | 4 | 8 | 16 | 32, words of a row per workgroup), read-only "poly_launches" and
+   "poly_views", and under "timing" read-only "poly_view_ns" / "poly_branch_ns"; read-only "sankoff_packed" (weighted engine: 1 while
+   the store holds two 16-bit costs per word, i.e. "sankoff_short" is on and 3 n_taxa (max cost + 1) < 2^16). */
+int mpf_polytomy_branch_substitutions(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t cap,
+                                      int32_t *node1, int32_t *node2, uint32_t *subst, int32_t *n);
+int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_sites,
+                                int32_t unit_cost_parstree, int32_t cap, int32_t *node1, int32_t *node2, double *length /* [cap] */, int32_t *n);
 /* The same climb under -bb (save_all_trees == 2), with the UFBoot tracker of mpf_ufboot_attach booking every tree the climb looks
    at through IQTree::saveCurrentTree, in the reference's order: at the start of every step that is not a rollback step the current
    tree with curScore (iqtree.cpp:2181-2183), then for every branch the step evaluates, in evaluation order, the tree after move 0

@@ -98,5 +98,23 @@ void mpfitch_phylotree_install_brlen(const mpf_phylotree_brlen_hooks *hooks);
 // PhyloTree::fixNegativeBranch(force) from the root on the engine: the tree is marshalled as computeParsimony() marshals it (the
 // cached engine is reused), every branch's length comes from ONE mpf_branch_lengths call (walk from the root leaf: hook root_id,
 // else taxon 0) and is written through set_length.  force == 0: only branches whose current length is negative are rewritten;
-// then any length <= 0 becomes 1e-6 (:3626-3629).  Returns the number of rewritten branches.  Bifurcating trees only.
+// then any length <= 0 becomes 1e-6 (:3626-3629).  Returns the number of rewritten branches.  A multifurcating tree is served once
+// the table below is installed.
 int mpfitch_fix_negative_branch(PhyloTree *t, int force);
+
+// ---- multifurcating trees (the bootstrap consensus of phyloanalysis.cpp:2263-2307, user trees with polytomies; INTEGRATION.md
+// "Branch lengths").  A further, optional table: `neighbors` above hands out three ids and cannot show a node of higher degree.
+//     static int hk_degree(const PhyloTree *t, int id) { return (int)node_of(t, id)->neighbors.size(); }
+//     static int hk_nei_n(const PhyloTree *t, int id, int *out, int cap)
+//         { Node *v = node_of(t, id); int d = (int)v->neighbors.size(); for (int k = 0; k < d && k < cap; k++) out[k] = v->neighbors[k]->node->id; return d; }
+//     ... mpfitch_phylotree_install_poly(&poly_hooks);
+// With it installed, computeParsimony() (both classes) and mpfitch_fix_negative_branch walk the tree from leaf 0 through
+// neighbors_n; a tree with a node of degree above 3 (or fewer than n - 2 inner nodes) goes to the engine as neighbour lists
+// (mpf_polytomy_parsimony / mpf_polytomy_branch_lengths: the reference's k-ary rules, evaluated at hook root_id -- the Fitch length
+// of such a tree depends on it), a fully resolved one takes the path it took before.  Inner ids need not be contiguous.  Without
+// the table a multifurcating tree is refused as before.
+struct mpf_phylotree_poly_hooks {
+  int (*degree)(const PhyloTree *, int node_id);                                   // neighbors.size()
+  int (*neighbors_n)(const PhyloTree *, int node_id, int *out, int cap);           // ids in neighbors[] order, at most cap; returns the degree
+};
+void mpfitch_phylotree_install_poly(const mpf_phylotree_poly_hooks *hooks);       // NULL (or a table with a NULL entry) uninstalls

@@ -19,6 +19,7 @@
 // by tests/test_gpu_dropin.py.
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -136,11 +137,73 @@ void marshal_tree(PhyloTree *t, int n, std::vector<int32_t> &back)
   }
 }
 
+mpf_phylotree_poly_hooks g_poly;
+bool g_poly_installed = false;
+
+// A tree with polytomies as the neighbour lists the engine's polytomy calls take (include/mpfitch.h): walked from leaf 0 through the
+// optional hook table; inner node numbers n + 1 + i follow the order of the host's inner ids, ids[i] = the host id of inner node i.
+// false: no table installed, or the tree is fully resolved (n - 2 inner nodes of degree 3) -- the caller takes marshal_tree
+bool marshal_lists(PhyloTree *t, int n, std::vector<int32_t> &first, std::vector<int32_t> &nbr, std::vector<int> &ids)
+{
+  if (!g_poly_installed) return false;
+  auto fail = [](const char *what, int id) { std::fprintf(stderr, "mpfitch phylotree shim: multifurcating tree: %s (node %d)\n", what, id); std::exit(EXIT_FAILURE); };
+  if (g_poly.degree(t, 0) != 1) fail("leaf 0 has not one neighbour", 0);
+  int r0 = -1;
+  g_poly.neighbors_n(t, 0, &r0, 1);
+  if (r0 < n) fail("leaf 0 hangs on no inner node", r0);
+  ids.assign(1, r0);
+  std::vector<int> stack(1, r0), buf;
+  bool resolved = true;
+  while (!stack.empty()) {                  // every inner node is reached from the first one through inner neighbours
+    const int v = stack.back();
+    stack.pop_back();
+    const int d = g_poly.degree(t, v);
+    if (d < 3) fail("an inner node of degree below 3", v);
+    if (d != 3) resolved = false;
+    buf.assign((size_t)d, -1);
+    g_poly.neighbors_n(t, v, buf.data(), d);
+    for (int u : buf)
+      if (u >= n && std::find(ids.begin(), ids.end(), u) == ids.end()) {
+        if ((int)ids.size() >= n - 2) fail("more than n - 2 inner nodes (a cycle?)", u);
+        ids.push_back(u);
+        stack.push_back(u);
+      }
+  }
+  if (resolved && (int)ids.size() == n - 2) return false;
+  std::sort(ids.begin(), ids.end());
+  first.assign(1, 0);
+  nbr.clear();
+  for (int v : ids) {
+    const int d = g_poly.degree(t, v);
+    buf.assign((size_t)d, -1);
+    g_poly.neighbors_n(t, v, buf.data(), d);
+    for (int u : buf) {
+      if (u < 0) fail("a neighbour without an id", v);
+      nbr.push_back(u < n ? u + 1 : n + 1 + (int32_t)(std::lower_bound(ids.begin(), ids.end(), u) - ids.begin()));
+    }
+    first.push_back((int32_t)nbr.size());
+  }
+  return true;                              // (what else can be wrong with the lists the engine's own checks refuse, with a message)
+}
+// node number of the lists -> host id
+inline int host_id(int node, int n, const std::vector<int> &ids) { return node <= n ? node - 1 : ids[(size_t)(node - n - 1)]; }
+
 int compute(PhyloTree *t, const unsigned int *cost)
 {
   mpf_engine *e = engine_for(t, cost);
   const int n = g_h.n_taxa(t), P = g_h.n_patterns(t);
-  std::vector<int32_t> back;
+  std::vector<int32_t> back, first, nbr;
+  std::vector<int> ids;
+  if (marshal_lists(t, n, first, nbr, ids)) {
+    // the k-ary rules at the root leaf: the Fitch length of a tree with polytomies depends on it as well (phylotree.cpp:869-931)
+    unsigned short *pp = g_h.pattern_pars(t, P + kVcsizeUshort);
+    std::memset(pp, 0, sizeof(unsigned short) * (size_t)(P + kVcsizeUshort));
+    const int root = g_h.root_id ? g_h.root_id(t) : 0;
+    if (root < 0 || root >= n) { std::fprintf(stderr, "mpfitch phylotree shim: root %d is not a leaf id\n", root); std::exit(EXIT_FAILURE); }
+    uint32_t score = 0;
+    if (mpf_polytomy_parsimony(e, (int32_t)ids.size(), first.data(), nbr.data(), root + 1, &score, pp)) die("mpf_polytomy_parsimony");
+    return (int)score;
+  }
   marshal_tree(t, n, back);
   unsigned short *pp = g_h.pattern_pars(t, P + kVcsizeUshort);           // phylotree.cpp:1056-1057
   std::memset(pp, 0, sizeof(unsigned short) * (size_t)(P + kVcsizeUshort));   // :957
@@ -157,6 +220,12 @@ mpf_phylotree_nni_hooks g_nni;
 bool g_nni_installed = false;
 
 }  // namespace
+
+void mpfitch_phylotree_install_poly(const mpf_phylotree_poly_hooks *hooks)
+{
+  g_poly_installed = hooks && hooks->degree && hooks->neighbors_n;
+  if (g_poly_installed) g_poly = *hooks;
+}
 
 void mpfitch_phylotree_install_nni(const mpf_phylotree_nni_hooks *hooks)
 {
@@ -204,8 +273,9 @@ void mpfitch_phylotree_install_brlen(const mpf_phylotree_brlen_hooks *hooks)
 }
 
 // int PhyloTree::fixNegativeBranch(bool force, Node *node = NULL, Node *dad = NULL) (phylotree.cpp:3597-3633) called from the root
-// -- _ZN9PhyloTree17fixNegativeBranchEbP4NodeS1_ in a mpboot build; served: phyloanalysis.cpp:1153, :1180, :1336, :1501.  The
-// consensus tree (:2280) may be multifurcating: marshal_tree refuses it, the host keeps its own code for that call.
+// -- _ZN9PhyloTree17fixNegativeBranchEbP4NodeS1_ in a mpboot build; served: phyloanalysis.cpp:1153, :1180, :1336, :1501, and the
+// consensus tree (:2280), which may be multifurcating, once mpfitch_phylotree_install_poly has been called (else marshal_tree
+// refuses such a tree).
 int mpfitch_fix_negative_branch(PhyloTree *t, int force)
 {
   if (!g_brlen_installed) { std::fprintf(stderr, "mpfitch phylotree shim: mpfitch_phylotree_install_brlen() was not called\n"); std::exit(EXIT_FAILURE); }
@@ -222,18 +292,27 @@ int mpfitch_fix_negative_branch(PhyloTree *t, int force)
   }
   mpf_engine *e = engine_for(t, cost);
   const int n = g_h.n_taxa(t);
-  std::vector<int32_t> back;
-  marshal_tree(t, n, back);
-  if (mpf_set_tree(e, back.data())) die("mpf_set_tree");
+  std::vector<int32_t> back, first, nbr;
+  std::vector<int> ids;
+  const bool poly = marshal_lists(t, n, first, nbr, ids);
+  if (!poly) {
+    marshal_tree(t, n, back);
+    if (mpf_set_tree(e, back.data())) die("mpf_set_tree");
+    ids.resize((size_t)(n - 2));
+    for (int i = 0; i < n - 2; i++) ids[(size_t)i] = n + i;          // node number = id + 1
+  }
   const int root = g_h.root_id ? g_h.root_id(t) : 0;
   if (root < 0 || root >= n) { std::fprintf(stderr, "mpfitch phylotree shim: root %d is not a leaf id\n", root); std::exit(EXIT_FAILURE); }
-  int32_t m = 2 * n - 3, k = 0;
+  int32_t m = n + (int32_t)ids.size() - 1, k = 0;
   std::vector<int32_t> n1((size_t)m), n2((size_t)m);
   std::vector<double> len((size_t)m);
-  if (mpf_branch_lengths(e, root + 1, g_brlen.n_sites(t), parstree, m, n1.data(), n2.data(), len.data(), &k) || k != m) die("mpf_branch_lengths");
+  if (poly) {
+    if (mpf_polytomy_branch_lengths(e, (int32_t)ids.size(), first.data(), nbr.data(), root + 1, g_brlen.n_sites(t), parstree, m, n1.data(), n2.data(),
+                                    len.data(), &k) || k != m) die("mpf_polytomy_branch_lengths");
+  } else if (mpf_branch_lengths(e, root + 1, g_brlen.n_sites(t), parstree, m, n1.data(), n2.data(), len.data(), &k) || k != m) die("mpf_branch_lengths");
   int fixed = 0;
   for (int i = 0; i < m; i++) {
-    const int a = n1[(size_t)i] - 1, b = n2[(size_t)i] - 1;         // node number = id + 1
+    const int a = host_id(n1[(size_t)i], n, ids), b = host_id(n2[(size_t)i], n, ids);
     double cur = g_brlen.get_length(t, a, b);
     if (cur < 0.0 || force) {
       cur = len[(size_t)i];

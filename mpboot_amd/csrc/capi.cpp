@@ -331,6 +331,17 @@ int mpf_branch_substitutions(mpf_engine *e, int32_t root_taxon, int32_t cap, int
   return MPF_OK;
 }
 
+// the length fixNegativeBranch(force = true) makes of a branch's count (phylotree.cpp:3608-3614), in double precision on the host
+static double parsimony_branch_length(int branch_subst, int n_sites, int S)
+{
+  double branch_length = (branch_subst > 0) ? ((double)branch_subst / n_sites) : (1.0 / n_sites);
+  const double z = (double)S / (S - 1);
+  const double x = 1.0 - (z * branch_length);
+  if (x > 0) branch_length = -std::log(x) / z;
+  if (branch_length < 1e-6) branch_length = 1e-6;      // MIN_BRANCH_LEN (phylotree.h:35)
+  return branch_length;
+}
+
 // ... and the lengths fixNegativeBranch(force = true) makes of them (phylotree.cpp:3608-3614), in double precision on the host
 int mpf_branch_lengths(mpf_engine *e, int32_t root_taxon, int32_t n_sites, int32_t unit_cost_parstree, int32_t cap, int32_t *node1,
                        int32_t *node2, double *length, int32_t *n)
@@ -357,13 +368,59 @@ int mpf_branch_lengths(mpf_engine *e, int32_t root_taxon, int32_t n_sites, int32
   for (size_t i = 0; i < br.size(); i++) {
     node1[i] = br[i].node1;
     node2[i] = br[i].node2;
-    const int branch_subst = (int)s[i];
-    double branch_length = (branch_subst > 0) ? ((double)branch_subst / n_sites) : (1.0 / n_sites);
-    const double z = (double)S / (S - 1);
-    const double x = 1.0 - (z * branch_length);
-    if (x > 0) branch_length = -std::log(x) / z;
-    if (branch_length < 1e-6) branch_length = 1e-6;      // MIN_BRANCH_LEN (phylotree.h:35)
-    length[i] = branch_length;
+    length[i] = parsimony_branch_length((int)s[i], n_sites, S);
+  }
+  return MPF_OK;
+}
+
+// ---- multifurcating trees (host/polytomy.cpp): computeParsimony() and fixNegativeBranch on a tree given as neighbour lists
+int mpf_polytomy_parsimony(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, uint32_t *score,
+                           uint16_t *pattern_pars)
+{
+  NEED(e);
+  return e->eng.polytomy_parsimony(n_inner, first, nbr, root_taxon, score, pattern_pars);
+}
+
+int mpf_polytomy_branch_substitutions(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t cap,
+                                      int32_t *node1, int32_t *node2, uint32_t *subst, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> s;
+  const int rc = e->eng.polytomy_branch_substitutions(n_inner, first, nbr, root_taxon, br, s);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !subst)) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    subst[i] = s[i];
+  }
+  return MPF_OK;
+}
+
+int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_sites,
+                                int32_t unit_cost_parstree, int32_t cap, int32_t *node1, int32_t *node2, double *length, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  if (n_sites < 1) { set_error("mpf_polytomy_branch_lengths: n_sites must be positive"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> s;
+  uint32_t len = 0;
+  const bool unit = unit_cost_parstree && !e->eng.weighted();
+  const int rc = e->eng.polytomy_branch_substitutions(n_inner, first, nbr, root_taxon, br, s, unit ? &len : nullptr);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !length)) { set_error("null output"); return MPF_E_INVALID; }
+  if (unit) std::fill(s.begin(), s.end(), len);        // ParsTree under -cost fitch | e: every branch takes the tree's length (parstree.cpp:534-535)
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    length[i] = parsimony_branch_length((int)s[i], n_sites, e->eng.S());
   }
   return MPF_OK;
 }

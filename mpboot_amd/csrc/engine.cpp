@@ -2114,6 +2114,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "grow_fault") { grow_fault_ = v; return MPF_OK; }
   if (key == "nni_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("nni_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } nni_vw_ = (int)v; return MPF_OK; }
   if (key == "brlen_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("brlen_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } brlen_vw_ = (int)v; return MPF_OK; }
+  if (key == "poly_tile") { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32) { set_error("poly_tile: 0 (from the row length), 4, 8, 16 or 32 words per workgroup"); return MPF_E_INVALID; } poly_tile_ = (int)v; return MPF_OK; }
   if (key == "nni_weighted") { nni_weighted_ = v ? 1 : 0; return MPF_OK; }     // the -cost NNI climb (host/nni.cpp); no effect on a Fitch engine
   if (key == "nni_weighted_tracked") { nni_weighted_tracked_ = v ? 1 : 0; return MPF_OK; }   // ... under -bb; no effect on a Fitch engine
   if (key == "max_visits") { max_visits_ = std::max<int64_t>(0, v); return MPF_OK; }
@@ -2225,6 +2226,11 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "brlen_tile") *v = brlen_vw_;
   else if (key == "brlen_launches") *v = (int64_t)brlen_launches_;
   else if (key == "brlen_kernel_ns") *v = (int64_t)brlen_kernel_ns_;
+  else if (key == "poly_tile") *v = poly_tile_;
+  else if (key == "poly_launches") *v = (int64_t)poly_launches_;
+  else if (key == "poly_views") *v = (int64_t)poly_views_;
+  else if (key == "poly_view_ns") *v = (int64_t)poly_view_ns_;
+  else if (key == "poly_branch_ns") *v = (int64_t)poly_branch_ns_;
   else if (key == "nni_booked") *v = ufb_ ? (int64_t)ufb_->nni_booked : 0;
   else if (key == "grow_steps") *v = (int64_t)grow_steps_;
   else if (key == "grow_us") *v = (int64_t)(grow_ms_total_ * 1000.0);
@@ -2243,6 +2249,7 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "ufb_early_batches") *v = ufb_stat_early_;
   else if (key == "force_big") *v = force_big_;
   else if (key == "sankoff_short") *v = snk16_opt_;
+  else if (key == "sankoff_packed") *v = g_.snk16;       // the store holds two 16-bit costs per word (the guard of Engine::pack let sankoff_short through)
   else if (key == "check_counts") *v = check_counts_;
   else if (key == "climb_device") *v = climb_device_;
   else if (key == "climb_tile") *v = climb_vw_;

@@ -340,6 +340,13 @@ class Engine {
   void branch_order(int root_taxon, std::vector<NniBranch> &br) const;
   bool weighted() const { return sankoff_; }     // made with a cost matrix (mpf_engine_create_sankoff)
 
+  // ---- multifurcating trees (host/polytomy.cpp, polytomy.hip): a tree given as CSR neighbour lists (tips 1 .. n, inner node i =
+  // node n + 1 + i with neighbours nbr[first[i] .. first[i + 1])) scored by the reference's k-ary rules.  Stateless towards the
+  // engine's own tree: its topology stays, its vectors are marked stale (the views are made in the engine's store); books nothing
+  int polytomy_parsimony(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, uint32_t *score, uint16_t *pattern_pars);
+  int polytomy_branch_substitutions(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, std::vector<NniBranch> &br,
+                                    std::vector<uint32_t> &subst, uint32_t *fitch_len = nullptr);
+
   // ---- online UFBoot-MP bookkeeping (host/ufboot.cpp; reference IQTree::saveCurrentTree, iqtree.cpp:3271-3785)
   int ufboot_attach(int n_samples, const uint16_t *samples, double epsilon, int n_local = -1, const int32_t *sample_ids = nullptr,
                     mpf_ufb_exchange_fn exchange = nullptr, void *exchange_arg = nullptr);
@@ -530,6 +537,31 @@ class Engine {
   PinBuf<BranchDesc> h_br_desc_;
   DevBuf<uint32_t> d_br_out_;
   PinBuf<uint32_t> h_br_out_;
+
+  // multifurcating trees: the rooted shape of the tree handed over and the items of its view launch; option "poly_tile" (0 = from
+  // the row length, 4 | 8 | 16 | 32 words per workgroup), read-only options poly_launches / poly_views (directed views written) and,
+  // under "timing", poly_view_ns / poly_branch_ns (HIP-event time of the view launch / of the branch launch)
+  struct PolyTree {
+    std::vector<int32_t> tip_nb, parent, order, lev_off;
+    std::vector<uint32_t> up_slot, inputs;      // up_slot[v]: the view of v towards its parent (a tip: its own vector)
+    std::vector<PolyItem> items;
+    std::vector<PolyOut> outs;
+    int n_rows = 0;                              // step-mask rows (Fitch): one per up view + the root edge
+  } poly_tree_;
+  int polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, PolyTree &t) const;
+  int polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, bool all_views, PolyTree &t);
+  void polytomy_view_time();
+  int poly_tile_ = 0;
+  bool poly_view_timed_ = false;
+  uint64_t poly_launches_ = 0, poly_views_ = 0, poly_view_ns_ = 0, poly_branch_ns_ = 0;
+  DevBuf<uint8_t> d_poly_stage_;
+  PinBuf<uint8_t> h_poly_stage_;
+  DevBuf<uint32_t> d_poly_masks_, d_poly_cnt_, d_poly_planes_;
+  PinBuf<uint32_t> h_poly_cnt_;
+  DevBuf<uint16_t> d_poly_ptn_;                  // per-pattern lengths ([P] Fitch, [Wp] weighted) and their pinned landing place
+  PinBuf<uint16_t> h_poly_ptn_;
+  DevBuf<int32_t> d_poly_first_;                 // first_site_ on the device, as of packing poly_first_gen_
+  uint64_t poly_first_gen_ = ~0ull;
 
   int addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *insert_per_step);
   void apply_move(int remove_rec, int insert_rec);

@@ -1121,8 +1121,7 @@ __global__ __launch_bounds__(256) void k_nni_eval_masks(const uint32_t *__restri
 // Here a wave takes a chunk of <= 63 joins for its tile and adds their mutation masks into SIX
 // bit-sliced counter planes (carry-save ripple), i.e. 32 sites are counted per instruction;
 // k_pattern_sum then reads each pattern's first site out of the planes.
-constexpr int kPlaneChunk = 63;
-constexpr int kPlanes = 6;
+// (kPlaneChunk = 63 joins per chunk, kPlanes = 6 planes: kernels.hpp)
 
 template <int S, int VW>
 __global__ __launch_bounds__(256) void k_site_planes(const uint32_t *__restrict__ vec, const EvOp *__restrict__ ops,
@@ -3193,6 +3192,13 @@ hipError_t launch_site_counts(hipStream_t st, const Geometry &g, const uint32_t 
   dispatch_sv(g, [&](auto S, auto VW) { hipLaunchKernelGGL((k_site_planes<S, VW>), grid, block, 0, st, vec, ops, n_ops, planes, g.Wp, tiles); });
   hipLaunchKernelGGL(k_pattern_sum, dim3((n_ptn + 255) / 256), dim3(256), 0, st, planes, n_chunks, g.Wp, ptn_first_site,
                      n_ptn, ptn_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pattern_sum(hipStream_t st, const Geometry &g, const uint32_t *planes, int n_chunks, const int32_t *ptn_first_site,
+                              int n_ptn, uint16_t *ptn_out)
+{
+  hipLaunchKernelGGL(k_pattern_sum, dim3((n_ptn + 255) / 256), dim3(256), 0, st, planes, n_chunks, g.Wp, ptn_first_site, n_ptn, ptn_out);
   return hipGetLastError();
 }
 

@@ -256,6 +256,29 @@ size_t scan_prog_blocks(const Geometry &g, int n_scans);
 hipError_t launch_site_counts(hipStream_t st, const Geometry &g, const uint32_t *vec, const EvOp *ops, int n_ops,
                               uint32_t *planes, const int32_t *ptn_first_site, int n_ptn, uint16_t *ptn_out);
 size_t site_planes_words(const Geometry &g, int n_ops);
+// the bit-sliced per-site counters behind it: chunks of kPlaneChunk mask rows, kPlanes planes each ([chunk][plane][Wp] words);
+// launch_pattern_sum reads every pattern's first site out of n_chunks of them (k_pattern_sum)
+constexpr int kPlaneChunk = 63;
+constexpr int kPlanes = 6;
+hipError_t launch_pattern_sum(hipStream_t st, const Geometry &g, const uint32_t *planes, int n_chunks, const int32_t *ptn_first_site,
+                              int n_ptn, uint16_t *ptn_out);
+
+// Multifurcating trees (polytomy.hip; host/polytomy.cpp): every directed view of a tree given as neighbour lists, by the reference's
+// k-ary rules.  An item is one node's accumulation over inputs[in_begin .. in_begin + n_in) (slots) followed by its outputs
+// outs[out_begin .. out_begin + n_out): output = the rule over the inputs other than the vector in slot `excl` (0xFFFFFFFF: over all
+// of them), stored at slot dst (0xFFFFFFFF: not stored) and, Fitch engine, its step mask ~OR_rows(AND) at masks[mask_row][Wp]
+// (0xFFFFFFFF: none).  Items are laid out by level, lev_off[0 .. n_lev]; one launch, a workgroup barrier between levels.
+// tile: words (elements) of a row per workgroup, 4 | 8 | 16 | 32; 0 = chosen from the row length (poly_tile)
+struct PolyItem { uint32_t in_begin, n_in, out_begin, n_out; };
+struct PolyOut { uint32_t dst, excl, mask_row, pad; };
+int poly_tile(int W, int want);
+hipError_t launch_poly_views(hipStream_t st, const Geometry &g, uint32_t *vec, const PolyItem *items, const PolyOut *outs,
+                             const uint32_t *inputs, const int32_t *lev_off, int n_lev, uint32_t *masks, int tile);
+// cnt[i] = set bits of mask row i
+hipError_t launch_poly_rowsum(hipStream_t st, const Geometry &g, const uint32_t *masks, int n_rows, uint32_t *cnt);
+// per-pattern Fitch lengths from the mask rows (planes: site_planes_words(g, n_rows) words of scratch), as launch_site_counts
+hipError_t launch_poly_site_counts(hipStream_t st, const Geometry &g, const uint32_t *masks, int n_rows, uint32_t *planes,
+                                   const int32_t *ptn_first_site, int n_ptn, uint16_t *ptn_out);
 
 // Sankoff: per-pattern cost of the branch (a, b): ptn[j] = min_x(A[x] + min_y(cost[x][y] + B[y]))
 hipError_t launch_sankoff_pattern(hipStream_t st, const Geometry &g, const uint32_t *vec, uint32_t a, uint32_t b,

@@ -36,6 +36,7 @@ EXPORTS = [
     "mpf_iq_random_nnis", "mpf_iq_perturb_weights", "mpf_iq_topology_key", "mpf_ufboot_adopt", "mpf_optimize_spr_many", "mpf_optimize_spr_many_round",
     "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves", "mpf_ufboot_optimize_nni", "mpf_nni_pattern_terms", "mpf_nni_pattern_lengths",
     "mpf_branch_substitutions", "mpf_branch_lengths",
+    "mpf_polytomy_parsimony", "mpf_polytomy_branch_substitutions", "mpf_polytomy_branch_lengths",
 ]
 
 
@@ -174,6 +175,9 @@ def load_library():
         L.mpf_nni_pattern_lengths.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_branch_substitutions.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.mpf_branch_lengths.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.mpf_polytomy_parsimony.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
+        L.mpf_polytomy_branch_substitutions.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.mpf_polytomy_branch_lengths.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -618,6 +622,48 @@ class FitchEngine:
                                                C.byref(n)))
         assert n.value == m
         return a, b, ln
+
+    # ---- multifurcating trees (neighbour lists: trees.collapse_branches)
+    @staticmethod
+    def _lists(first, nbr):
+        f = np.ascontiguousarray(first, dtype=np.int32)
+        return f, np.ascontiguousarray(nbr, dtype=np.int32), len(f) - 1
+
+    def polytomy_parsimony(self, first, nbr, root_taxon: int = 1, with_patterns: bool = False):
+        """length of the tree given as CSR neighbour lists (tips 1 .. n, inner node i = node n + 1 + i with the neighbours
+        nbr[first[i]:first[i + 1]]) by the reference's rules for nodes of any degree, evaluated at the leaf root_taxon's edge
+        (computeParsimony()); with_patterns: (length, _pattern_pars[P]).  The engine's own tree is not touched."""
+        f, nb, k = self._lists(first, nbr)
+        s = C.c_uint32()
+        pp = np.zeros(self.P, dtype=np.uint16) if with_patterns else None
+        _chk(load_library().mpf_polytomy_parsimony(self.h, k, _p(f), _p(nb), root_taxon, C.byref(s), _p(pp) if with_patterns else None))
+        return (int(s.value), pp) if with_patterns else int(s.value)
+
+    def polytomy_branch_substitutions(self, first, nbr, root_taxon: int = 1):
+        """branch_substitutions for such a tree: (node1[m], node2[m], subst[m]), m = n + n_inner - 1, the walk from root_taxon with
+        the neighbours in list order; all directed views of the tree in one launch, all branches in another"""
+        f, nb, k = self._lists(first, nbr)
+        m = self.n + k - 1
+        n = C.c_int32()
+        a = np.zeros(max(m, 1), dtype=np.int32)
+        b = np.zeros(max(m, 1), dtype=np.int32)
+        s = np.zeros(max(m, 1), dtype=np.uint32)
+        _chk(load_library().mpf_polytomy_branch_substitutions(self.h, k, _p(f), _p(nb), root_taxon, m, _p(a), _p(b), _p(s), C.byref(n)))
+        assert n.value == m
+        return a[:m], b[:m], s[:m]
+
+    def polytomy_branch_lengths(self, first, nbr, n_sites: int, root_taxon: int = 1, unit_cost_parstree: bool = False):
+        """branch_lengths for such a tree: (node1[m], node2[m], length[m] float64)"""
+        f, nb, k = self._lists(first, nbr)
+        m = self.n + k - 1
+        n = C.c_int32()
+        a = np.zeros(max(m, 1), dtype=np.int32)
+        b = np.zeros(max(m, 1), dtype=np.int32)
+        ln = np.zeros(max(m, 1), dtype=np.float64)
+        _chk(load_library().mpf_polytomy_branch_lengths(self.h, k, _p(f), _p(nb), root_taxon, int(n_sites), int(bool(unit_cost_parstree)), m,
+                                                        _p(a), _p(b), _p(ln), C.byref(n)))
+        assert n.value == m
+        return a[:m], b[:m], ln[:m]
 
     def nni_pattern_terms(self, root_taxon: int = 1):
         """nni_scores by the mask-writing kernel of the tracked climb: (node1[m], node2[m], len[m][2], terms[m][3][n_patterns]);

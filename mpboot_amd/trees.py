@@ -231,3 +231,67 @@ def random_spr_moves(engine_obj, back: np.ndarray, rng: np.random.Generator, k: 
         b = apply_spr(b, rec, int(q[int(rng.integers(0, n_p))]))
         done += 1
     return b
+
+
+# ---------------------------------------------------------------- multifurcating trees as neighbour lists
+def collapse_branches(back: np.ndarray, n: int, inner_branches=()):
+    """Contract the given inner branches [(node, node), ...] of the binary tree `back` -> (first, nbr), the CSR neighbour lists
+    the engine's polytomy calls take: tips stay nodes 1 .. n, the surviving inner nodes are renumbered n + 1 .. n + n_inner in
+    the order of the smallest binary node number of each merged group, inner node i has the neighbours nbr[first[i]:first[i + 1]].
+    Neighbour order is kept: a merged node lists what its smallest member lists, slot order, with every contracted neighbour
+    replaced in place by that neighbour's other neighbours in its slot order behind the branch contracted (cyclically)."""
+    pairs = {frozenset((int(a), int(b))) for a, b in inner_branches}
+    for pr in pairs:
+        assert len(pr) == 2 and all(n < v <= 2 * n - 2 for v in pr), "inner branches only"
+    rep = list(range(2 * n - 1))
+
+    def find(v):
+        while rep[v] != v:
+            rep[v] = rep[rep[v]]
+            v = rep[v]
+        return v
+
+    for pr in pairs:
+        a, b = sorted(find(v) for v in pr)
+        assert any(int(back[3 * min(pr) + s]) // 3 == max(pr) for s in range(3)), "not a branch of the tree"
+        rep[b] = a
+
+    def others(v, frm):
+        if frm is None:
+            slots = (0, 1, 2)
+        else:
+            k = next(s for s in range(3) if int(back[3 * v + s]) // 3 == frm)
+            slots = ((k + 1) % 3, (k + 2) % 3)
+        return [(v, int(back[3 * v + s]) // 3) for s in slots]
+
+    reps = sorted({find(v) for v in range(n + 1, 2 * n - 1)})
+    number = {r: n + 1 + i for i, r in enumerate(reps)}
+    first, nbr = [0], []
+    for r in reps:
+        stack = list(reversed(others(r, None)))
+        while stack:
+            v, u = stack.pop()
+            if u > n and frozenset((v, u)) in pairs:
+                stack.extend(reversed(others(u, v)))
+            else:
+                nbr.append(u if u <= n else number[find(u)])
+        first.append(len(nbr))
+    return np.array(first, dtype=np.int32), np.array(nbr, dtype=np.int32)
+
+
+def lists_to_back(first, nbr, n: int) -> np.ndarray:
+    """the record links of a tree whose inner nodes all have three neighbours (slot = position in the list)"""
+    first = np.asarray(first)
+    assert len(first) - 1 == n - 2 and (np.diff(first) == 3).all(), "a fully resolved tree only"
+    back = empty_back(n)
+    pos = {}
+    for i in range(n - 2):
+        for s in range(3):
+            pos[(n + 1 + i, int(nbr[first[i] + s]))] = 3 * (n + 1 + i) + s
+    for (v, u), r in pos.items():
+        if u <= n:
+            back[r] = 3 * u
+            back[3 * u] = r
+        else:
+            back[r] = pos[(u, v)]
+    return back
