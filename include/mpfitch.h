@@ -384,7 +384,11 @@ int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *f
    engine's: patterns it drops (keep_all_sites 0) count 0.
    Served: the default update rule, -mulhits, mpf_ufboot_set_cutoff, -cutoff_from_btrees, ratchet booking; under
    mpf_ufboot_set_ratchet_booking(e, 0) a re-weighted climb runs without booking (the plain climb).  NOT served, MPF_E_UNSUPPORTED:
-   -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, the weighted engine (but see below).
+   the weighted engine (but see below); -storetrees, -mulhits -topboot, -distinct_iter_top_boot and a sample-sharded tracker unless
+   the option "nni_tracked_rules" (mpf_set_option, default 0) is 1: then the booked trees go through the rule in force exactly as an
+   SPR climb's do (mpf_ufboot_set_iteration gives -distinct_iter_top_boot its iteration), and on a tracker attached with
+   mpf_ufboot_attach_sharded every rank makes the same call: ONE exchange per scoring step (tags 0x40000000 + step, a closing one
+   0xFFFFFFFE per climb) carries the step's events and the current tree's scores under the rank's samples.
    Arguments, results, swap log (mpf_get_nni_moves) and counters as mpf_optimize_nni; MPF_E_STATE without a tracker or a tree.
    Read-only option "nni_booked": trees NNI climbs have handed to saveCurrentTree since the attach.
 

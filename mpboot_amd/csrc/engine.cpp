@@ -2117,6 +2117,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "poly_tile") { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32) { set_error("poly_tile: 0 (from the row length), 4, 8, 16 or 32 words per workgroup"); return MPF_E_INVALID; } poly_tile_ = (int)v; return MPF_OK; }
   if (key == "nni_weighted") { nni_weighted_ = v ? 1 : 0; return MPF_OK; }     // the -cost NNI climb (host/nni.cpp); no effect on a Fitch engine
   if (key == "nni_weighted_tracked") { nni_weighted_tracked_ = v ? 1 : 0; return MPF_OK; }   // ... under -bb; no effect on a Fitch engine
+  if (key == "nni_tracked_rules") { nni_tracked_rules_ = v ? 1 : 0; return MPF_OK; }         // ... with the optional update rules and on a sharded tracker
   if (key == "max_visits") { max_visits_ = std::max<int64_t>(0, v); return MPF_OK; }
   if (key == "small_batch_max") { small_batch_max_ = (int)std::max<int64_t>(1, std::min<int64_t>(v, 1 << 30)); return MPF_OK; }
   if (key == "ufb_moot") { ufb_moot_ = v ? 1 : 0; return MPF_OK; }
@@ -2221,6 +2222,7 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "nni_branches_scored") *v = (int64_t)nni_branches_;
   else if (key == "nni_weighted") *v = nni_weighted_;
   else if (key == "nni_weighted_tracked") *v = nni_weighted_tracked_;
+  else if (key == "nni_tracked_rules") *v = nni_tracked_rules_;
   else if (key == "nni_kept_worse") *v = (int64_t)nni_kept_worse_;
   else if (key == "nni_kernel_ns") *v = (int64_t)nni_kernel_ns_;
   else if (key == "brlen_tile") *v = brlen_vw_;

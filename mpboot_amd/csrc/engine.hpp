@@ -158,6 +158,7 @@ struct UfbState : books::Deferred {      // (boot_trees, store, refs, topo_index
   const std::vector<ScanPlan> *log_plans = nullptr;
   uint64_t draws = 0, events = 0, gemm_rows = 0, batches = 0, stored = 0;
   uint64_t nni_booked = 0;                       // trees NNI climbs have handed to saveCurrentTree (read-only option "nni_booked")
+  uint32_t nni_tag = 0;                          // sample-sharded tracker: scoring steps of the NNI climb under way that exchanged their events
   double gemm_ms = 0.0;
   double t_lookup = 0;                           // ... of t_replay: canonical forms for the topology map
   uint64_t lookups = 0;
@@ -507,6 +508,8 @@ class Engine {
   int nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home, const std::vector<uint32_t> &part, const std::vector<uint32_t> &crow,
                          const std::vector<uint8_t> &pass, const std::vector<uint32_t> *sel_rows, int rows_p, bool have_C, Product product,
                          std::vector<UfbEvent> &events);
+  // sample-sharded tracker: the step's local events and the current tree's own scores (index 0) -> the events of all ranks, in replay order
+  int nni_exchange_events(uint32_t n_idx, std::vector<UfbEvent> &events);
   void nni_full_order(int root_taxon, std::vector<NniBranch> &br) const;
   void nni_swap(const NniSwap &m);
   std::vector<NniSwap> nni_log_;
@@ -519,6 +522,9 @@ class Engine {
   // option "nni_weighted_tracked" (with "nni_weighted"): mpf_ufboot_optimize_nni and mpf_nni_pattern_lengths are served on the weighted
   // engine (k_snk_nni_eval_vals, nni_book_step_snk); 0: refused as before
   int nni_weighted_tracked_ = 0;
+  // option "nni_tracked_rules": mpf_ufboot_optimize_nni also serves -storetrees, -mulhits -topboot, -distinct_iter_top_boot and a
+  // sample-sharded tracker (the rules of host/ufboot_common.hpp joined to the NNI booking step); 0: the four are refused as before
+  int nni_tracked_rules_ = 0;
   uint64_t nni_kernel_ns_ = 0;                   // option "timing": HIP-event time of the scoring kernels (read-only option "nni_kernel_ns")
   DevBuf<NniDesc> d_nni_desc_;
   DevBuf<uint32_t> d_nni_planes_;                // k_nni_eval_masks: [2 planes][3 rows per branch, padded to the product's row tile][Wp]

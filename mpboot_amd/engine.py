@@ -706,11 +706,12 @@ class FitchEngine:
         return np.stack([c[:k.value] for c in cols], axis=1) if k.value else np.zeros((0, 4), dtype=np.int32)
 
     # ---- online UFBoot-MP bookkeeping (IQTree::saveCurrentTree during optimize_spr)
-    def ufboot_attach(self, samples, epsilon: float = 0.5, shard=None, exchange=None):
+    def ufboot_attach(self, samples, epsilon: float = 0.5, shard=None, exchange=None, sample_ids=None):
         """samples: [n_samples][n_patterns] bootstrap weights (all of them, on every rank).
-        shard = (rank, world): multi-GPU online phase -- this engine keeps samples rank, rank + world, ... and
-        `exchange` (default: mpboot_amd.shard.event_exchange(), an all-gather over torch.distributed) merges the
-        per-batch events of all ranks; every rank must then make the same optimize_spr calls."""
+        shard = (rank, world): multi-GPU online phase -- this engine keeps samples rank, rank + world, ... (or `sample_ids`, any
+        other split the ranks agree on) and `exchange` (default: mpboot_amd.shard.event_exchange(), an all-gather over
+        torch.distributed) merges the per-batch events of all ranks; every rank must then make the same optimize_spr /
+        ufboot_optimize_nni calls (the latter on a sharded tracker: set_option("nni_tracked_rules", 1))."""
         samples = np.ascontiguousarray(samples, dtype=np.uint16)
         if samples.ndim != 2 or samples.shape[1] != self.P:
             raise ValueError("samples must be [n_samples][n_patterns]")
@@ -720,7 +721,7 @@ class FitchEngine:
             self._drop_exchange()
             return
         rank, world = shard
-        ids = np.arange(rank, self.ufb_B, world, dtype=np.int32)
+        ids = np.arange(rank, self.ufb_B, world, dtype=np.int32) if sample_ids is None else np.ascontiguousarray(sample_ids, dtype=np.int32)
         local = np.ascontiguousarray(samples[ids])
         if exchange is None:
             from . import shard as _shard
@@ -740,7 +741,9 @@ class FitchEngine:
         """optimize_nni under -bb: the attached tracker books the current tree of every scoring step and both NNIs of every
         evaluated branch (mpf_ufboot_optimize_nni) -> (length, nni_count, nni_steps).  A weighted engine serves it after
         set_option("nni_weighted", 1) and set_option("nni_weighted_tracked", 1) (defaults 0: MpfError -6): every booked tree with
-        its own row of per-pattern lengths -- a candidate's at its branch, the current tree's at the leaf root_taxon"""
+        its own row of per-pattern lengths -- a candidate's at its branch, the current tree's at the leaf root_taxon.
+        With -storetrees, -mulhits -topboot or -distinct_iter_top_boot in force, or on a sample-sharded tracker, it is served after
+        set_option("nni_tracked_rules", 1) (default 0: MpfError -6); ufboot_set_iteration keeps the iteration number in step"""
         s, cnt, steps = C.c_uint32(), C.c_int32(), C.c_int32()
         _chk(load_library().mpf_ufboot_optimize_nni(self.h, root_taxon, int(bool(speednni)), max_steps, C.byref(s), C.byref(cnt),
                                                     C.byref(steps)))

@@ -353,13 +353,20 @@ struct Engine::NniReplay {
     u.lookups++;
     return u.topo_index.emplace(topology_key(cand_code), tree_index).first->second;
   }
-  // the current tree under self_len, every sample offered R_T (u.h_rt) on the host
-  void book_self(uint32_t self_len, bool pass)
+  // the current tree under self_len, every sample offered R_T (u.h_rt) on the host; merged (a sample-sharded tracker): R_T lives in
+  // pieces on the ranks -- the offers are the events of index 0 the ranks have exchanged
+  void book_self(uint32_t self_len, bool pass, const std::vector<UfbEvent> *merged = nullptr)
   {
     u.cur_logl_now = -(int32_t)self_len;
-    int64_t tree_index = e.ufb_book_tree(self_len, pass, 0xFFFFFFFFu, false, [&](uint32_t cc) -> const std::string & { return topology_key(cc); });
+    int64_t tree_index = e.ufb_book_tree(self_len, pass, 0xFFFFFFFFu, u.store_trees, [&](uint32_t cc) -> const std::string & { return topology_key(cc); });
     if (tree_index < 0) return;
-    bool looked_up = false;
+    bool looked_up = u.store_trees;                // (-storetrees: tree_str is set at the top, no lookup per sample)
+    if (merged) {
+      for (size_t ep = 0; ep < merged->size() && (*merged)[ep].idx == 0u; ep++)
+        e.ufb_one_event((*merged)[ep].b, (*merged)[ep].s, tree_index, looked_up, 0xFFFFFFFFu,
+                        [&](int64_t ti, uint32_t cc) { return lookup_topology(ti, cc); }, dctx);
+      return;
+    }
     for (int c2 = 0; c2 < u.Bl; c2++)
       e.ufb_one_event((uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2], tree_index, looked_up, 0xFFFFFFFFu,
                       [&](int64_t ti, uint32_t cc) { return lookup_topology(ti, cc); }, dctx);
@@ -370,11 +377,11 @@ struct Engine::NniReplay {
     size_t ep = 0;
     for (uint32_t c = 0; c < (uint32_t)blen.size(); c++) {
       u.cur_logl_now = -(int32_t)blen[c];
-      int64_t tree_index = e.ufb_book_tree(blen[c], pass[c] != 0, c, false, [&](uint32_t cc) -> const std::string & { return topology_key(cc); });
+      int64_t tree_index = e.ufb_book_tree(blen[c], pass[c] != 0, c, u.store_trees, [&](uint32_t cc) -> const std::string & { return topology_key(cc); });
       if (tree_index < 0) continue;
       const uint32_t idx = 1u + c;
       while (ep < events.size() && events[ep].idx < idx) ep++;
-      bool looked_up = false;
+      bool looked_up = u.store_trees;
       for (; ep < events.size() && events[ep].idx == idx; ep++)
         e.ufb_one_event(events[ep].b, events[ep].s, tree_index, looked_up, c, [&](int64_t ti, uint32_t cc) { return lookup_topology(ti, cc); }, dctx);
     }
@@ -391,7 +398,7 @@ struct Engine::NniReplay {
 
 // One step's event extraction.  Output indices: 0 = the current tree (offered on the host), 1 + c = candidate c, behind them the
 // home slots; part[idx] = the part of a candidate (0xFFFFFFFF: no candidate), home[part] = its home slot, crow[idx] = the row of C
-// an index reads (0xFFFFFFFF: none), pass[c]: candidate c takes part.  sel_rows (or nullptr): the mask rows a compact product
+// an index reads (0xFFFFFFFF: none), pass[c]: candidate c takes part (under -storetrees every one does: the replay decides).  sel_rows (or nullptr): the mask rows a compact product
 // multiplies, handed to product(rows_p, device copy) -- which runs here unless the caller has C already.  events: in replay order.
 // staging: thr[n_parts] | home[n_parts] | best[Bp] | crow[n_idx] | cost[n_idx] | (even) info[n_idx] as pairs | sel[rows_p] | event counter
 template <class Product>
@@ -425,10 +432,13 @@ int Engine::nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home
   if (u.ev.cap == 0) { const size_t c0 = (size_t)std::min<int64_t>(ufb_event_cap_, 1 << 18); UCHK(u.ev.reserve(c0)); }
   uint32_t *d_evcount = u.thr.p + o_cnt;
   uint32_t n_ev = 0;
+  // the list rules and -storetrees see every (candidate, sample) at or below the sample's bound at the start of the step, not only the
+  // strict improvements of a running minimum (as spr_sweeps_ufboot asks for them)
+  const int all_events = (u.topboot || u.distinct || u.store_trees) ? 1 : 0;
   for (bool again = false;; again = true) {
     if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
     UCHK(launch_ufb_events(st_, reinterpret_cast<const uint2 *>(u.thr.p + o_info), u.thr.p + o_cost, u.thr.p, u.thr.p + o_home, u.thr.p + o_crow, u.C.p,
-                           u.Bp, u.Bl, u.rt.p, u.thr.p + o_best, n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, 0));
+                           u.Bp, u.Bl, u.rt.p, u.thr.p + o_best, n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, all_events));
     UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
     UCHK(hipStreamSynchronize(st_));
     n_ev = u.h_small.p[0];
@@ -442,11 +452,37 @@ int Engine::nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home
     UCHK(hipStreamSynchronize(st_));
     events.assign(u.h_ev.p, u.h_ev.p + n_ev);
     for (UfbEvent &e : events) e.b = (uint32_t)u.ids[(size_t)e.b];
-    std::vector<UfbEvent> tmp;
-    std::vector<uint32_t> count;
-    sort_events(events, tmp, count, n_idx, (uint32_t)u.B);
+    if (!u.exchange) {                             // (a sample-sharded tracker orders the merged events: nni_exchange_events)
+      std::vector<UfbEvent> tmp;
+      std::vector<uint32_t> count;
+      sort_events(events, tmp, count, n_idx, (uint32_t)u.B);
+    }
   }
   u.events += n_ev;
+  return MPF_OK;
+}
+
+// A sample-sharded tracker: the product and the extraction ran over this rank's columns, R_T (u.h_rt) holds its samples only.  ONE
+// exchange per scoring step: the step's local events and, as index 0, the current tree's score under every local sample; every rank
+// then replays the union in (candidate, sample) order, so books and draws stay identical everywhere.  Tags 0x40000000 + step: the
+// scan batches of an SPR climb count from 0, and the exchanges keep 31 bits of a tag.
+int Engine::nni_exchange_events(uint32_t n_idx, std::vector<UfbEvent> &events)
+{
+  UfbState &u = *ufb_;
+  static_assert(sizeof(UfbEvent) == sizeof(mpf_ufb_event), "event layouts must match");
+  for (int c2 = 0; c2 < u.Bl; c2++) events.push_back(UfbEvent{0u, (uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2]});
+  const mpf_ufb_event *all = nullptr;
+  uint32_t n_all_ev = 0;
+  const uint32_t tag = 0x40000000u | (u.nni_tag++ & 0x3FFFFFFFu);
+  if (u.exchange(u.exchange_arg, tag, reinterpret_cast<const mpf_ufb_event *>(events.data()), (uint32_t)events.size(), &all, &n_all_ev) != 0) {
+    set_error("tracked NNI climb: event exchange failed (ranks out of step?)");
+    return MPF_E_STATE;
+  }
+  const UfbEvent *pa = reinterpret_cast<const UfbEvent *>(all);
+  std::vector<UfbEvent> merged(pa, pa + n_all_ev), tmp;
+  std::vector<uint32_t> count;
+  sort_events(merged, tmp, count, n_idx, (uint32_t)u.B);
+  events.swap(merged);
   return MPF_OK;
 }
 
@@ -480,7 +516,10 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
   const double lim = -u.logl_cutoff + 1e-4;        // iqtree.cpp:3343: booked iff  -len > logl_cutoff - 1e-4
   const bool none_pass = have_cut && lim <= 0.0;
   const uint32_t mp_max = have_cut ? (none_pass ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
-  if (none_pass) return MPF_OK;
+  // -storetrees (iqtree.cpp:3302-3341): a topology met before is counted, and booked again when its length improved, whatever the
+  // cut-off says -- no step is skipped, every row is multiplied, every candidate takes part in the extraction and the replay decides
+  const bool store_trees = u.store_trees, sharded = u.exchange != nullptr;
+  if (none_pass && !store_trees) return MPF_OK;
   const double t0 = now_ms();
   if (!u.rt_valid) { int rc = ufb_current_tree_reps(); if (rc) return rc; }       // (uses C: in front of the product)
   UCHK(u.h_rt.reserve((size_t)u.Bp));
@@ -516,32 +555,40 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
 
   // ---- the current tree: its own length (ratchet: its length on the original alignment), every sample from R_T
   const uint32_t self_len = ratchet ? u.rt_orig : cur;
-  replay.book_self(self_len, self_len <= mp_max);
+  const bool self_pass = !none_pass && self_len <= mp_max;
+  if (!sharded) replay.book_self(self_len, self_pass);
 
   // ---- the candidates that pass: product (unless a ratchet step has it), extraction
-  std::vector<uint8_t> pass(2 * (size_t)nb);
+  std::vector<uint8_t> pass(2 * (size_t)nb), take(2 * (size_t)nb);       // pass: the cut-off test; take: part of the extraction
   uint32_t n_pass = 0;
-  for (size_t c = 0; c < pass.size(); c++) { pass[c] = blen[c] <= mp_max; n_pass += pass[c]; }
+  for (size_t c = 0; c < pass.size(); c++) { pass[c] = !none_pass && blen[c] <= mp_max; take[c] = store_trees || pass[c]; n_pass += take[c]; }
   std::vector<UfbEvent> events;
   if (n_pass) {
-    const bool compact = have_cut && !ratchet;
+    const bool compact = have_cut && !ratchet && !store_trees;
     std::vector<uint32_t> sel_rows, home(nb), part((size_t)n_idx, 0xFFFFFFFFu);
     std::vector<uint32_t> crow((size_t)n_idx, 0xFFFFFFFFu);
     for (uint32_t i = 0; i < nb; i++) {
       home[i] = 1u + 2u * nb + i;
       part[1 + 2 * i] = part[2 + 2 * i] = i;
-      if (!pass[2 * i] && !pass[2 * i + 1]) continue;
+      if (!take[2 * i] && !take[2 * i + 1]) continue;
       if (!compact) {
         crow[1 + 2 * i] = 3 * i + 1; crow[2 + 2 * i] = 3 * i + 2; crow[1 + 2 * nb + i] = 3 * i;
         continue;
       }
       crow[1 + 2 * nb + i] = (uint32_t)sel_rows.size(); sel_rows.push_back(3 * i);
       for (uint32_t k = 0; k < 2; k++)
-        if (pass[2 * i + k]) { crow[1 + 2 * i + k] = (uint32_t)sel_rows.size(); sel_rows.push_back(3 * i + 1 + k); }
+        if (take[2 * i + k]) { crow[1 + 2 * i + k] = (uint32_t)sel_rows.size(); sel_rows.push_back(3 * i + 1 + k); }
     }
     const int rows_p = compact ? round_up((int)sel_rows.size(), kUfbRowTile) : mask_rows_p;
-    int rc = nni_extract_events(n_idx, home, part, crow, pass, compact ? &sel_rows : nullptr, rows_p, have_C, product, events);
+    int rc = nni_extract_events(n_idx, home, part, crow, take, compact ? &sel_rows : nullptr, rows_p, have_C, product, events);
     if (rc) return rc;
+  }
+  if (sharded) {
+    // (the bounds the extraction ran under are those in front of the current tree's own booking: more events at most, each of
+    //  which the rule looks at again)
+    int rc = nni_exchange_events(n_idx, events);
+    if (rc) return rc;
+    replay.book_self(self_len, self_pass, &events);
   }
   const double t1 = now_ms();
   u.t_dev += t1 - t0;
@@ -573,13 +620,14 @@ int Engine::nni_book_step_snk(const std::vector<NniBranch> &br, const std::vecto
   const double lim = -u.logl_cutoff + 1e-4;        // iqtree.cpp:3343
   const bool none_pass = have_cut && lim <= 0.0;
   const uint32_t mp_max = have_cut ? (none_pass ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
-  if (none_pass) return MPF_OK;
+  const bool store_trees = u.store_trees, sharded = u.exchange != nullptr;      // (-storetrees: as in nni_book_step)
+  if (none_pass && !store_trees) return MPF_OK;
   std::vector<uint32_t> blen(len.begin(), len.begin() + 2 * (size_t)nb);
-  std::vector<uint8_t> pass(2 * (size_t)nb);
+  std::vector<uint8_t> pass(2 * (size_t)nb), take(2 * (size_t)nb, 1);
   uint32_t n_pass = 0;
   if (!ratchet) {
-    for (size_t c = 0; c < pass.size(); c++) { pass[c] = blen[c] <= mp_max; n_pass += pass[c]; }
-    if (!n_pass && cur > mp_max) return MPF_OK;    // nothing of this step is booked: nothing to multiply
+    for (size_t c = 0; c < pass.size(); c++) { pass[c] = !none_pass && blen[c] <= mp_max; n_pass += pass[c]; }
+    if (!store_trees && !n_pass && cur > mp_max) return MPF_OK;    // nothing of this step is booked: nothing to multiply
   }
   const double t0 = now_ms();
   // ---- K from vmax (nni_eval has waited for it), the bit planes of all 2 nb + 1 rows
@@ -624,22 +672,24 @@ int Engine::nni_book_step_snk(const std::vector<NniBranch> &br, const std::vecto
     UCHK(hipMemcpyAsync(u.h_col.p, u.d_col.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
     UCHK(hipStreamSynchronize(st_));
     u.rt_orig = self_len = (uint32_t)u.h_col.p[R];
-    for (size_t c = 0; c < pass.size(); c++) { blen[c] = (uint32_t)u.h_col.p[c]; pass[c] = blen[c] <= mp_max; n_pass += pass[c]; }
+    for (size_t c = 0; c < pass.size(); c++) { blen[c] = (uint32_t)u.h_col.p[c]; pass[c] = !none_pass && blen[c] <= mp_max; n_pass += pass[c]; }
   }
+  if (!store_trees) take = pass;
   // ---- product of the rows that are booked (unless a ratchet step has it), extraction
-  const bool compact = have_cut && !ratchet;
+  const bool compact = have_cut && !ratchet && !store_trees;
   std::vector<uint32_t> sel_rows, home(1, 1u + 2u * nb), part((size_t)n_idx, 0xFFFFFFFFu), crow((size_t)n_idx, 0xFFFFFFFFu);
   for (uint32_t c = 0; c < 2 * nb; c++) {
     part[1 + c] = 0u;
     if (!compact) crow[1 + c] = c;
-    else if (pass[c]) { crow[1 + c] = (uint32_t)sel_rows.size(); sel_rows.push_back(c); }
+    else if (take[c]) { crow[1 + c] = (uint32_t)sel_rows.size(); sel_rows.push_back(c); }
   }
   if (compact) { cur_row = (uint32_t)sel_rows.size(); sel_rows.push_back(R); }
   crow[1 + 2 * nb] = cur_row;
   const int rows_p = compact ? round_up((int)sel_rows.size(), kUfbRowTile) : plane_rows_p;
   std::vector<UfbEvent> events;
-  int rc = nni_extract_events(n_idx, home, part, crow, pass, compact ? &sel_rows : nullptr, rows_p, have_C, product, events);
+  int rc = nni_extract_events(n_idx, home, part, crow, take, compact ? &sel_rows : nullptr, rows_p, have_C, product, events);
   if (rc) return rc;
+  if (sharded) { rc = nni_exchange_events(n_idx, events); if (rc) return rc; }
   if (!ratchet) u.rt_orig = (uint32_t)u.h_rt.p[oc];
   float ms = 0.f;
   if (timed && hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) u.gemm_ms += ms;
@@ -647,7 +697,7 @@ int Engine::nni_book_step_snk(const std::vector<NniBranch> &br, const std::vecto
   u.t_dev += t1 - t0;
   // ---- host replay: the current tree (every sample from R_T), then the candidates
   NniReplay replay(*this, mv);
-  replay.book_self(self_len, self_len <= mp_max);
+  replay.book_self(self_len, !none_pass && self_len <= mp_max, sharded ? &events : nullptr);
   replay.book_candidates(blen, pass, events);
   u.t_replay += now_ms() - t1;
   return MPF_OK;
@@ -660,17 +710,26 @@ int Engine::ufboot_optimize_nni(int root_taxon, bool speednni, int max_steps, ui
   if (!ufb_) { set_error("no UFBoot tracker attached"); return MPF_E_STATE; }
   if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
   const UfbState &u = *ufb_;
-  if (u.exchange || u.Bl != u.B) { set_error("tracked NNI climb: not served with a sample-sharded tracker"); return MPF_E_UNSUPPORTED; }
-  if (u.store_trees) { set_error("tracked NNI climb: -storetrees is not served"); return MPF_E_UNSUPPORTED; }
-  if (u.topboot) { set_error("tracked NNI climb: -mulhits -topboot is not served"); return MPF_E_UNSUPPORTED; }
-  if (u.distinct) { set_error("tracked NNI climb: -distinct_iter_top_boot is not served"); return MPF_E_UNSUPPORTED; }
+  // option "nni_tracked_rules": the three optional rules and a sample-sharded tracker are served (nni_book_step); 0: refused as ever
+  const bool rules = nni_tracked_rules_ != 0;
+  if ((u.exchange || u.Bl != u.B) && !(rules && u.exchange)) { set_error("tracked NNI climb: not served with a sample-sharded tracker"); return MPF_E_UNSUPPORTED; }
+  if (u.store_trees && !rules) { set_error("tracked NNI climb: -storetrees is not served"); return MPF_E_UNSUPPORTED; }
+  if (u.topboot && !rules) { set_error("tracked NNI climb: -mulhits -topboot is not served"); return MPF_E_UNSUPPORTED; }
+  if (u.distinct && !rules) { set_error("tracked NNI climb: -distinct_iter_top_boot is not served"); return MPF_E_UNSUPPORTED; }
   if (root_taxon < 1 || root_taxon > n_) { set_error("NNI climb: root_taxon must be in 1 .. n_taxa"); return MPF_E_INVALID; }
   // (suspended: other weights than the attach-time ones under -no_hclimb1_bb, or an attach-time pattern without a site --
   //  saveCurrentTree is not called, iqtree.cpp:3280: the plain climb)
   const bool tracked = !u.suspended;
   if (tracked) ufb_->rt_valid = false;
+  ufb_->nni_tag = 0;
   const int rc = nni_climb(root_taxon, speednni, max_steps, tracked, score, nni_count, nni_steps);
   ufb_->rt_valid = false;
+  if (rc == MPF_OK && tracked && u.exchange) {
+    // closing handshake, as the SPR climb has one: a rank that took another path would be in the middle of a step here
+    const mpf_ufb_event *all = nullptr;
+    uint32_t n_all_ev = 0;
+    if (u.exchange(u.exchange_arg, 0xFFFFFFFEu, nullptr, 0, &all, &n_all_ev) != 0) { set_error("tracked NNI climb: ranks out of step at the end of the climb"); return MPF_E_STATE; }
+  }
   return rc;
 }
 

@@ -104,8 +104,54 @@ def wall(workloads, n_samples, out_path):
             json.dump(out, f, indent=1)
 
 
+def rules(workloads, n_samples, rule_names, out_path):
+    """--rule: per workload ONE tracked climb from the tool's random tree under each named rule (option nni_tracked_rules), the
+    default rule timed next to it in the same run; a fresh tracker per climb, so that every climb books into empty lists"""
+    out = {}
+    for wl in workloads:
+        codes, e, _start = load(wl)
+        n, P = codes.shape
+        e.set_option("nni_tracked_rules", 1)
+        rnd = trees.random_topology(n, np.random.default_rng(5))
+        samples = np.random.default_rng(7).multinomial(P, np.ones(P) / P, size=n_samples).astype(np.uint16)
+        r = {"n": n, "Wp": e.Wp, "samples": n_samples}
+        for name in ["default"] + [x for x in rule_names if x != "default"]:
+            ts = []
+            for _ in range(3):
+                e.seed_ties(engine.TIE_RANDOM, 5)
+                e.ufboot_attach(samples)
+                if name == "storetrees":
+                    e.ufboot_set_store_trees(True)
+                elif name == "topboot":
+                    e.ufboot_set_mulhits(True)
+                    e.ufboot_set_topboot(10)
+                elif name == "distinct":
+                    e.ufboot_set_distinct_iter(2)
+                    e.ufboot_set_iteration(1)
+                e.set_tree(rnd)
+                b0 = e.get_option("nni_booked")
+                t0 = time.perf_counter()
+                res = e.ufboot_optimize_nni(1, True, 50)
+                ts.append((time.perf_counter() - t0) * 1e3)
+                booked = e.get_option("nni_booked") - b0
+                dups = e.ufboot_duplicates()
+                e.ufboot_detach()
+            r[name] = {"tracked_climb_random_ms": spread(ts), "result": list(res), "booked": booked, "duplicates": dups}
+        for name in r:
+            if isinstance(r[name], dict) and name != "default":
+                r[name]["ratio_to_default"] = r[name]["tracked_climb_random_ms"]["median"] / r["default"]["tracked_climb_random_ms"]["median"]
+        out[wl] = r
+        print(wl, json.dumps(r), flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rule", nargs="*", default=None, choices=["default", "storetrees", "topboot", "distinct"],
+                    help="one tracked climb per named rule next to the default rule (no name: all of them)")
     ap.add_argument("--kernels", nargs="*", default=None, help="only full evaluations by both kernels (for a kernel trace)")
     ap.add_argument("--workloads", nargs="*", default=["C2", "C3"])
     ap.add_argument("--samples", type=int, default=1000)
@@ -113,5 +159,7 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.kernels is not None:
         kernels(a.kernels or ["C2", "C3"])
+    elif a.rule is not None:
+        rules(a.workloads, a.samples, a.rule or ["storetrees", "topboot", "distinct"], a.out)
     else:
         wall(a.workloads, a.samples, a.out)
