@@ -45,7 +45,7 @@ Engine::~Engine()
   if (std::getenv("MPF_VIEWS_PROFILE"))
     std::fprintf(stderr, "[views] launches %llu ops %llu levels %llu\n", (unsigned long long)stats.view_launches, (unsigned long long)stats.newview_ops, (unsigned long long)dbg_levels_);
   if (d_codes_) (void)hipFree(d_codes_);
-  if (d_vec_) (void)hipFree(d_vec_);
+  if (d_vec_store_) (void)hipFree(d_vec_store_);
   if (d_tipslots_) (void)hipFree(d_tipslots_);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
@@ -225,7 +225,7 @@ int Engine::pack()
     // 16-bit costs, two patterns per lane (the reference's default "short" arithmetic, sprparsimony.cpp:556-641), while
     // no intermediate can reach 2^16: a view entry is at most (tips below) x max cost, a candidate sums three terms
     const bool want16 = snk16_opt_ != 0 && 3ull * (uint64_t)n_ * (uint64_t)g_.highest_cost < 65536ull;
-    if (wp != g_.Wp || !d_vec_ || (int)want16 != g_.snk16) {
+    if (wp != g_.Wp || !d_vec_store_ || (int)want16 != g_.snk16) {
       g_.Wp = wp;
       g_.snk16 = want16 ? 1 : 0;
       vec_words_ = nslots_ * (size_t)g_.S * (size_t)(want16 ? g_.Wp / 2 : g_.Wp);
@@ -271,7 +271,7 @@ int Engine::pack()
       HIPCHK(hipMemcpyAsync(d_infidx_.p, inf_index_.data(), inf_index_.size() * sizeof(int32_t), hipMemcpyHostToDevice, st_));
     g_.cost = d_cost_.p;
     g_.pwgt = d_pwgt_.p;
-    HIPCHK(launch_pack_tips_sankoff(st_, g_, d_vec_, d_codes_, n_, P_, d_infidx_.p, ninf_, datatype_));
+    HIPCHK(launch_pack_tips_sankoff(st_, g_, vec_base(), d_codes_, n_, P_, d_infidx_.p, ninf_, datatype_));
     HIPCHK(hipStreamSynchronize(st_));
     invalidate_vectors();
     return MPF_OK;
@@ -296,7 +296,7 @@ int Engine::pack()
   Wref_ = (ce % 8) ? ce + (8 - ce % 8) : ce;           // the reference's parsimonyLength (AVX build)
   int wp = ((ce + 31) / 32) * 32;                      // our row pitch: whole 128-byte lines
   if (wp == 0) wp = 32;
-  if (wp != g_.Wp || !d_vec_) {
+  if (wp != g_.Wp || !d_vec_store_) {
     g_.Wp = wp;
     vec_words_ = nslots_ * (size_t)g_.S * g_.Wp;
     // below 2 GiB the scan kernel addresses the whole store through one raw buffer (32-bit offsets); above, 64-bit bases
@@ -312,7 +312,7 @@ int Engine::pack()
       for (int w = 0; w < wgt_[s]; w++) s2p[(size_t)first_site_[s] + w] = s;
   HIPCHK(d_site2ptn_.reserve(s2p.size()));
   HIPCHK(hipMemcpyAsync(d_site2ptn_.p, s2p.data(), s2p.size() * sizeof(int32_t), hipMemcpyHostToDevice, st_));
-  HIPCHK(launch_pack_tips(st_, g_, d_vec_, d_codes_, n_, P_, d_site2ptn_.p, nsites_, datatype_, d_tipslots_));
+  HIPCHK(launch_pack_tips(st_, g_, vec_base(), d_codes_, n_, P_, d_site2ptn_.p, nsites_, datatype_, d_tipslots_));
   HIPCHK(hipStreamSynchronize(st_));
   invalidate_vectors();                      // (re-weighting changes every vector, not the tree)
   return MPF_OK;
@@ -324,9 +324,9 @@ int Engine::pack()
 // stream stood still each time (eight chains of an iteration-parallel -bb run spent more time there than in their kernels).
 hipError_t Engine::vec_store_fit(size_t bytes)
 {
-  if (d_vec_ && bytes <= vec_cap_bytes_) return hipSuccess;
-  if (d_vec_) { (void)hipFree(d_vec_); d_vec_ = nullptr; vec_cap_bytes_ = 0; }
-  const hipError_t e = hipMalloc((void **)&d_vec_, bytes);
+  if (d_vec_store_ && bytes <= vec_cap_bytes_) return hipSuccess;
+  if (d_vec_store_) { (void)hipFree(d_vec_store_); d_vec_store_ = nullptr; vec_cap_bytes_ = 0; }
+  const hipError_t e = hipMalloc((void **)&d_vec_store_, bytes);
   if (e == hipSuccess) vec_cap_bytes_ = bytes;
   return e;
 }
@@ -358,7 +358,7 @@ int Engine::tip_vector(int tipno, uint32_t *out)
   if (tipno < 1 || tipno > n_) { set_error("tip out of range"); return MPF_E_INVALID; }
   if (sankoff_) { set_error("mpf_get_tip_vector: bit-packed tips exist in Fitch mode only"); return MPF_E_UNSUPPORTED; }
   std::vector<uint32_t> tmp((size_t)g_.S * g_.Wp);
-  HIPCHK(hipMemcpy(tmp.data(), d_vec_ + (size_t)(tipno - 1) * g_.S * g_.Wp, tmp.size() * sizeof(uint32_t),
+  HIPCHK(hipMemcpy(tmp.data(), vec_base() + (size_t)(tipno - 1) * g_.S * g_.Wp, tmp.size() * sizeof(uint32_t),
                    hipMemcpyDeviceToHost));
   // hand back the reference's rows: its state count (rows the kernels do not carry -- multistate symbols beyond the 20th, never
   // present -- are empty) and its length W; sites behind the alignment are all ones in every row (sprparsimony.cpp:2947-2960)
@@ -443,6 +443,7 @@ void Engine::invalidate_all()
   sched_cache_valid_ = false;
   sweep_cache_valid_ = false;
   shadow_ok_ = g_.shoff != 0;                      // (no valid inner vector left that the word-major copy could disagree with)
+  rows_ok_ = true;                                 // (... nor one whose rows could be stale)
 }
 
 // every vector stale, topology unchanged (re-weighting, a full re-evaluation, the same tree handed over again): what
@@ -455,6 +456,39 @@ void Engine::invalidate_vectors()
   views_valid_ = false;
   all_invalid_ = true;
   shadow_ok_ = g_.shoff != 0;
+  rows_ok_ = true;
+}
+
+// The refresh about to be launched can work on the word-major copy alone: DNA, one word per lane, a kernel that has the shape
+// (k_newview_wgq, k_newview_chain), and every valid vector current in that copy.
+bool Engine::refresh_wm_only(bool chains) const
+{
+  return refresh_wm_ && shadow_ok_ && views_mode_ >= 1 && !sankoff_ && g_.S == 4 && g_.vw == 1 && g_.shoff != 0 && (chains || g_.nv_pipe);
+}
+
+// Brings the row-major layout of every valid inner vector up to date from the word-major copy (one launch), in front of a launch
+// that reads rows.  Nothing to do while rows_ok_ holds.
+int Engine::ensure_rows()
+{
+  if (rows_ok_) return MPF_OK;
+  // (rows_ok_ goes down only behind a word-major-only refresh, which needs shadow_ok_ and keeps it; every later refresh that is
+  //  not word-major-only comes through here first)
+  if (!shadow_ok_ || !g_.shoff) { set_error("ensure_rows: neither layout of the vectors is current"); broken_ = true; return MPF_E_STATE; }
+  std::vector<uint32_t> &slots = row_slots_;
+  slots.clear();
+  for (size_t r = 3 * ((size_t)n_ + 1); r < valid_.size() && r < back_.size(); r++)
+    if (valid_[r]) slots.push_back(slot((int)r));
+  if (!slots.empty()) {
+    // (the list goes up as the single EvOp of tree_length does: a copy from pageable memory is staged before the call returns.
+    //  Everything is on the engine's own stream, in order with the refresh before and the reader behind -- no wait on the host)
+    hipError_t e = d_rowslots_.reserve(slots.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rowslots_.p, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_);
+    if (e == hipSuccess) e = launch_rows_from_wm(st_, g_, d_vec_store_, d_rowslots_.p, (int)slots.size());
+    if (e != hipSuccess) { set_error(std::string("ensure_rows: ") + hipGetErrorString(e)); broken_ = true; return MPF_E_HIP; }
+    ensure_rows_launches_++;
+  }
+  rows_ok_ = true;
+  return MPF_OK;
 }
 
 // Invariant: a valid vector has valid inputs.  The vectors containing `node` are its own three and, walking
@@ -726,7 +760,9 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
     x.wp_out = d_out();
     x.wp_max_parts = (uint32_t)(8 * n_prune);
   }
-  HIPCHK(launch_newview_levels(st_, g_, d_vec_, dops, dlo, 1, d_cntp_.p, (uint32_t)nslots_, d_cnt(), nullptr, x));
+  x.wm_only = refresh_wm_only(false);             // (nothing is valid: the inputs are tips, current in both layouts)
+  HIPCHK(launch_newview_levels(st_, g_, vec_base(), dops, dlo, 1, d_cntp_.p, (uint32_t)nslots_, d_cnt(), nullptr, x));
+  if (x.wm_only) rows_ok_ = false;
   stats.view_launches++;
   HIPCHK(launch_cntsum(st_, g_, dops, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), tiles_for_levels(g_)));
   if (timing_ >= 2) { HIPCHK(hipEventRecord(ev3_, st_)); view_events_pending_ = true; }
@@ -792,7 +828,9 @@ int Engine::schedule_views(const std::vector<int> *roots)
     if (timing_ >= 2) HIPCHK(hipEventRecord(ev2_, st_));
     RefreshExtra x;
     if (sc_maxlev_ < 0) x.n_lev_ptr = reinterpret_cast<const int32_t *>(src + sc_nlev_off_);      // (made by k_sched: the count lives there)
-    HIPCHK(launch_newview_levels(st_, g_, d_vec_, dops, dlo, sc_maxlev_ < 0 ? 1 : sc_maxlev_, d_cntp_.p, (uint32_t)nslots_, d_cnt(), nullptr, x));
+    x.wm_only = refresh_wm_only(false);           // (nothing is valid: the inputs are tips, current in both layouts)
+    HIPCHK(launch_newview_levels(st_, g_, vec_base(), dops, dlo, sc_maxlev_ < 0 ? 1 : sc_maxlev_, d_cntp_.p, (uint32_t)nslots_, d_cnt(), nullptr, x));
+    if (x.wm_only) rows_ok_ = false;
     stats.view_launches++;
     HIPCHK(launch_cntsum(st_, g_, dops, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), tiles_for_levels(g_)));
     if (timing_ >= 2) { HIPCHK(hipEventRecord(ev3_, st_)); view_events_pending_ = true; }
@@ -1013,6 +1051,11 @@ int Engine::schedule_views(const std::vector<int> *roots)
   // chip-wide launch when there are many (one workgroup would need longer than the launch costs)
   const bool fold_inside = views_mode_ >= 1 && !sankoff_ && nops <= 512;   // (independent of chain_max_ops_)
   RefreshExtra x;
+  // the word-major copy alone where the kernel has that shape and the copy is current; every other refresh reads rows
+  x.wm_only = refresh_wm_only(chains);
+  if (!x.wm_only) { const int rc = ensure_rows(); if (rc) return rc; }
+  uint32_t *const vec = vec_base();
+  x.rows = rows_ok_;                              // (chained kernel: keeps the rows current as long as they are)
   cnt_on_host_ = false;
   if (fold_inside && want_host_results_) { x.cnt_host = h_cnt(); cnt_on_host_ = true; }   // small batch: counts land in the host mirror
   for (int i = 0; i < 2; i++)
@@ -1031,7 +1074,7 @@ int Engine::schedule_views(const std::vector<int> *roots)
       x.n_kid_upd = (int)(kid_upd_.size() / 3);
       x.kids = reinterpret_cast<uint2 *>(d_vstage_.p);
     }
-    HIPCHK(launch_newview_chains(st_, g_, d_vec_, dops, dlo, ch_levels_, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), fold_inside ? d_done_.p : nullptr, x));
+    HIPCHK(launch_newview_chains(st_, g_, vec, dops, dlo, ch_levels_, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), fold_inside ? d_done_.p : nullptr, x));
     stats.view_launches++;
   } else if (views_mode_ >= 1) {
     // narrow levels (the partial trees of the addition phase, small refreshes): fewer waves per workgroup -- a wave of the
@@ -1042,11 +1085,12 @@ int Engine::schedule_views(const std::vector<int> *roots)
       const long need = (2 * per_level * newview_tile(g_) + 63) / 64;
       x.waves_hint = need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
     }
-    HIPCHK(launch_newview_levels(st_, g_, d_vec_, dops, dlo, maxlev, d_cntp_.p, (uint32_t)nslots_, d_cnt(), fold_inside ? d_done_.p : nullptr, x));
+    HIPCHK(launch_newview_levels(st_, g_, vec, dops, dlo, maxlev, d_cntp_.p, (uint32_t)nslots_, d_cnt(), fold_inside ? d_done_.p : nullptr, x));
+    if (x.wm_only) rows_ok_ = false;              // (k_newview_wgq's word-major shape writes no rows)
     stats.view_launches++;
   } else {
     for (int l = 0; l < maxlev; l++) {
-      HIPCHK(launch_newview(st_, g_, d_vec_, dops + lo[l], lo[l + 1] - lo[l], d_cntp_.p, (uint32_t)nslots_));
+      HIPCHK(launch_newview(st_, g_, vec, dops + lo[l], lo[l + 1] - lo[l], d_cntp_.p, (uint32_t)nslots_));
       stats.view_launches++;
     }
   }
@@ -1057,8 +1101,10 @@ int Engine::schedule_views(const std::vector<int> *roots)
   if (timing_ >= 2) { HIPCHK(hipEventRecord(ev3_, st_)); view_events_pending_ = true; }
   cnt_copy_pending_ = true;                 // copied back together with the scan results (or by update_views)
   {
-    // shadow_ok_ = "every valid vector has its word-major copy": true whenever nothing is valid (invalidate_all / _vectors),
-    // kept by k_newview_wgq and k_newview_chain, which write both layouts, lost when any other kernel writes vectors
+    // shadow_ok_ = "every valid vector is current in the word-major copy": true whenever nothing is valid (invalidate_all /
+    // _vectors), kept by k_newview_wgq and k_newview_chain, which always write that copy, lost when any other kernel writes vectors.
+    // rows_ok_ = the same for the row-major layout of the inner vectors: lost behind a refresh that wrote the word-major copy alone
+    // (above: k_newview_wgq's word-major shape; the chained kernel writes rows as long as they are current), restored by ensure_rows
     const bool both = views_mode_ >= 1 && !sankoff_ && g_.vw == 1 && g_.shoff != 0 && (chains || g_.nv_pipe);
     if (!both) shadow_ok_ = false;
   }
@@ -1177,7 +1223,11 @@ int Engine::tree_length(uint32_t *len)
   HIPCHK(reserve_results(1));
   HIPCHK(hipMemcpyAsync(d_evops_.p, &op, sizeof(op), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(d_out(), 0, clear_words(1) * sizeof(uint32_t), st_));
-  HIPCHK(launch_evaluate(st_, g_, d_vec_, d_evops_.p, 1, d_out()));
+  {
+    // (right after a word-major-only refresh: two vectors from that copy instead of a conversion of the whole tree)
+    const bool wm = !sankoff_ && !rows_ok_ && shadow_ok_ && g_.S == 4 && g_.shoff != 0;
+    HIPCHK(launch_evaluate(st_, g_, wm ? vec_base() : vec_rows(), d_evops_.p, 1, d_out(), wm));
+  }
   HIPCHK(hipMemcpyAsync(h_out(), d_out(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
   HIPCHK(hipStreamSynchronize(st_));
   tree_len_ = sankoff_ ? h_out()[0] : (tip(a) ? 0u : sc_[a]) + (tip(b) ? 0u : sc_[b]) + h_out()[0];
@@ -1375,7 +1425,7 @@ int Engine::run_scans(std::vector<ScanPlan> &plans, std::vector<uint32_t> &out_h
     vmax = ufb_->vmax.p;
     vals_rows_ = (uint32_t)nout;
   }
-  HIPCHK(launch_scan(st_, g_, d_vec_, dhdr, (int)nh, dprog, d_out(), prog_max_depth_, host_direct ? h_out() : nullptr, (uint32_t)nout,
+  HIPCHK(launch_scan(st_, g_, vec_rows(), dhdr, (int)nh, dprog, d_out(), prog_max_depth_, host_direct ? h_out() : nullptr, (uint32_t)nout,
                      d_done_.p + 16, vals, (uint32_t)g_.Wp, vmax));
   if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
   if (host_direct) {           // the kernels wrote the host's result buffers themselves
@@ -1571,6 +1621,7 @@ int Engine::run_walks(std::vector<ScanPlan> &plans, const uint32_t **out_host)
       ufb_rows_ = (uint32_t)nout;
     }
     if (host_direct) __atomic_store_n(h_out() + nout, 0u, __ATOMIC_RELAXED);     // the flag word behind the results
+    const bool wm = shadow_ok_ && scan_shadow_ && (prog ? scan_prog_word_major(g_) : scan_walk_word_major(g_, maxd));
     if (prog) {
       HIPCHK(d_prog_.reserve(scan_prog_bytes((int)nd)));
       // (a cached sweep re-uses the program only if one was planned for exactly these descriptors: the sweep may have run on
@@ -1589,12 +1640,12 @@ int Engine::run_walks(std::vector<ScanPlan> &plans, const uint32_t **out_host)
         HIPCHK(hipMemsetAsync(d_trace_.p, 0, trace_words_ * sizeof(unsigned long long), st_));
         trace = d_trace_.p;
       }
-      HIPCHK(launch_scan_prog(st_, g_, d_vec_, descs, (int)nd, d_prog_.p, d_out(), d_ncand_.p,
-                              host_direct ? h_out() : nullptr, (uint32_t)nout, d_done_.p + 8, trace, shadow_ok_ && scan_shadow_));
+      HIPCHK(launch_scan_prog(st_, g_, wm ? vec_base() : vec_rows(), descs, (int)nd, d_prog_.p, d_out(), d_ncand_.p,
+                              host_direct ? h_out() : nullptr, (uint32_t)nout, d_done_.p + 8, trace, wm));
       stats.plan_launches++;
     } else {
-      HIPCHK(launch_scan_walk(st_, g_, d_vec_, d_kids(), n_, descs, (int)nd, d_out(), d_ncand_.p, maxd, mask_ptr, info_ptr,
-                              host_direct ? h_out() : nullptr, (uint32_t)nout, d_done_.p + 8, shadow_ok_ && scan_shadow_));
+      HIPCHK(launch_scan_walk(st_, g_, wm ? vec_base() : vec_rows(), d_kids(), n_, descs, (int)nd, d_out(), d_ncand_.p, maxd, mask_ptr, info_ptr,
+                              host_direct ? h_out() : nullptr, (uint32_t)nout, d_done_.p + 8, wm));
     }
     if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
     part_min_used_ = false;
@@ -1905,8 +1956,9 @@ int Engine::sweep_scan_dev(int mt, uint64_t *n_tests, uint32_t *min_mp)
       parts_gen_ = walk_gen_;
       n_parts_dev_ = nd;
     }
-    HIPCHK(launch_scan_prog(st_, g_, d_vec_, d_walk_.p, (int)nd, d_prog_.p, d_out(), d_ncand_.p, nullptr, (uint32_t)nout, d_done_.p + 8, nullptr,
-                            shadow_ok_ && scan_shadow_));
+    const bool wm = shadow_ok_ && scan_shadow_ && scan_prog_word_major(g_);
+    HIPCHK(launch_scan_prog(st_, g_, wm ? vec_base() : vec_rows(), d_walk_.p, (int)nd, d_prog_.p, d_out(), d_ncand_.p, nullptr, (uint32_t)nout, d_done_.p + 8, nullptr,
+                            wm));
     stats.plan_launches++;
     if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
     __atomic_store_n(h_pmin_.p + nd, 0u, __ATOMIC_RELAXED);
@@ -2009,7 +2061,7 @@ int Engine::pattern_scores(uint16_t *ptn, int32_t *total)
     DevBuf<uint16_t> d_p;
     std::vector<uint16_t> hp((size_t)g_.Wp);
     HIPCHK(d_p.reserve((size_t)g_.Wp));
-    HIPCHK(launch_sankoff_pattern(st_, g_, d_vec_, slot(back_[start_]), slot(start_), d_p.p));      // (left = far end, right = start: as tree_length)
+    HIPCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(back_[start_]), slot(start_), d_p.p));      // (left = far end, right = start: as tree_length)
     HIPCHK(hipMemcpyAsync(hp.data(), d_p.p, hp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st_));
     HIPCHK(hipStreamSynchronize(st_));
     long sum = 0;
@@ -2044,7 +2096,7 @@ int Engine::pattern_scores(uint16_t *ptn, int32_t *total)
   HIPCHK(d_ptn.reserve((size_t)P_));
   HIPCHK(hipMemcpyAsync(d_evops_.p, ops.data(), ops.size() * sizeof(EvOp), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemcpyAsync(d_first.p, first_site_.data(), (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice, st_));
-  HIPCHK(launch_site_counts(st_, g_, d_vec_, d_evops_.p, (int)ops.size(), planes.p, d_first.p, P_, d_ptn.p));
+  HIPCHK(launch_site_counts(st_, g_, vec_rows(), d_evops_.p, (int)ops.size(), planes.p, d_first.p, P_, d_ptn.p));
   HIPCHK(hipMemcpyAsync(ptn, d_ptn.p, (size_t)P_ * sizeof(uint16_t), hipMemcpyDeviceToHost, st_));
   HIPCHK(hipStreamSynchronize(st_));
   if (total) {
@@ -2088,6 +2140,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   }
   if (key == "dev_sched") { dev_sched_ = v != 0; sched_cache_valid_ = false; dsw_valid_ = false; return MPF_OK; }
   if (key == "dev_plan") { dev_plan_ = v != 0; plan_ride_ = !(v & 2); dsw_valid_ = false; return MPF_OK; }   // (bit 1: the walk plan as a launch of its own)               // scan descriptors of mpf_sweep_scan laid out on the device   // refresh schedule of a new topology made on the device (k_sched)
+  if (key == "refresh_wm") { refresh_wm_ = v != 0; return MPF_OK; }          // refreshes on the word-major copy alone where they can (A/B switch; no effect without that copy)
   if (key == "scan_shadow") { scan_shadow_ = v != 0; return MPF_OK; }        // planned scan reads the word-major copy when it is current (A/B switch)
   if (key == "reduce") { g_.reduce = v ? 1 : 0; return MPF_OK; }
   if (key == "xcd_map") { g_.map = v ? 1 : 0; return MPF_OK; }
@@ -2191,6 +2244,12 @@ int Engine::get_option(const std::string &key, int64_t *v) const
 {
   if (key == "scan_prog") *v = scan_prog_;
   else if (key == "prog_min_descs") *v = prog_min_descs_;
+  else if (key == "refresh_wm") *v = refresh_wm_ ? 1 : 0;
+  // ... and whether this engine can follow it at all (DNA with a word-major copy; the weighted engine, wider alphabets and stores of
+  // 2 GiB and more ignore the option)
+  else if (key == "refresh_wm_active") *v = (refresh_wm_ && !sankoff_ && g_.S == 4 && g_.shoff != 0) ? 1 : 0;
+  else if (key == "rows_ok") *v = rows_ok_ ? 1 : 0;
+  else if (key == "ensure_rows_launches") *v = (int64_t)ensure_rows_launches_;
   else if (key == "scan_batch") *v = scan_batch_;
   else if (key == "words_per_lane") *v = g_.vw;
   else if (key == "kernel_states") *v = g_.S;            // state rows the kernels carry: 4 (DNA, binary), 20 (protein, multistate <= 20 symbols), 32

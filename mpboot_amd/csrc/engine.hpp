@@ -658,7 +658,16 @@ private:
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr, ev2_ = nullptr, ev3_ = nullptr, ev4_ = nullptr;
   bool plan_event_pending_ = false;
   uint8_t *d_codes_ = nullptr;
-  uint32_t *d_vec_ = nullptr, *d_tipslots_ = nullptr;
+  // The vector store.  Nobody takes d_vec_store_ directly: vec_rows() is for launches that read inner vectors in the row-major
+  // layout (it brings the rows up to date first), vec_base() for the rest -- launches that read the word-major copy and have
+  // checked shadow_ok_, launches that read or write tips only, and kernels that rebuild whatever they read.
+  uint32_t *d_vec_store_ = nullptr, *d_tipslots_ = nullptr;
+  uint32_t *vec_base() const { return d_vec_store_; }
+  uint32_t *vec_rows() { return ensure_rows() == 0 ? d_vec_store_ : nullptr; }      // (nullptr: every launcher refuses it)
+  int ensure_rows();
+  bool refresh_wm_only(bool chains) const;
+  DevBuf<uint32_t> d_rowslots_;
+  std::vector<uint32_t> row_slots_;              // ensure_rows: the valid inner vectors (a member: no allocation per conversion)
   // results buffer: [cnt: nslots][out: ...] so that one copy brings back both
   DevBuf<uint32_t> d_res_;
   PinBuf<uint32_t> h_res_;
@@ -785,8 +794,11 @@ private:
   int dsw_key_[4] = {0, 0, 0, 0};               // ... this radius / these options
   uint32_t dsw_parts_ = 0, dsw_out_ = 0;
   bool sched_on_dev_ = false;                   // d_vstage_ holds a k_sched-made schedule (diagnostics: options sched_levels / sched_ticks / sched_desc_ticks)
-  bool shadow_ok_ = false;                      // every VALID vector has its word-major copy (Geometry::shoff) in place
+  bool shadow_ok_ = false;                      // every VALID vector is current in the word-major copy (Geometry::shoff); refreshes may read it then
   bool scan_shadow_ = true;                     // option scan_shadow
+  bool rows_ok_ = true;                         // every VALID inner vector is current in the row-major layout (the mirror of shadow_ok_)
+  bool refresh_wm_ = true;                      // option refresh_wm: refreshes read and write the word-major copy alone where they can
+  uint64_t ensure_rows_launches_ = 0;           // option ensure_rows_launches (read only)
   bool plan_ride_ = true;                       // the walk plan of a device-planned sweep rides on the refresh launch
   std::vector<int> sc_order_;
   bool sweep_cache_valid_ = false, walk_dev_reuse_ = false;

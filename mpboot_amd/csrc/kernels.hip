@@ -102,6 +102,17 @@ __device__ __forceinline__ void store_tile(const Tile<S, VW> &t, uint32_t *__res
   }
 }
 
+// DNA, one word per lane, from / to the word-major copy (Geometry::shoff): the four state words of site word w0 in one 16-byte access
+__device__ __forceinline__ void load_tile_wm(Tile<4, 1> &t, const uint32_t *wm, uint32_t slot, int Wp, int w0)
+{
+  const uint4 x = *reinterpret_cast<const uint4 *>(wm + ((size_t)slot * (size_t)Wp + (size_t)w0) * 4);
+  t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
+}
+__device__ __forceinline__ void store_tile_wm(const Tile<4, 1> &t, uint32_t *wm, uint32_t slot, int Wp, int w0)
+{
+  *reinterpret_cast<uint4 *>(wm + ((size_t)slot * (size_t)Wp + (size_t)w0) * 4) = make_uint4(t.v[0][0], t.v[1][0], t.v[2][0], t.v[3][0]);
+}
+
 // gfx950 has a three-input bitwise op (v_bitop3_b32); truth table with src0 = 0xF0, src1 = 0xCC, src2 = 0xAA
 #define MPF_B3_ANDOR 0xEA   // (a & b) | c
 #define MPF_B3_FITCH 0xD4   // c ? (a & b) : (a | b)
@@ -454,12 +465,15 @@ struct ProgEnt;
 __device__ void walk_plan_item(const uint2 *__restrict__ kids, uint32_t n, const WalkDesc *__restrict__ desc, int n_scans,
                                ProgEnt *__restrict__ prog, uint32_t cid_mask, int item, int lane);
 
-template <int S, int TW>
+// WM (DNA): operands and result live in the word-major copy alone (x.shadow) -- one 16-byte load per operand, one 16-byte store,
+// the row-major store is neither read nor written (Engine::rows_ok_ goes down; Engine::ensure_rows rewrites the rows on demand)
+template <int S, int TW, bool WM = false>
 __global__ __launch_bounds__(1024) void k_newview_wgq(uint32_t *__restrict__ vec, const NvOp *__restrict__ ops,
                                                       const int32_t *__restrict__ lev_off, int n_lev,
                                                       uint32_t *__restrict__ cntp, uint32_t nslots, int Wp,
                                                       uint32_t *__restrict__ cnt, uint32_t *__restrict__ done, RefreshExtra x)
 {
+  static_assert(!WM || S == 4, "word-major copy: DNA");
   constexpr int OPI = 64 / TW;                     // ops per wave and round
   __shared__ int s_last;
   const int lane = threadIdx.x & 63;
@@ -490,20 +504,25 @@ __global__ __launch_bounds__(1024) void k_newview_wgq(uint32_t *__restrict__ vec
     if (ib < e) {
       // descriptors run two rounds ahead, operands one.  Indices are clamped into the level: surplus lanes repeat its last op on
       // the same words as the lanes that own it and write the same values -- no lane is switched off, so every round issues
-      // the same requests (1 descriptor, 2 S operand rows, S result rows, 1 count) and the wait for the next operands can
-      // be counted past this round's stores
+      // the same requests (1 descriptor, 2 S operand rows, S result rows, 1 count; WM: 1 descriptor, 2 operands, 1 result, 1 count)
+      // and the wait for the next operands can be counted past this round's stores
       NvOp o = ops[min(ib + sub, e - 1)], o1 = ops[min(ib + step + sub, e - 1)];
       Tile<S, 1> ta, tb;
-      load_tile<S, 1>(ta, vec, o.a, Wp, w0);
-      load_tile<S, 1>(tb, vec, o.b, Wp, w0);
+      auto ld = [&](Tile<S, 1> &t, uint32_t slot) {
+        if constexpr (WM) load_tile_wm(t, x.shadow, slot, Wp, w0);
+        else load_tile<S, 1>(t, vec, slot, Wp, w0);
+      };
+      ld(ta, o.a);
+      ld(tb, o.b);
       for (; ib < e; ib += step) {
         const NvOp o2 = ops[min(ib + 2 * step + sub, e - 1)];
         Tile<S, 1> na, nb, tc;
-        load_tile<S, 1>(na, vec, o1.a, Wp, w0);
-        load_tile<S, 1>(nb, vec, o1.b, Wp, w0);
+        ld(na, o1.a);
+        ld(nb, o1.b);
         const uint32_t k = fitch<S, 1>(tc, ta, tb);
-        store_tile<S, 1>(tc, vec, o.dst, Wp, w0);
-        if constexpr (S == 4)
+        if constexpr (WM) store_tile_wm(tc, x.shadow, o.dst, Wp, w0);
+        else store_tile<S, 1>(tc, vec, o.dst, Wp, w0);
+        if constexpr (S == 4 && !WM)
           if (x.shadow) *reinterpret_cast<uint4 *>(x.shadow + ((size_t)o.dst * (size_t)Wp + (size_t)w0) * 4) = make_uint4(tc.v[0][0], tc.v[1][0], tc.v[2][0], tc.v[3][0]);
         cntp[(size_t)tile * nslots + o.dst] = group_sum<TW>(k);
         ta = na; tb = nb; o = o1; o1 = o2;
@@ -536,19 +555,26 @@ constexpr uint32_t kPrev = 0xFFFFFFFFu;
 // lane) those spilled to scratch (round 5: 560-1300 bytes per lane).  They run EIGHT waves -- 256 registers --, each wave taking
 // two of the sixteen chain slots of a level one after the other.
 template <int S, int VW> constexpr int chain_waves() { return S * VW >= 16 ? 8 : 16; }
-template <int S, int VW, int RED, int D>
+// WM (DNA, one word per lane): operands come from the word-major copy (x.shadow), the result always goes there; its rows are
+// written as well while x.rows says that the row-major store is current (Engine::rows_ok_), so that it stays so
+template <int S, int VW, int RED, int D, bool WM = false>
 __global__ __launch_bounds__((chain_waves<S, VW>() * 64)) void k_newview_chain(uint32_t *__restrict__ vec, const NvOp *__restrict__ ops,
                                                         const int32_t *__restrict__ wl_off, int n_lev,
                                                         uint32_t *__restrict__ cntp, uint32_t nslots, int Wp,
                                                         uint32_t *__restrict__ cnt, uint32_t *__restrict__ done, int n_ops,
                                                         RefreshExtra x)
 {
+  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
   __shared__ int s_last;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int tile = blockIdx.x;
   bool valid;
   const int w0 = lane_word<VW>(tile, lane, Wp, valid);
+  auto ld = [&](Tile<S, VW> &t, uint32_t slot) {
+    if constexpr (WM) load_tile_wm(t, x.shadow, slot, Wp, w0);
+    else load_tile<S, VW>(t, vec, slot, Wp, w0);
+  };
   {
     // chores for the scan launch that follows on the stream, so that it needs neither a copy nor a memset dispatch in
     // front of it: topology updates for the device-walked scan (this kernel does not read kids) and the cleared outputs
@@ -572,8 +598,8 @@ __global__ __launch_bounds__((chain_waves<S, VW>() * 64)) void k_newview_chain(u
       for (int d = 0; d < D; d++) o[d] = ops[b + d < e ? b + d : e - 1];
 #pragma unroll
       for (int d = 0; d < D; d++) {                 // unconditional (indices are clamped): keeps the request counts static
-        if constexpr (!TA1) { if (o[d].a != kPrev) load_tile<S, VW>(ta[d], vec, o[d].a, Wp, w0); }
-        load_tile<S, VW>(tb[d], vec, o[d].b, Wp, w0);
+        if constexpr (!TA1) { if (o[d].a != kPrev) ld(ta[d], o[d].a); }
+        ld(tb[d], o[d].b);
       }
 #pragma unroll
       for (int d = 0; d < D; d++) nx[d] = ops[b + D + d < e ? b + D + d : e - 1];
@@ -582,13 +608,13 @@ __global__ __launch_bounds__((chain_waves<S, VW>() * 64)) void k_newview_chain(u
   {                                                                                                      \
     uint32_t cost;                                                                                       \
     if (o[d].a != kPrev) {                                                                               \
-      if constexpr (TA1) load_tile<S, VW>(ta[0], vec, o[d].a, Wp, w0);                                   \
+      if constexpr (TA1) ld(ta[0], o[d].a);                                   \
       cost = fitch<S, VW>(c, ta[TA1 ? 0 : d], tb[d]);                                                    \
     } else {                                                                                             \
       Tile<S, VW> p = c;                                                                                 \
       cost = fitch<S, VW>(c, p, tb[d]);                                                                  \
     }                                                                                                    \
-    if (valid) store_tile<S, VW>(c, vec, o[d].dst, Wp, w0);                                              \
+    if (valid && (!WM || x.rows)) store_tile<S, VW>(c, vec, o[d].dst, Wp, w0);                           \
     if constexpr (S == 4 && VW == 1)                                                                     \
       if (valid && x.shadow)  /* the word-major copy the planned scan reads (Geometry::shoff) */         \
         *reinterpret_cast<uint4 *>(x.shadow + ((size_t)o[d].dst * (size_t)Wp + (size_t)w0) * 4) = make_uint4(c.v[0][0], c.v[1][0], c.v[2][0], c.v[3][0]); \
@@ -596,8 +622,8 @@ __global__ __launch_bounds__((chain_waves<S, VW>() * 64)) void k_newview_chain(u
     if (lane == 0) cntp[(size_t)tile * nslots + o[d].dst] = tot;                                         \
     o[d] = nx[d];                                                                                        \
     if (RELOAD) {                                                                                        \
-      if constexpr (!TA1) { if (o[d].a != kPrev) load_tile<S, VW>(ta[d], vec, o[d].a, Wp, w0); }         \
-      load_tile<S, VW>(tb[d], vec, o[d].b, Wp, w0);                                                      \
+      if constexpr (!TA1) { if (o[d].a != kPrev) ld(ta[d], o[d].a); }         \
+      ld(tb[d], o[d].b);                                                      \
     }                                                                                                    \
   }
       int k = b;
@@ -916,7 +942,8 @@ __global__ __launch_bounds__(256) void k_cntsum(const NvOp *__restrict__ ops, in
 
 // ---------------------------------------------------------------- K2: batched evaluate
 
-template <int S, int VW, int RED>
+// WM: `vec` is the word-major copy (Geometry::shoff), one 16-byte load per lane and vector (DNA, one word per lane).
+template <int S, int VW, int RED, bool WM = false>
 __global__ __launch_bounds__(256) void k_evaluate(const uint32_t *__restrict__ vec, const EvOp *__restrict__ ops,
                                                   int n_ops, uint32_t *__restrict__ out, int Wp, int tiles)
 {
@@ -929,12 +956,36 @@ __global__ __launch_bounds__(256) void k_evaluate(const uint32_t *__restrict__ v
   bool valid;
   const int w0 = lane_word<VW>(tile, lane, Wp, valid);
   Tile<S, VW> a, b;
-  load_tile<S, VW>(a, vec, o.a, Wp, w0);
-  load_tile<S, VW>(b, vec, o.b, Wp, w0);
+  if constexpr (WM) {
+    static_assert(S == 4 && VW == 1, "word-major copy: DNA, one word per lane");
+    load_tile_wm(a, vec, o.a, Wp, w0);
+    load_tile_wm(b, vec, o.b, Wp, w0);
+  } else {
+    load_tile<S, VW>(a, vec, o.a, Wp, w0);
+    load_tile<S, VW>(b, vec, o.b, Wp, w0);
+  }
   uint32_t cost = empty_count<S, VW>(a, b);
   cost = valid ? cost : 0u;
   const uint32_t tot = wave_total<RED>(cost);
   if (lane == 0 && tot) atomic_add_u32(out + o.out, tot);
+}
+
+// Rows from the word-major copy (Engine::ensure_rows): after refreshes that wrote the word-major copy alone, the row-major store of
+// the listed vectors is rewritten from it.  A wave per (listed vector, 64 words): one 16-byte load and four row stores per lane.
+__global__ __launch_bounds__(256) void k_rows_from_wm(uint32_t *__restrict__ vec, const uint32_t *__restrict__ wm,
+                                                      const uint32_t *__restrict__ slots, int n_slots, int Wp, int tiles)
+{
+  const int lane = threadIdx.x & 63;
+  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  gw = __builtin_amdgcn_readfirstlane(gw);
+  if (gw >= n_slots * tiles) return;
+  const int i = gw / tiles, tile = gw - i * tiles;
+  const uint32_t slot = slots[i];
+  bool valid;
+  const int w0 = lane_word<1>(tile, lane, Wp, valid);
+  Tile<4, 1> t;
+  load_tile_wm(t, wm, slot, Wp, w0);
+  if (valid) store_tile<4, 1>(t, vec, slot, Wp, w0);
 }
 
 // ---------------------------------------------------------------- NNI scoring (IQTree::optimizeNNI, host/nni.cpp)
@@ -2725,6 +2776,7 @@ hipError_t launch_newview_levels(hipStream_t st, const Geometry &g, uint32_t *ve
     });
     return hipGetLastError();
   }
+  if (x.wm_only && !(g.vw == 1 && g.nv_pipe && g.S == 4 && g.shoff)) return hipErrorInvalidValue;   // (only k_newview_wgq has that shape)
   if (g.vw == 1 && g.nv_pipe) {                    // TW lanes per op on TW-word tiles, operands requested a round ahead
     RefreshExtra xs = x;
     if (g.shoff && g.S == 4) xs.shadow = vec + g.shoff;
@@ -2734,6 +2786,12 @@ hipError_t launch_newview_levels(hipStream_t st, const Geometry &g, uint32_t *ve
     dim3 qgrid((unsigned)(g.Wp / tw) + extra);
     dispatch_states(g.S, [&](auto S) {
       auto launch = [&](auto TW) {
+        if constexpr (S == 4) {
+          if (xs.wm_only) {                         // (checked above: there is a word-major copy)
+            hipLaunchKernelGGL((k_newview_wgq<4, TW, true>), qgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, xs);
+            return;
+          }
+        }
         hipLaunchKernelGGL((k_newview_wgq<S, TW>), qgrid, block, 0, st, vec, ops, lev_off, n_lev, cntp, nslots, g.Wp, cnt, done, xs);
       };
       if (tw == 32) launch(int_c<32>()); else if (tw == 16) launch(int_c<16>()); else if (tw == 8) launch(int_c<8>()); else launch(int_c<4>());
@@ -2766,6 +2824,14 @@ hipError_t launch_newview_chains(hipStream_t st, const Geometry &g, uint32_t *ve
   dim3 grid((unsigned)tiles_of(g));
   RefreshExtra xs = x;
   if (g.shoff && g.S == 4 && g.vw == 1) xs.shadow = vec + g.shoff;
+  if (x.wm_only) {                                 // operands from the word-major copy; rows written while xs.rows
+    if (!xs.shadow) return hipErrorInvalidValue;
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_newview_chain<4, 1, RED, 4, true>), grid, dim3(chain_waves<4, 1>() * 64), 0, st, vec, ops,
+                         wl_off, n_lev, cntp, nslots, g.Wp, cnt, done, n_ops, xs);
+    });
+    return hipGetLastError();
+  }
   dispatch_sv(g, [&](auto S, auto VW) {
     dispatch_reduce(g, [&](auto RED) {
       hipLaunchKernelGGL((k_newview_chain<S, VW, RED, (S * VW <= 4 ? 4 : 2)>), grid, dim3(chain_waves<S, VW>() * 64), 0, st, vec, ops,
@@ -2797,9 +2863,21 @@ hipError_t launch_cntsum(hipStream_t st, const Geometry &g, const NvOp *ops, int
 
 int tiles_for(const Geometry &g) { return g.sankoff ? (snk_elems(g) + 63) / 64 : tiles_of(g); }
 
-hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *vec, const EvOp *ops, int n_ops,
-                           uint32_t *out)
+hipError_t launch_rows_from_wm(hipStream_t st, const Geometry &g, uint32_t *vec, const uint32_t *slots, int n_slots)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
+  if (n_slots <= 0) return hipSuccess;
+  if (g.sankoff || g.S != 4 || !g.shoff) return hipErrorInvalidValue;
+  const int tiles = (g.Wp + 63) / 64;
+  const long waves = (long)n_slots * tiles;
+  hipLaunchKernelGGL(k_rows_from_wm, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, vec, vec + g.shoff, slots, n_slots, g.Wp, tiles);
+  return hipGetLastError();
+}
+
+hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *vec, const EvOp *ops, int n_ops,
+                           uint32_t *out, bool word_major)
+{
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_ops <= 0) return hipSuccess;
   const int tiles = tiles_of(g);
   const long waves = (long)n_ops * tiles;
@@ -2809,6 +2887,14 @@ hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *ve
     dim3 sgrid((unsigned)(((long)n_ops * stiles + 3) / 4));
     dispatch_snk(g, [&](auto S, auto PK) {
       hipLaunchKernelGGL((k_snk_evaluate<S, PK>), sgrid, block, 0, st, vec, g.moff, ops, n_ops, g.cost, g.pwgt, out, We, stiles);
+    });
+    return hipGetLastError();
+  }
+  if (word_major && g.S == 4 && g.shoff) {         // one word per lane whatever g.vw says
+    const int wtiles = (g.Wp + 63) / 64;
+    dim3 wgrid((unsigned)(((long)n_ops * wtiles + 3) / 4));
+    dispatch_reduce(g, [&](auto RED) {
+      hipLaunchKernelGGL((k_evaluate<4, 1, RED, true>), wgrid, block, 0, st, vec + g.shoff, ops, n_ops, out, g.Wp, wtiles);
     });
     return hipGetLastError();
   }
@@ -2823,6 +2909,7 @@ hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *ve
 hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
                            unsigned long long *out, int vw, bool word_major)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (g.sankoff) return hipErrorInvalidValue;
   const bool wm = word_major && g.S == 4 && g.shoff;
@@ -2847,6 +2934,7 @@ hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *ve
 hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
                                  unsigned long long *out, int vw, bool word_major, uint32_t *plane0, uint32_t *plane1)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (g.sankoff || !plane0 || !plane1) return hipErrorInvalidValue;
   const bool wm = word_major && g.S == 4 && g.shoff;
@@ -2872,6 +2960,7 @@ hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32
 hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
                                unsigned long long *out, bool wide_addr, uint16_t *vals, uint32_t *vmax)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (!g.sankoff || !g.moff || (vals != nullptr) != (vmax != nullptr)) return hipErrorInvalidValue;
   const int We = snk_elems(g), tiles = (We + 63) / 64;
@@ -2893,6 +2982,7 @@ hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t
 hipError_t launch_branch_subst(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                                uint32_t *out, int vw, bool word_major)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (g.sankoff) return hipErrorInvalidValue;
   const bool wm = word_major && g.S == 4 && g.shoff;
@@ -2917,6 +3007,7 @@ hipError_t launch_branch_subst(hipStream_t st, const Geometry &g, const uint32_t
 hipError_t launch_snk_branch_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                                   uint32_t *out, bool wide_addr)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (!g.sankoff || !g.moff) return hipErrorInvalidValue;
   const int We = snk_elems(g), tiles = (We + 63) / 64;
@@ -2934,6 +3025,7 @@ hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, c
                        const ScanOp *ops, uint32_t *out, int max_depth, uint32_t *host_out, uint32_t n_out, uint32_t *done,
                        uint16_t *vals, uint32_t npat, uint32_t *vmax)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_scans <= 0) return hipSuccess;
   const int tiles = tiles_of(g);
   dim3 block(256);
@@ -3004,6 +3096,7 @@ hipError_t launch_scan_walk(hipStream_t st, const Geometry &g, const uint32_t *v
                             const WalkDesc *desc, int n_scans, uint32_t *out, uint32_t *ncand, int max_depth,
                             uint32_t *masks, uint2 *info, uint32_t *host_out, uint32_t n_out, uint32_t *done, bool word_major)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_scans <= 0) return hipSuccess;
   const bool split = g.S >= 20;                                    // protein / 32-state data: states split over the wave halves
   const int tiles = split ? (g.Wp + 31) / 32 : (g.big ? (g.Wp + 63) / 64 : tiles_of(g));    // the 64-bit path is one word per lane
@@ -3051,7 +3144,7 @@ hipError_t launch_scan_walk(hipStream_t st, const Geometry &g, const uint32_t *v
       dispatch_reduce(g, [&](auto RED) {
         if constexpr (!SPLIT) {
           // the vectors from the word-major copy (the caller knows it is current): one 16-byte load per lane and vector
-          if (g.vw == 1 && word_major && g.shoff) return launch(int_c<1>(), RED, bool_c<false>(), bool_c<true>());
+          if (word_major && scan_walk_word_major(g, max_depth)) return launch(int_c<1>(), RED, bool_c<false>(), bool_c<true>());
           if (g.vw != 1) return launch(int_c<2>(), RED, bool_c<false>(), bool_c<false>());
         }
         launch(int_c<1>(), RED, bool_c<false>(), bool_c<false>());
@@ -3151,6 +3244,7 @@ hipError_t launch_scan_prog(hipStream_t st, const Geometry &g, const uint32_t *v
                             const void *prog, uint32_t *out, uint32_t *ncand, uint32_t *host_out, uint32_t n_out, uint32_t *done,
                             unsigned long long *trace, bool word_major)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_scans <= 0) return hipSuccess;
   const int vw = g.big ? 1 : g.vw;
   const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
@@ -3165,7 +3259,7 @@ hipError_t launch_scan_prog(hipStream_t st, const Geometry &g, const uint32_t *v
   auto launch = [&](auto kernel, const uint32_t *v) {
     hipLaunchKernelGGL(kernel, grid, block, 0, st, v, desc, n_scans, pg, out, ncand, g.Wp, tiles, g.map, host_out, n_out, done, trace);
   };
-  const bool wm = word_major && g.shoff && !g.big && vw == 1;
+  const bool wm = word_major && scan_prog_word_major(g);
 #ifdef MPF_EXPERIMENTS                     // (wrong results on purpose: never in the production library)
   static const int expr = getenv("MPF_PROG_EXPERIMENT") ? atoi(getenv("MPF_PROG_EXPERIMENT")) : 0;
   if (expr == 1) launch(k_scan_prog<4, 1, false, 1>, vec);
@@ -3184,6 +3278,7 @@ hipError_t launch_scan_prog(hipStream_t st, const Geometry &g, const uint32_t *v
 hipError_t launch_site_counts(hipStream_t st, const Geometry &g, const uint32_t *vec, const EvOp *ops, int n_ops,
                               uint32_t *planes, const int32_t *ptn_first_site, int n_ptn, uint16_t *ptn_out)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_ops <= 0) return hipSuccess;
   const int tiles = tiles_of(g);
   const int n_chunks = (n_ops + kPlaneChunk - 1) / kPlaneChunk;
@@ -3211,6 +3306,7 @@ size_t site_planes_words(const Geometry &g, int n_ops)
 hipError_t launch_sankoff_pattern(hipStream_t st, const Geometry &g, const uint32_t *vec, uint32_t a, uint32_t b,
                                   uint16_t *ptn_out, uint32_t *vmax)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   const int We = snk_elems(g);
   dim3 grid((We + 255) / 256), block(256);
   dispatch_snk(g, [&](auto S, auto PK) {

@@ -52,7 +52,10 @@ struct Geometry {
   // DNA, below 2 GiB: a second copy of every vector in WORD-major order (the four state words of a 32-site word side by side, 16 B)
   // `shoff` words behind the row-major store.  A CU loads 1 KB of it with ONE buffer_load_dwordx4 per wave at 124-146 GB/s, against
   // 75 GB/s for the four 256-byte row loads (tools/ubench/l1_rate: the load path inside the CU is what bounds the planned scan).
-  // Written by k_pack_tips and k_newview_wgq, read by k_scan_prog while Engine::shadow_ok_ holds.
+  // Written by k_pack_tips, k_newview_wgq and k_newview_chain; current for every valid vector while Engine::shadow_ok_ holds, and
+  // then what the scans, the NNI / branch-length kernels and k_evaluate read.  The refresh kernels' word-major shapes also READ it
+  // and leave the rows of what they write alone: the row-major store of the inner vectors is current only while Engine::rows_ok_
+  // holds (launch_rows_from_wm brings it up to date on demand).  The tips are always current in both layouts.
   size_t shoff = 0;
   // radii above kMaxDepth (k_scan_deep): the scans' per-level up-vectors live in this scratch area (allocated on first use)
   uint32_t *deep_scratch = nullptr;
@@ -67,6 +70,12 @@ struct Geometry {
   int snk16 = 0;                    // weighted mode: two 16-bit costs per lane (v_pk_add_u16 / v_pk_min_u16)
   size_t moff = 0;                  // words from a vector to its min-plus transform m(v) (second half of the vector array)
 };
+
+// The shapes in which launch_scan_prog / launch_scan_walk follow `word_major = true` and read the word-major copy; in every other
+// shape they read rows whatever they are told.  The launchers and the engine (which must bring the rows up to date for a launch
+// that reads them) both decide by these.
+inline bool scan_prog_word_major(const Geometry &g) { return g.S == 4 && g.shoff != 0 && !g.big && g.vw == 1; }
+inline bool scan_walk_word_major(const Geometry &g, int max_depth) { return g.S == 4 && g.shoff != 0 && !g.big && g.vw == 1 && max_depth <= kWalkMaxDepth; }
 
 // ---------------------------------------------------------------- launch dispatch
 // Each helper turns one runtime value into a compile-time constant (std::integral_constant, usable as a template argument) and
@@ -151,7 +160,11 @@ struct RefreshExtra { const uint32_t *kid_upd = nullptr; int n_kid_upd = 0; uint
                       // the refresh leaves idle -- no plan kernel on the critical path
                       const uint2 *wp_kids = nullptr; uint32_t wp_n = 0; const WalkDesc *wp_desc = nullptr; const uint32_t *wp_hdr = nullptr /* {parts, candidates} */;
                       void *wp_prog = nullptr; uint32_t *wp_out = nullptr; uint32_t wp_max_parts = 0;
-                      uint32_t *shadow = nullptr; /* k_newview_wgq: the word-major copy of every vector written (Geometry::shoff) */
+                      uint32_t *shadow = nullptr; /* the word-major copy (Geometry::shoff; set by the launchers): every vector written goes there */
+                      // DNA, one word per lane, the word-major copy current for every valid vector: the refresh reads its operands
+                      // from that copy.  k_newview_wgq then writes no rows at all; k_newview_chain writes them while `rows` is set
+                      // (the rows of every valid vector are current and shall stay so)
+                      int wm_only = 0, rows = 0;
                       int waves_hint = 0; /* launch_newview_levels: waves per workgroup (0 = sixteen); narrow levels need fewer */ };
 // Refresh schedule of a COMPLETE tree made on the device from the topology array alone (kids[cid], cids n .. n + n_ops - 1 are
 // the inner records): ops in level order, lev_off[0 .. n_lev] as launch_newview_levels reads them, *n_lev.  One workgroup;
@@ -194,8 +207,11 @@ hipError_t launch_cntsum(hipStream_t st, const Geometry &g, const NvOp *ops, int
 int tiles_for(const Geometry &g);
 int newview_tile(const Geometry &g);
 int tiles_for_levels(const Geometry &g);      // tiles (rows of cntp) launch_newview_levels uses: 32-word tiles for one word per lane
+// word_major: read DNA from the word-major copy (Geometry::shoff), which the caller knows to be current
 hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *vec, const EvOp *ops, int n_ops,
-                           uint32_t *out);
+                           uint32_t *out, bool word_major = false);
+// rows of the listed vectors (slots[0 .. n_slots)) rewritten from their word-major copies (DNA with a word-major copy only)
+hipError_t launch_rows_from_wm(hipStream_t st, const Geometry &g, uint32_t *vec, const uint32_t *slots, int n_slots);
 // NNI scoring: the two moves of every branch (cids of the subtrees A, B at node1 and C0, C1 at node2; move k swaps A with C_k).
 // out[i] (zeroed by the caller) = steps of move 0 | steps of move 1 << 32, the subtrees' own scores not included.
 // vw = words per lane of the row-major store (1 | 2 | 4, DNA; other alphabets run 1); word_major: read DNA from the word-major

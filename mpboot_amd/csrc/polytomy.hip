@@ -234,6 +234,7 @@ template <class F> static decltype(auto) dispatch_tw(int tw, F &&f)
 hipError_t launch_poly_views(hipStream_t st, const Geometry &g, uint32_t *vec, const PolyItem *items, const PolyOut *outs,
                              const uint32_t *inputs, const int32_t *lev_off, int n_lev, uint32_t *masks, int tile)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_lev <= 0) return hipSuccess;
   if (g.sankoff) {
     const int We = g.snk16 ? g.Wp / 2 : g.Wp;

@@ -729,6 +729,7 @@ hipError_t launch_vals_planes(hipStream_t st, const uint16_t *vals, uint32_t row
 // ------------------------------------------------------------------------------------------------ launchers
 hipError_t launch_join_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const EvOp *ops, int n_ops, uint32_t *masks)
 {
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_ops <= 0) return hipSuccess;
   const int S = g.S;
   hipLaunchKernelGGL(k_join_masks, dim3((g.Wp + 255) / 256, n_ops), dim3(256), 0, st, vec, ops, n_ops, S, g.Wp, masks);

@@ -74,8 +74,8 @@ int Engine::branch_substitutions(int root_taxon, std::vector<NniBranch> &br, std
   HIPCHK(hipMemcpyAsync(d_br_desc_.p, h_br_desc_.p, nb * sizeof(BranchDesc), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(d_br_out_.p, 0, nb * sizeof(uint32_t), st_));
   if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
-  if (sankoff_) HIPCHK(launch_snk_branch_eval(st_, g_, d_vec_, d_br_desc_.p, (int)nb, d_br_out_.p, force_big_ != 0));
-  else HIPCHK(launch_branch_subst(st_, g_, d_vec_, d_br_desc_.p, (int)nb, d_br_out_.p, vw, wm));
+  if (sankoff_) HIPCHK(launch_snk_branch_eval(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_br_out_.p, force_big_ != 0));
+  else HIPCHK(launch_branch_subst(st_, g_, wm ? vec_base() : vec_rows(), d_br_desc_.p, (int)nb, d_br_out_.p, vw, wm));
   if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
   HIPCHK(hipMemcpyAsync(h_br_out_.p, d_br_out_.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
   HIPCHK(hipStreamSynchronize(st_));

@@ -134,7 +134,7 @@ int Engine::climb_prepare(int maxtrav_eff, int total, int i, uint32_t randomMP, 
   h.batch = 0;
   h.start_mp = start_mp;
   std::memcpy(cd_.h_out.p, &h, sizeof(h));
-  p.vec = d_vec_;
+  p.vec = vec_base();                              // (the kernel starts from the tips and rebuilds every vector it reads)
   p.n = (uint32_t)n_;
   p.nslots = (uint32_t)ns;
   p.Wp = (uint32_t)g_.Wp;
@@ -190,7 +190,12 @@ int Engine::climb_prepare(int maxtrav_eff, int total, int i, uint32_t randomMP, 
   HIPCHK(hipMemcpyAsync(cd_.order.p, cd_.h_order.p, (size_t)total * sizeof(uint16_t), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(cd_.out.p, cd_.h_out.p, sizeof(h), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(cd_.gsum.p, 0, gsum_words * sizeof(unsigned long long), st));
-  shadow_ok_ = false;                              // (k_climb rewrites vectors in the row-major store only)
+  // (k_climb starts from the tips and rewrites vectors in the row-major store only: the word-major copy no longer counts.  Where
+  //  the rows of the vectors in place are stale -- a word-major-only refresh came before -- neither layout would be current for a
+  //  launch that gives up and leaves the engine with the vectors it had: they are forgotten here, nothing is converted for a
+  //  kernel that reads none of them)
+  if (!rows_ok_) invalidate_all();
+  shadow_ok_ = false;
   return MPF_OK;
 }
 
@@ -603,7 +608,7 @@ int Engine::grow_segment(const std::vector<int> &perm, uint32_t len0, uint32_t *
   h.rng = rng_.state;
   std::memcpy(gd_.h_out.p, &h, sizeof(h));
   GrowParams p;
-  p.vec = vw == 0 ? d_vec_ + g_.shoff : d_vec_;
+  p.vec = vw == 0 ? vec_base() + g_.shoff : vec_base();      // (the kernel builds every inner vector it reads)
   p.n = (uint32_t)n; p.nslots = (uint32_t)nslots_; p.Wp = (uint32_t)g_.Wp; p.tiles = (uint32_t)tiles;
   p.m0 = m0; p.steps = (uint32_t)steps; p.tie_mode = (uint32_t)tie_mode_; p.len0 = len0;
   p.root_cid = slot(f); p.root_node = node_of(back_[f]);
@@ -633,6 +638,7 @@ int Engine::grow_segment(const std::vector<int> &perm, uint32_t len0, uint32_t *
   }
   HIPCHK(hipMemcpyAsync(gd_.init.p, gd_.h_init.p, (8 * N2 + 3 * (size_t)steps) * sizeof(uint16_t), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemcpyAsync(gd_.out.p, gd_.h_out.p, sizeof(h), hipMemcpyHostToDevice, st_));
+  if (!rows_ok_) invalidate_all();                 // (as climb_prepare: the kernel builds every inner vector it reads)
   shadow_ok_ = false;                              // (k_grow writes vectors in the row-major store only)
   HIPCHK(launch_grow(st_, g_, vw, p));
   HIPCHK(hipMemcpyAsync(gd_.h_out.p, gd_.out.p, out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));

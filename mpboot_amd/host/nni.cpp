@@ -107,10 +107,10 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
   if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
   if (snk_rows) {
     // tracked climb: the same lengths, and the rows _pattern_pars holds when each tree is booked (k_snk_nni_eval_vals)
-    HIPCHK(launch_snk_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, force_big_ != 0, d_nni_vals_.p, d_nni_vmax_.p));
+    HIPCHK(launch_snk_nni_eval(st_, g_, vec_rows(), d_nni_desc_.p, (int)nb, d_nni_out_.p, force_big_ != 0, d_nni_vals_.p, d_nni_vmax_.p));
   } else if (sankoff_) {
     // ParsTree::computeParsimonyBranch(node1->findNeighbor(node2), node1) for both moves of every branch (k_snk_nni_eval)
-    HIPCHK(launch_snk_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, force_big_ != 0));
+    HIPCHK(launch_snk_nni_eval(st_, g_, vec_rows(), d_nni_desc_.p, (int)nb, d_nni_out_.p, force_big_ != 0));
   } else if (masks) {
     // tracked climb: the two bit planes of (h, c_0, c_1) per branch, each padded to the product's row tile
     const size_t rows_p = (size_t)round_up((int)(3 * nb), kUfbRowTile);
@@ -118,14 +118,14 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
     // (the padding rows are multiplied along with the others when a product takes every row: zero, as ufb_current_tree_reps keeps its own)
     for (int bp = 0; bp < 2 && rows_p > 3 * nb; bp++)
       HIPCHK(hipMemsetAsync(d_nni_planes_.p + ((size_t)bp * rows_p + 3 * nb) * (size_t)g_.Wp, 0, (rows_p - 3 * nb) * (size_t)g_.Wp * sizeof(uint32_t), st_));
-    HIPCHK(launch_nni_eval_masks(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm, d_nni_planes_.p, d_nni_planes_.p + rows_p * (size_t)g_.Wp));
+    HIPCHK(launch_nni_eval_masks(st_, g_, wm ? vec_base() : vec_rows(), d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm, d_nni_planes_.p, d_nni_planes_.p + rows_p * (size_t)g_.Wp));
   } else
-    HIPCHK(launch_nni_eval(st_, g_, d_vec_, d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm));
+    HIPCHK(launch_nni_eval(st_, g_, wm ? vec_base() : vec_rows(), d_nni_desc_.p, (int)nb, d_nni_out_.p, vw, wm));
   if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
   if (snk_rows) {
     // row 2 nb: the current tree at the root leaf's edge, the rest of the tree the parent -- what ParsTree::computeParsimony() wrote
     // (parstree.cpp:101-116) and the row whose weighted sum is tree_length() under the caller's StartGuard
-    HIPCHK(launch_sankoff_pattern(st_, g_, d_vec_, slot(back_[start_]), slot(start_), d_nni_vals_.p + 2 * nb * (size_t)g_.Wp, d_nni_vmax_.p));
+    HIPCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(back_[start_]), slot(start_), d_nni_vals_.p + 2 * nb * (size_t)g_.Wp, d_nni_vmax_.p));
     HIPCHK(hipMemcpyAsync(h_nni_vmax_.p, d_nni_vmax_.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
   }
   if (nb) HIPCHK(hipMemcpyAsync(h_nni_out_.p, d_nni_out_.p, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st_));

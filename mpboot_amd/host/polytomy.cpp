@@ -211,7 +211,7 @@ int Engine::polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr
   HIPCHK(hipMemcpyAsync(d_poly_stage_.p, h_poly_stage_.p, bytes, hipMemcpyHostToDevice, st_));
   if (!sankoff_) HIPCHK(d_poly_masks_.reserve((size_t)t.n_rows * (size_t)g_.Wp));
   if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
-  HIPCHK(launch_poly_views(st_, g_, d_vec_, reinterpret_cast<const PolyItem *>(d_poly_stage_.p + o_items),
+  HIPCHK(launch_poly_views(st_, g_, vec_rows(), reinterpret_cast<const PolyItem *>(d_poly_stage_.p + o_items),
                            reinterpret_cast<const PolyOut *>(d_poly_stage_.p + o_outs), reinterpret_cast<const uint32_t *>(d_poly_stage_.p + o_in),
                            reinterpret_cast<const int32_t *>(d_poly_stage_.p + o_lev), n_lev, d_poly_masks_.p, poly_tile_));
   if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
@@ -247,10 +247,10 @@ int Engine::polytomy_parsimony(int n_inner, const int32_t *first, const int32_t 
     HIPCHK(hp.reserve((size_t)g_.Wp));
     HIPCHK(hipMemcpyAsync(d_evops_.p, &op, sizeof(op), hipMemcpyHostToDevice, st_));
     HIPCHK(hipMemsetAsync(d_out(), 0, clear_words(1) * sizeof(uint32_t), st_));
-    HIPCHK(launch_evaluate(st_, g_, d_vec_, d_evops_.p, 1, d_out()));
+    HIPCHK(launch_evaluate(st_, g_, vec_rows(), d_evops_.p, 1, d_out()));
     HIPCHK(hipMemcpyAsync(h_out(), d_out(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
     if (pattern_pars) {
-      HIPCHK(launch_sankoff_pattern(st_, g_, d_vec_, rest, leaf, d_p.p));
+      HIPCHK(launch_sankoff_pattern(st_, g_, vec_rows(), rest, leaf, d_p.p));
       HIPCHK(hipMemcpyAsync(hp.p, d_p.p, (size_t)g_.Wp * sizeof(uint16_t), hipMemcpyDeviceToHost, st_));
     }
     HIPCHK(hipStreamSynchronize(st_));
@@ -330,8 +330,8 @@ int Engine::polytomy_branch_substitutions(int n_inner, const int32_t *first, con
   HIPCHK(hipMemcpyAsync(d_br_desc_.p, h_br_desc_.p, nb * sizeof(BranchDesc), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(d_br_out_.p, 0, nb * sizeof(uint32_t), st_));
   if (timing_) HIPCHK(hipEventRecord(ev2_, st_));
-  if (sankoff_) HIPCHK(launch_snk_branch_eval(st_, g_, d_vec_, d_br_desc_.p, (int)nb, d_br_out_.p, force_big_ != 0));
-  else HIPCHK(launch_branch_subst(st_, g_, d_vec_, d_br_desc_.p, (int)nb, d_br_out_.p, vw, false));
+  if (sankoff_) HIPCHK(launch_snk_branch_eval(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_br_out_.p, force_big_ != 0));
+  else HIPCHK(launch_branch_subst(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_br_out_.p, vw, false));
   if (timing_) HIPCHK(hipEventRecord(ev3_, st_));
   HIPCHK(hipMemcpyAsync(h_br_out_.p, d_br_out_.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
   const size_t rows = (size_t)t.n_rows;

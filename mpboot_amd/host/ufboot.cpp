@@ -426,7 +426,7 @@ int Engine::ufb_current_tree_reps()
   UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
   UCHK(hipMemcpyAsync(d_evops_.p, ops.data(), ops.size() * sizeof(EvOp), hipMemcpyHostToDevice, st_));
   UCHK(hipMemsetAsync(u.jmasks.p + (size_t)rows * g_.Wp, 0, (size_t)(rows_p - rows) * g_.Wp * sizeof(uint32_t), st_));
-  UCHK(launch_join_masks(st_, g_, d_vec_, d_evops_.p, rows, u.jmasks.p));
+  UCHK(launch_join_masks(st_, g_, vec_rows(), d_evops_.p, rows, u.jmasks.p));
   for (int pl = 0; pl < u.planes; pl++)
     UCHK(launch_bitgemm(st_, u.jmasks.p, rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, 1 << (7 * pl), pl > 0));
   UCHK(launch_colsum(st_, u.C.p, rows, u.Bp, u.rt.p));

@@ -113,8 +113,8 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
       const uint32_t n_idx = vals_rows_, R = n_idx;
       UCHK(u.vals.reserve(((size_t)n_idx + 1) * npat));
       UCHK(u.h_vmax.reserve(4));
-      if (asym_) UCHK(launch_sankoff_pattern(st_, g_, d_vec_, slot(back_[start_]), slot(start_), u.vals.p + (size_t)R * npat, u.vmax.p));
-      else UCHK(launch_sankoff_pattern(st_, g_, d_vec_, slot(start_), slot(back_[start_]), u.vals.p + (size_t)R * npat, u.vmax.p));
+      if (asym_) UCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(back_[start_]), slot(start_), u.vals.p + (size_t)R * npat, u.vmax.p));
+      else UCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(start_), slot(back_[start_]), u.vals.p + (size_t)R * npat, u.vmax.p));
       UCHK(hipMemcpyAsync(u.h_vmax.p, u.vmax.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
       UCHK(hipStreamSynchronize(st_));
       int K = 1;

@@ -74,8 +74,8 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
         // ---- the current tree's row, the bit planes, the product
         UCHK(u.vals.reserve(((size_t)n_idx + 1) * npat));
         UCHK(u.h_vmax.reserve(4));
-        if (asym) UCHK(launch_sankoff_pattern(st_, g_, d_vec_, slot(back_[start_]), slot(start_), u.vals.p + (size_t)R * npat, u.vmax.p));     // (left = far end, as tree_length)
-        else UCHK(launch_sankoff_pattern(st_, g_, d_vec_, slot(start_), slot(back_[start_]), u.vals.p + (size_t)R * npat, u.vmax.p));
+        if (asym) UCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(back_[start_]), slot(start_), u.vals.p + (size_t)R * npat, u.vmax.p));     // (left = far end, as tree_length)
+        else UCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(start_), slot(back_[start_]), u.vals.p + (size_t)R * npat, u.vmax.p));
         UCHK(hipMemcpyAsync(u.h_vmax.p, u.vmax.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
         UCHK(hipStreamSynchronize(st_));
         int K = 1;
