@@ -53,9 +53,10 @@ enum {
      MPF_AA      20 states, codes 0..19, B = 20, Z = 21, 22 = undetermined
      MPF_BIN      2 states (PLL_BINARY_DATA), codes 1, 2, 3 = undetermined            (reference Fitch case 2, sprparsimony.cpp:679-721)
      MPF_GENERIC 32 states (PLL_GENERIC_32), codes 0..31, 32 = undetermined           (reference `default` case, :824-869)
-   The binary alphabet runs on the 4-state kernels and multistate data on the 20-state kernels with the unused state rows
-   empty -- Fitch sets never acquire a state no tip has, so lengths, vectors and trajectories are the reference's.  A
-   multistate alignment that uses symbols beyond the 20th (K..V) is refused with MPF_E_UNSUPPORTED. */
+   The binary alphabet runs on the 4-state kernels and multistate data with at most 20 symbols in use on the 20-state kernels
+   with the unused state rows empty -- Fitch sets never acquire a state no tip has, so lengths, vectors and trajectories are the
+   reference's.  A multistate alignment that uses more than 20 symbols, or any multistate alignment under a cost matrix, runs on
+   the 32-state kernels with the reference's own numbering (read-only option "kernel_states" tells which). */
 enum { MPF_DNA = 0, MPF_AA = 1, MPF_BIN = 2, MPF_GENERIC = 3 };
 enum { MPF_TIE_FIRST = 0, MPF_TIE_RANDOM = 1 };
 
@@ -372,6 +373,67 @@ int mpf_polytomy_branch_substitutions(mpf_engine *e, int32_t n_inner, const int3
                                       int32_t *node1, int32_t *node2, uint32_t *subst, int32_t *n);
 int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_sites,
                                 int32_t unit_cost_parstree, int32_t cap, int32_t *node1, int32_t *node2, double *length /* [cap] */, int32_t *n);
+/* The summary of a -bb run: split supports and the bootstrap consensus tree.  The reference weights the booked trees by the samples
+   that point to them (IQTree::summarizeBootstrap, iqtree.cpp:4020-4165), turns every tree into Split objects through its Newick
+   string and counts them in a hash map (MTreeSet::convertSplits, mtreeset.cpp:288-470), and builds the consensus from the counted
+   splits (computeConsensusTree, phyloanalysis.cpp:2488-2600, called at :2263-2267).  Here the trees are taken as the engine holds
+   them -- backs[n_trees][3 (2 n_taxa - 1)], each checked as mpf_set_tree checks it and for being ONE tree over all tips
+   (MPF_E_INVALID) -- and counted on the device (k_split_keys, k_split_insert, k_split_count, k_split_bits).  The results are exact:
+   a 64-bit key only routes a cluster to a table slot, equality is decided on the whole sets, and a true key collision goes through
+   an overflow list that the host resolves by whole-set comparison.
+
+   A split is the set of tips on the side of an inner branch that does not hold tip 1, as ceil(n_taxa / 32) words: bit (t - 1) % 32
+   of word (t - 1) / 32 means tip t.  weights[n_trees]: int32 >= 0 (a negative one: MPF_E_INVALID), NULL = all 1; a tree of weight 0
+   contributes nothing.  Counts and supports are 64-bit; *total_weight = the sum of the weights.  MPF_E_UNSUPPORTED above 2047 taxa
+   (a tree's records, 12 (2 n - 1) bytes, and its walk's stack, 8 n + 16 bytes, are kept in 64 KiB of LDS) and above 2^27
+   clusters, n_trees (n_taxa - 3), in one call.  No current tree is needed, none is changed, an attached tracker books nothing.
+   Test option "split_key_bits" (default 64; 1 .. 63 masks the keys so that they collide), read-only options "split_overflow" (length
+   of the last call's overflow list), "split_launches" and, under "timing", "split_keys_ns" / "split_count_ns" / "split_bits_ns".
+
+   mpf_split_counts (MTreeSet::convertSplits with SW_COUNT): the distinct splits ordered by count descending, then by their words
+   ascending as unsigned, word 0 first -- that order is the contract.  *n_distinct is always the full number; the first
+   min(*n_distinct, cap) rows of bits / count are written (cap = 0: the numbers only, bits and count may be NULL). */
+int mpf_split_counts(mpf_engine *e, int32_t n_trees, const int32_t *backs, const int32_t *weights, int32_t cap,
+                     uint32_t *bits /* [cap][ceil(n_taxa / 32)] */, int64_t *count /* [cap] */, int32_t *n_distinct, int64_t *total_weight);
+/* The supports the reference writes onto the best tree's branches (the assignment behind summarizeBootstrap: PhyloTree's
+   createBootstrapSupport / assignBranchSupport family): for every branch of target_back, in the walk order of
+   mpf_branch_substitutions from root_taxon = 1 (so that the two calls' arrays line up; *n = 2 n_taxa - 3, sizing protocol as there),
+   the summed weight of the trees that hold the branch's split; -1 on a leaf branch.  target_back need not be one of the trees. */
+int mpf_split_support(mpf_engine *e, int32_t n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target_back, int32_t cap,
+                      int32_t *node1, int32_t *node2, int64_t *support, int32_t *n, int64_t *total_weight);
+/* computeConsensusTree: the splits with count <= threshold * total_weight are dropped (mtreeset.cpp:301-312), then
+   SplitGraph::findMaxCompatibleSplits (splitgraph.cpp:615-648): the splits are taken by decreasing count and each one compatible with
+   all kept so far is kept.  threshold = 0 is the greedy consensus the reference writes to .contree; threshold >= 0.5 is the majority
+   rule, which is unique.  Among equal counts the reference takes the order its sort leaves; here it is the contract order of
+   mpf_split_counts.  0 <= threshold <= 1.
+   The tree comes back as the neighbour lists mpf_polytomy_parsimony and mpf_polytomy_branch_lengths take: *n_inner inner nodes
+   (1 .. n_taxa - 2), first[*n_inner + 1] (room for n_taxa - 1), nbr[first[*n_inner]] (room for 3 n_taxa - 6).  Tips are 1 .. n_taxa,
+   inner nodes are numbered n_taxa + 1 .. in pre-order from tip 1, each lists its parent first, then its children by their smallest
+   tip.  support_of_inner[i] (room for n_taxa - 2, may be NULL): the count of the split above inner node i, -1 for the first. */
+int mpf_consensus_tree(mpf_engine *e, int32_t n_trees, const int32_t *backs, const int32_t *weights, double threshold, int32_t *n_inner,
+                       int32_t *first, int32_t *nbr, int64_t *support_of_inner, int64_t *total_weight);
+/* The same three results for the attached UFBoot tracker, trees and weights taken as IQTree::summarizeBootstrap takes them.  rule:
+     MPF_SUMMARY_DEFAULT  tree_weights[boot_trees[b]]++                                          (iqtree.cpp:4036-4038)
+     MPF_SUMMARY_MULHITS  -mulhits: += B / |boot_trees_parsimony[b]| for each tree of sample b   (summarizeBootstrapParsimonyWeight, :4097-4115)
+     MPF_SUMMARY_TOPBOOT  -mulhits -topboot: +1 per tree on a sample's list                      (summarizeBootstrapParsimonyTop, :4117-4130)
+     MPF_SUMMARY_AUTO     the one the tracker's own options select, as the reference does        (:4021-4027)
+   Every field of *s that is a buffer may be NULL with its cap 0: that result is then not made (sizes as in the three calls above).
+   MPF_E_STATE without a tracker, before any sample points to a tree, or for a rule whose lists the tracker does not keep. */
+enum { MPF_SUMMARY_AUTO = -1, MPF_SUMMARY_DEFAULT = 0, MPF_SUMMARY_MULHITS = 1, MPF_SUMMARY_TOPBOOT = 2 };
+typedef struct mpf_bb_summary {
+  /* in */
+  int32_t split_cap;            uint32_t *bits; int64_t *count;                      /* as mpf_split_counts */
+  const int32_t *target_back;   int32_t branch_cap; int32_t *node1, *node2; int64_t *support;   /* as mpf_split_support; NULL target: skipped */
+  double threshold;             int32_t *first, *nbr; int64_t *support_of_inner;     /* as mpf_consensus_tree; NULL first or nbr: skipped */
+  /* out */
+  int32_t n_trees;              /* trees of the tracker with a weight > 0 */
+  int32_t n_distinct, n_branches, n_inner;
+  int64_t total_weight;
+} mpf_bb_summary;
+int mpf_ufboot_summarize(mpf_engine *e, int32_t rule, mpf_bb_summary *s);
+/* ... and the weighted tree set itself: tree_index[cap], weights[cap], backs[cap][3 (2 n_taxa - 1)] (each may be NULL), *n always the
+   full number of trees */
+int mpf_ufboot_summary_trees(mpf_engine *e, int32_t rule, int32_t cap, int64_t *tree_index, int32_t *weights, int32_t *backs, int32_t *n);
 /* The same climb under -bb (save_all_trees == 2), with the UFBoot tracker of mpf_ufboot_attach booking every tree the climb looks
    at through IQTree::saveCurrentTree, in the reference's order: at the start of every step that is not a rollback step the current
    tree with curScore (iqtree.cpp:2181-2183), then for every branch the step evaluates, in evaluation order, the tree after move 0

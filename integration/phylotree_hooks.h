@@ -118,3 +118,20 @@ struct mpf_phylotree_poly_hooks {
   int (*neighbors_n)(const PhyloTree *, int node_id, int *out, int cap);           // ids in neighbors[] order, at most cap; returns the degree
 };
 void mpfitch_phylotree_install_poly(const mpf_phylotree_poly_hooks *hooks);       // NULL (or a table with a NULL entry) uninstalls
+
+// ---- split supports on the host's tree (the summary of a -bb run: IQTree::summarizeBootstrap, iqtree.cpp:4020-4165, and the
+// assignment of the supports to the best tree behind it; INTEGRATION.md "Bootstrap summary").  A further, optional table; nothing
+// above is rerouted.
+//     static void hk_setsup(PhyloTree *t, int id1, int id2, long long support, long long total)
+//         { Node *a = node_of(t, id1), *b = node_of(t, id2); Node *inner = ...the end away from the root...;
+//           inner->name = convertIntToString((int)(100.0 * support / total + 0.5)); }
+//     ... mpfitch_phylotree_install_support(&support_hooks);
+struct mpf_phylotree_support_hooks {
+  // inner branch id1 -- id2 (id1 the end nearer leaf 0) is held by trees of summed weight `support` out of `total_weight`
+  void (*set_support)(PhyloTree *, int id1, int id2, long long support, long long total_weight);
+};
+void mpfitch_phylotree_install_support(const mpf_phylotree_support_hooks *hooks);   // NULL (or a NULL entry) uninstalls
+// The host's (fully resolved) tree is marshalled as computeParsimony() marshals it and handed to mpf_split_support as the target;
+// the weighted tree set comes in the engine's record format (e.g. from mpf_ufboot_summary_trees of the engine that ran the search;
+// weights NULL = all 1).  Every inner branch is reported once through set_support.  Returns the number of inner branches.
+int mpfitch_assign_split_support(PhyloTree *t, int n_trees, const int *backs, const int *weights);

@@ -324,6 +324,39 @@ int mpfitch_fix_negative_branch(PhyloTree *t, int force)
   return fixed;
 }
 
+static mpf_phylotree_support_hooks g_support;
+static bool g_support_installed = false;
+
+void mpfitch_phylotree_install_support(const mpf_phylotree_support_hooks *hooks)
+{
+  g_support_installed = hooks && hooks->set_support;
+  if (g_support_installed) g_support = *hooks;
+}
+
+// the supports summarizeBootstrap's split counts put on the best tree (iqtree.cpp:4020-4165): one mpf_split_support call, the
+// branches in the walk order of mpf_branch_substitutions from leaf 0 (node number = id + 1)
+int mpfitch_assign_split_support(PhyloTree *t, int n_trees, const int *backs, const int *weights)
+{
+  if (!g_support_installed) { std::fprintf(stderr, "mpfitch phylotree shim: mpfitch_phylotree_install_support() was not called\n"); std::exit(EXIT_FAILURE); }
+  const unsigned int *cost = g_h.cost_matrix ? g_h.cost_matrix(t) : nullptr;
+  mpf_engine *e = engine_for(t, cost);
+  const int n = g_h.n_taxa(t);
+  std::vector<int32_t> back;
+  marshal_tree(t, n, back);
+  int32_t m = 2 * n - 3, k = 0;
+  int64_t total = 0;
+  std::vector<int32_t> n1((size_t)m), n2((size_t)m);
+  std::vector<int64_t> sup((size_t)m);
+  if (mpf_split_support(e, n_trees, backs, weights, back.data(), m, n1.data(), n2.data(), sup.data(), &k, &total) || k != m) die("mpf_split_support");
+  int inner = 0;
+  for (int i = 0; i < m; i++)
+    if (sup[(size_t)i] >= 0) {
+      g_support.set_support(t, n1[(size_t)i] - 1, n2[(size_t)i] - 1, (long long)sup[(size_t)i], (long long)total);
+      inner++;
+    }
+  return inner;
+}
+
 void mpfitch_phylotree_install(const mpf_phylotree_hooks *hooks)
 {
   g_h = *hooks;

@@ -265,3 +265,17 @@ def bb_run(eng, samples, start_trees, iters, maxtrav=6, seed=1, engines=None, ve
         out["mean_refined"] = float(np.mean(sc))
         out["samples_improved_by_refinement"] = int((np.asarray(sc) < out["online_scores"]).sum())
     return out
+
+
+def bb_summary(eng, best_tree, threshold=0.0, rule=-1):
+    """The two products of a `-bb` run from the tracker attached to `eng` (IQTree::summarizeBootstrap + computeConsensusTree,
+    iqtree.cpp:4020-4165, phyloanalysis.cpp:2488-2600, :2263-2307): the supports on the branches of best_tree and the bootstrap
+    consensus tree with its parsimony length.  Call it while the tracker is attached (bb_run detaches it at its end).
+
+    -> dict: node1 / node2 / support (the branches of best_tree in the order of branch_substitutions(1); support = the summed weight
+    of the samples' trees that hold the branch's split, -1 on leaf branches), total_weight, consensus = (first, nbr),
+    consensus_support (per inner node), consensus_length (mpf_polytomy_parsimony of the consensus), n_distinct_splits."""
+    s = eng.ufboot_summarize(target=best_tree, threshold=threshold, rule=rule)
+    return {"node1": s["node1"], "node2": s["node2"], "support": s["support"], "total_weight": s["total_weight"],
+            "consensus": (s["first"], s["nbr"]), "consensus_support": s["support_of_inner"],
+            "consensus_length": eng.polytomy_parsimony(s["first"], s["nbr"]), "n_distinct_splits": len(s["count"])}

@@ -425,6 +425,130 @@ int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *f
   return MPF_OK;
 }
 
+// ---- the summary of a -bb run (host/splits.cpp): MTreeSet::convertSplits, the supports on a tree, computeConsensusTree
+static int split_counts_out(const mpf::splitsets::SplitTable &t, int32_t cap, uint32_t *bits, int64_t *count, int32_t *n_distinct)
+{
+  if (n_distinct) *n_distinct = (int32_t)t.size();
+  const size_t m = std::min<size_t>(t.size(), cap > 0 ? (size_t)cap : 0);
+  if (m && (!bits || !count)) { set_error("null output"); return MPF_E_INVALID; }
+  if (m) {
+    std::memcpy(bits, t.bits.data(), m * (size_t)t.words * sizeof(uint32_t));
+    std::memcpy(count, t.count.data(), m * sizeof(int64_t));
+  }
+  return MPF_OK;
+}
+
+static int consensus_out(const mpf::splitsets::ListTree &t, int32_t *n_inner, int32_t *first, int32_t *nbr, int64_t *support_of_inner)
+{
+  if (!n_inner || !first || !nbr) { set_error("null output"); return MPF_E_INVALID; }
+  *n_inner = t.n_inner();
+  std::copy(t.first.begin(), t.first.end(), first);
+  std::copy(t.nbr.begin(), t.nbr.end(), nbr);
+  if (support_of_inner) std::copy(t.support.begin(), t.support.end(), support_of_inner);
+  return MPF_OK;
+}
+
+int mpf_split_counts(mpf_engine *e, int32_t n_trees, const int32_t *backs, const int32_t *weights, int32_t cap, uint32_t *bits, int64_t *count,
+                     int32_t *n_distinct, int64_t *total_weight)
+{
+  NEED(e);
+  if (!n_distinct) { set_error("null output"); return MPF_E_INVALID; }
+  mpf::splitsets::SplitTable t;
+  const int rc = e->eng.split_counts(n_trees, backs, weights, t);
+  if (rc) return rc;
+  if (total_weight) *total_weight = t.total;
+  return split_counts_out(t, cap, bits, count, n_distinct);
+}
+
+int mpf_split_support(mpf_engine *e, int32_t n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target_back, int32_t cap,
+                      int32_t *node1, int32_t *node2, int64_t *support, int32_t *n, int64_t *total_weight)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<int64_t> sup;
+  const int rc = e->eng.split_support(n_trees, backs, weights, target_back, br, sup, total_weight);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !support)) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    support[i] = sup[i];
+  }
+  return MPF_OK;
+}
+
+int mpf_consensus_tree(mpf_engine *e, int32_t n_trees, const int32_t *backs, const int32_t *weights, double threshold, int32_t *n_inner,
+                       int32_t *first, int32_t *nbr, int64_t *support_of_inner, int64_t *total_weight)
+{
+  NEED(e);
+  mpf::splitsets::ListTree t;
+  const int rc = e->eng.consensus_tree(n_trees, backs, weights, threshold, t, total_weight);
+  if (rc) return rc;
+  return consensus_out(t, n_inner, first, nbr, support_of_inner);
+}
+
+int mpf_ufboot_summary_trees(mpf_engine *e, int32_t rule, int32_t cap, int64_t *tree_index, int32_t *weights, int32_t *backs, int32_t *n)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<int32_t> bk, w;
+  std::vector<int64_t> idx;
+  const int rc = e->eng.ufboot_summary_trees(rule, bk, w, idx);
+  if (rc) return rc;
+  *n = (int32_t)idx.size();
+  if (cap < *n) return MPF_OK;
+  if (tree_index) std::copy(idx.begin(), idx.end(), tree_index);
+  if (weights) std::copy(w.begin(), w.end(), weights);
+  if (backs) std::copy(bk.begin(), bk.end(), backs);
+  return MPF_OK;
+}
+
+int mpf_ufboot_summarize(mpf_engine *e, int32_t rule, mpf_bb_summary *s)
+{
+  NEED(e);
+  if (!s) { set_error("null argument"); return MPF_E_INVALID; }
+  std::vector<int32_t> bk, w;
+  std::vector<int64_t> idx;
+  int rc = e->eng.ufboot_summary_trees(rule, bk, w, idx);
+  if (rc) return rc;
+  const int32_t T = (int32_t)idx.size();
+  s->n_trees = T;
+  s->n_distinct = s->n_branches = s->n_inner = 0;
+  s->total_weight = 0;
+  for (int32_t x : w) s->total_weight += x;
+  {
+    mpf::splitsets::SplitTable t;
+    rc = e->eng.split_counts(T, bk.data(), w.data(), t);
+    if (rc) return rc;
+    rc = split_counts_out(t, s->bits && s->count ? s->split_cap : 0, s->bits, s->count, &s->n_distinct);
+    if (rc) return rc;
+  }
+  if (s->target_back) {
+    std::vector<mpf::Engine::NniBranch> br;
+    std::vector<int64_t> sup;
+    rc = e->eng.split_support(T, bk.data(), w.data(), s->target_back, br, sup, nullptr);
+    if (rc) return rc;
+    s->n_branches = (int32_t)br.size();
+    if (s->branch_cap >= s->n_branches && s->node1 && s->node2 && s->support)
+      for (size_t i = 0; i < br.size(); i++) {
+        s->node1[i] = br[i].node1;
+        s->node2[i] = br[i].node2;
+        s->support[i] = sup[i];
+      }
+  }
+  if (s->first && s->nbr) {
+    mpf::splitsets::ListTree t;
+    rc = e->eng.consensus_tree(T, bk.data(), w.data(), s->threshold, t, nullptr);
+    if (rc) return rc;
+    rc = consensus_out(t, &s->n_inner, s->first, s->nbr, s->support_of_inner);
+    if (rc) return rc;
+  }
+  return MPF_OK;
+}
+
 // mpf_nni_scores by the mask-writing kernel of the tracked climb, its rows per pattern
 int mpf_nni_pattern_terms(mpf_engine *e, int32_t root_taxon, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *len, uint8_t *terms, int32_t *n)
 {

@@ -25,9 +25,11 @@
 #include "../../include/mpfitch.h"
 #include "../host/rng.hpp"
 #include "../host/ufb_books.hpp"
+#include "../host/split_sets.hpp"
 #include "climb.hpp"
 #include "kernels.hpp"
 #include "ufboot.hpp"
+#include "splits.hpp"
 
 namespace mpf {
 
@@ -348,6 +350,15 @@ class Engine {
   int polytomy_branch_substitutions(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, std::vector<NniBranch> &br,
                                     std::vector<uint32_t> &subst, uint32_t *fitch_len = nullptr);
 
+  // ---- the summary of a -bb run (host/splits.cpp, splits.hip; reference IQTree::summarizeBootstrap, MTreeSet::convertSplits,
+  // computeConsensusTree): the splits of a weighted set of complete trees counted exactly on the device, the supports of a target
+  // tree's branches, the consensus tree as neighbour lists.  Stateless towards the engine's own tree and its vectors
+  int split_counts(int n_trees, const int32_t *backs, const int32_t *weights, splitsets::SplitTable &out);
+  int split_support(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, std::vector<NniBranch> &br,
+                    std::vector<int64_t> &support, int64_t *total);
+  int consensus_tree(int n_trees, const int32_t *backs, const int32_t *weights, double threshold, splitsets::ListTree &out, int64_t *total);
+  int ufboot_summary_trees(int rule, std::vector<int32_t> &backs, std::vector<int32_t> &weights, std::vector<int64_t> &index);
+
   // ---- online UFBoot-MP bookkeeping (host/ufboot.cpp; reference IQTree::saveCurrentTree, iqtree.cpp:3271-3785)
   int ufboot_attach(int n_samples, const uint16_t *samples, double epsilon, int n_local = -1, const int32_t *sample_ids = nullptr,
                     mpf_ufb_exchange_fn exchange = nullptr, void *exchange_arg = nullptr);
@@ -544,6 +555,27 @@ class Engine {
   DevBuf<uint32_t> d_br_out_;
   PinBuf<uint32_t> h_br_out_;
 
+  // the bootstrap summary: option "split_key_bits" (tests: 1 .. 63 masks the cluster keys so that they collide and the overflow
+  // list carries the result; default 64), read-only options split_overflow (length of the last call's overflow list),
+  // split_launches and, under "timing", split_keys_ns / split_count_ns / split_bits_ns (HIP-event time of k_split_keys, of
+  // insert + count + compact + gather, of k_split_bits)
+  struct SplitRun { splitsets::SplitTable table; splitsets::TreeClusters target; std::vector<int64_t> target_support; } split_run_;
+  int split_run(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, bool want_sets, double threshold, SplitRun &r);
+  struct SplitBufs {
+    PinBuf<int32_t> h_backs, h_flags;
+    DevBuf<int32_t> backs, pos, order, flags, w;
+    DevBuf<SplitCluster> cl;
+    DevBuf<unsigned long long> table;              // keys | representatives | counts
+    DevBuf<uint32_t> slot_of, ovf, counters, ids, bits;
+    DevBuf<SplitEntry> entries;
+    PinBuf<SplitEntry> h_entries;
+    PinBuf<uint32_t> h_ids, h_bits;
+    DevBuf<long long> tsup;
+    PinBuf<long long> h_tsup;
+  } split_;
+  std::vector<int32_t> split_hw_, split_pick_;
+  int split_key_bits_ = 64;
+  uint64_t split_overflow_ = 0, split_launches_ = 0, split_keys_ns_ = 0, split_count_ns_ = 0, split_bits_ns_ = 0;
   // multifurcating trees: the rooted shape of the tree handed over and the items of its view launch; option "poly_tile" (0 = from
   // the row length, 4 | 8 | 16 | 32 words per workgroup), read-only options poly_launches / poly_views (directed views written) and,
   // under "timing", poly_view_ns / poly_branch_ns (HIP-event time of the view launch / of the branch launch)

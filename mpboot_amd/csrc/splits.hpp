@@ -1,0 +1,34 @@
+// splits.hpp -- launchers of splits.hip: the bipartitions of a set of complete trees, counted exactly on the device.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace mpf {
+
+// a cluster of a tree: the tips whose DFS position lies in [lo, hi), and the wrapping sum of their per-taxon constants
+struct SplitCluster { uint32_t lo, hi; unsigned long long key; };
+// a used slot of the table: its representative cluster (the smallest cluster number that claimed it) and the summed weight of the
+// clusters that ARE that set
+struct SplitEntry { uint32_t rep, slot; unsigned long long count; };
+
+constexpr unsigned long long kSplitEmpty = ~0ull;        // an unclaimed key / representative
+constexpr uint32_t kSplitNoSlot = 0xFFFFFFFFu;           // slot_of[] of a cluster that went to the overflow list
+// k_split_keys keeps a tree's records (3 (2n - 1) words) and its walk's stack (2n + 4 words) in LDS: 32 n + 4 bytes.  Within the
+// 64 KiB a workgroup gets without asking for more that is n <= 2047
+constexpr int kSplitMaxTaxa = 2047;
+inline size_t split_keys_lds_bytes(int n) { return sizeof(int32_t) * ((size_t)3 * (2 * (size_t)n - 1) + 2 * (size_t)n + 4); }
+
+hipError_t launch_split_keys(hipStream_t st, const int32_t *backs, int n_trees, int n, int key_bits, int32_t *pos, int32_t *order,
+                             SplitCluster *cl, int32_t *bad);
+hipError_t launch_split_insert(hipStream_t st, const SplitCluster *cl, uint32_t n_clusters, unsigned long long *tkey, unsigned long long *trep,
+                               uint32_t tsize, uint32_t *slot_of);
+hipError_t launch_split_count(hipStream_t st, const SplitCluster *cl, uint32_t n_clusters, int n, const int32_t *pos, const int32_t *order,
+                              const unsigned long long *trep, uint32_t *slot_of, const int32_t *weights, unsigned long long *tcount,
+                              uint32_t *ovf, uint32_t *counters);
+hipError_t launch_split_compact(hipStream_t st, const unsigned long long *trep, const unsigned long long *tcount, uint32_t tsize, SplitEntry *out,
+                                uint32_t *counters);
+hipError_t launch_split_gather(hipStream_t st, const uint32_t *slot_of, uint32_t first, uint32_t m, const unsigned long long *tcount, long long *out);
+hipError_t launch_split_bits(hipStream_t st, const SplitCluster *cl, const uint32_t *ids, uint32_t m, int n, const int32_t *pos, uint32_t *bits);
+
+}  // namespace mpf

@@ -37,6 +37,7 @@ EXPORTS = [
     "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves", "mpf_ufboot_optimize_nni", "mpf_nni_pattern_terms", "mpf_nni_pattern_lengths",
     "mpf_branch_substitutions", "mpf_branch_lengths",
     "mpf_polytomy_parsimony", "mpf_polytomy_branch_substitutions", "mpf_polytomy_branch_lengths",
+    "mpf_split_counts", "mpf_split_support", "mpf_consensus_tree", "mpf_ufboot_summarize", "mpf_ufboot_summary_trees",
 ]
 
 
@@ -75,6 +76,18 @@ class Stats(C.Structure):
 
 
 _lib = None
+
+
+class BbSummary(C.Structure):
+    """mpf_bb_summary (include/mpfitch.h)"""
+    _fields_ = [("split_cap", C.c_int32), ("bits", C.c_void_p), ("count", C.c_void_p),
+                ("target_back", C.c_void_p), ("branch_cap", C.c_int32), ("node1", C.c_void_p), ("node2", C.c_void_p), ("support", C.c_void_p),
+                ("threshold", C.c_double), ("first", C.c_void_p), ("nbr", C.c_void_p), ("support_of_inner", C.c_void_p),
+                ("n_trees", C.c_int32), ("n_distinct", C.c_int32), ("n_branches", C.c_int32), ("n_inner", C.c_int32),
+                ("total_weight", C.c_int64)]
+
+
+SUMMARY_AUTO, SUMMARY_DEFAULT, SUMMARY_MULHITS, SUMMARY_TOPBOOT = -1, 0, 1, 2
 
 
 def load_library():
@@ -178,6 +191,11 @@ def load_library():
         L.mpf_polytomy_parsimony.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
         L.mpf_polytomy_branch_substitutions.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.mpf_polytomy_branch_lengths.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.mpf_split_counts.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]
+        L.mpf_split_support.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.mpf_consensus_tree.argtypes = [vp, C.c_int32, vp, vp, C.c_double, vp, vp, vp, vp, vp]
+        L.mpf_ufboot_summarize.argtypes = [vp, C.c_int32, C.POINTER(BbSummary)]
+        L.mpf_ufboot_summary_trees.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -664,6 +682,98 @@ class FitchEngine:
                                                         _p(a), _p(b), _p(ln), C.byref(n)))
         assert n.value == m
         return a[:m], b[:m], ln[:m]
+
+    # ---- the summary of a -bb run: split counts, supports on a tree, consensus tree (host/splits.cpp, splits.hip)
+    def _tree_set(self, backs, weights):
+        b = np.ascontiguousarray(backs, dtype=np.int32).reshape(-1, 3 * (2 * self.n - 1))
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32)
+        assert w is None or len(w) == len(b)
+        return b, w
+
+    def split_counts(self, backs, weights=None, counts_only: bool = False):
+        """The distinct non-trivial splits of the trees backs[T][3 (2n - 1)] with the summed weights of the trees that hold them
+        (weights int32 >= 0, None = all 1): (bits[D][ceil(n / 32)] uint32, count[D] int64, total_weight), ordered by count
+        descending, then by the words ascending.  Bit (t - 1) % 32 of word (t - 1) / 32 = tip t is on the side without tip 1.
+        counts_only: (D, total_weight).  Exact: counted on the device, sets compared as whole sets."""
+        b, w = self._tree_set(backs, weights)
+        nd, tot = C.c_int32(), C.c_int64()
+        L = load_library()
+        _chk(L.mpf_split_counts(self.h, len(b), _p(b), None if w is None else _p(w), 0, None, None, C.byref(nd), C.byref(tot)))
+        if counts_only:
+            return int(nd.value), int(tot.value)
+        D, words = int(nd.value), (self.n + 31) // 32
+        bits = np.zeros((max(D, 1), words), dtype=np.uint32)
+        cnt = np.zeros(max(D, 1), dtype=np.int64)
+        _chk(L.mpf_split_counts(self.h, len(b), _p(b), None if w is None else _p(w), D, _p(bits), _p(cnt), C.byref(nd), C.byref(tot)))
+        assert nd.value == D
+        return bits[:D], cnt[:D], int(tot.value)
+
+    def split_support(self, backs, target, weights=None):
+        """(node1[m], node2[m], support[m] int64, total_weight) for the m = 2 n - 3 branches of `target` in the order of
+        branch_substitutions(root_taxon=1): the summed weight of the trees that hold the branch's split, -1 on a leaf branch"""
+        b, w = self._tree_set(backs, weights)
+        t = np.ascontiguousarray(target, dtype=np.int32)
+        m = 2 * self.n - 3
+        n, tot = C.c_int32(), C.c_int64()
+        a, c, s = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+        _chk(load_library().mpf_split_support(self.h, len(b), _p(b), None if w is None else _p(w), _p(t), m, _p(a), _p(c), _p(s), C.byref(n),
+                                              C.byref(tot)))
+        assert n.value == m
+        return a, c, s, int(tot.value)
+
+    def consensus_tree(self, backs, weights=None, threshold: float = 0.0):
+        """The reference's consensus of the weighted trees: splits with count <= threshold * total dropped, then the greedy maximal
+        compatible set (threshold 0: the greedy consensus of .contree; >= 0.5: majority rule).  -> (first, nbr, support_of_inner,
+        total_weight): the neighbour lists polytomy_parsimony / polytomy_branch_lengths take, inner nodes in pre-order from tip 1,
+        support_of_inner[i] = the count of the split above inner node n + 1 + i (-1 for the first)."""
+        b, w = self._tree_set(backs, weights)
+        n = self.n
+        ni, tot = C.c_int32(), C.c_int64()
+        first, nbr, sup = np.zeros(n - 1, dtype=np.int32), np.zeros(3 * n - 6, dtype=np.int32), np.zeros(n - 2, dtype=np.int64)
+        _chk(load_library().mpf_consensus_tree(self.h, len(b), _p(b), None if w is None else _p(w), float(threshold), C.byref(ni), _p(first),
+                                               _p(nbr), _p(sup), C.byref(tot)))
+        k = int(ni.value)
+        return first[:k + 1].copy(), nbr[:int(first[k])].copy(), sup[:k].copy(), int(tot.value)
+
+    def ufboot_summary_trees(self, rule: int = SUMMARY_AUTO):
+        """(tree_index[T] int64, weights[T] int32, backs[T][3 (2n - 1)]): the weighted tree set IQTree::summarizeBootstrap makes of the
+        attached tracker under `rule` (SUMMARY_*)"""
+        L = load_library()
+        n = C.c_int32()
+        _chk(L.mpf_ufboot_summary_trees(self.h, rule, 0, None, None, None, C.byref(n)))
+        T = int(n.value)
+        idx, w = np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int32)
+        b = np.zeros((T, 3 * (2 * self.n - 1)), dtype=np.int32)
+        _chk(L.mpf_ufboot_summary_trees(self.h, rule, T, _p(idx), _p(w), _p(b), C.byref(n)))
+        return idx, w, b
+
+    def ufboot_summarize(self, target=None, threshold: float = 0.0, rule: int = SUMMARY_AUTO):
+        """split_counts, split_support (if a target tree is given) and consensus_tree of the attached tracker's trees, weighted as
+        the reference weights them (rule: SUMMARY_AUTO = by the tracker's own options, SUMMARY_DEFAULT, SUMMARY_MULHITS,
+        SUMMARY_TOPBOOT) -> dict"""
+        L = load_library()
+        n, words = self.n, (self.n + 31) // 32
+        s = BbSummary()
+        s.threshold = float(threshold)
+        _chk(L.mpf_ufboot_summarize(self.h, rule, C.byref(s)))          # sizes first
+        D = int(s.n_distinct)
+        bits, cnt = np.zeros((max(D, 1), words), dtype=np.uint32), np.zeros(max(D, 1), dtype=np.int64)
+        m = 2 * n - 3
+        a, c, sup = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+        first, nbr, isup = np.zeros(n - 1, dtype=np.int32), np.zeros(3 * n - 6, dtype=np.int32), np.zeros(n - 2, dtype=np.int64)
+        t = None if target is None else np.ascontiguousarray(target, dtype=np.int32)
+        s.split_cap, s.bits, s.count = D, bits.ctypes.data, cnt.ctypes.data
+        if t is not None:
+            s.target_back, s.branch_cap, s.node1, s.node2, s.support = t.ctypes.data, m, a.ctypes.data, c.ctypes.data, sup.ctypes.data
+        s.first, s.nbr, s.support_of_inner = first.ctypes.data, nbr.ctypes.data, isup.ctypes.data
+        _chk(L.mpf_ufboot_summarize(self.h, rule, C.byref(s)))
+        assert s.n_distinct == D
+        k = int(s.n_inner)
+        out = {"bits": bits[:D], "count": cnt[:D], "total_weight": int(s.total_weight), "n_trees": int(s.n_trees),
+               "first": first[:k + 1].copy(), "nbr": nbr[:int(first[k])].copy(), "support_of_inner": isup[:k].copy()}
+        if t is not None:
+            out.update(node1=a, node2=c, support=sup)
+        return out
 
     def nni_pattern_terms(self, root_taxon: int = 1):
         """nni_scores by the mask-writing kernel of the tracked climb: (node1[m], node2[m], len[m][2], terms[m][3][n_patterns]);

@@ -1,0 +1,283 @@
+// split_sets.hpp -- the host-only part of the bootstrap summary (host/splits.cpp): no device code, no engine, so that it can be
+// compiled into a stand-alone program and run under a sanitizer (host/splits_host_main.cpp, tests/test_splits_host.py).
+//
+// A split is the set of tips on the side of an inner branch that does NOT hold tip 1 (the normal form of trees.splits), kept as
+// words = ceil(n / 32) 32-bit words: bit (t - 1) % 32 of word (t - 1) / 32 means tip t is in the set.  Sets are always compared
+// as whole sets; the hash of SetIndex only picks a bucket.
+//
+//   walk_clusters     the walk of k_split_keys restated: DFS from tip 1, every inner branch an interval [lo, hi) of DFS positions
+//   SetIndex          exact set -> index map (the overflow list of k_split_count is resolved through it; so is count_splits)
+//   count_splits      the whole summary on the host (the CPU yardstick of tools/splits_timing.py)
+//   order_splits      the contract order: count descending, then the words ascending as unsigned, word 0 first
+//   greedy_compatible SplitGraph::findMaxCompatibleSplits (reference splitgraph.cpp:615-648): walk the splits in that order and
+//                     keep each one that is compatible with all kept so far; at most n - 3 non-trivial ones fit a tree
+//   build_lists       the kept (pairwise compatible) sets as the CSR neighbour lists mpf_polytomy_* takes
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <numeric>
+#include <unordered_map>
+#include <vector>
+
+namespace mpf {
+namespace splitsets {
+
+inline int words_of(int n) { return (n + 31) / 32; }
+
+// the engine's record convention: rec = 3 * node + slot, the ring of an inner node
+inline int nxt(int r) { const int v = r / 3, s = r % 3; return 3 * v + (s + 1) % 3; }
+
+// mpf_set_tree's check of a complete tree on n taxa: every record of tips 1 .. n and inner nodes n + 1 .. 2n - 2 linked both ways
+inline bool links_ok(const int32_t *back, int n)
+{
+  const int len = 3 * (2 * n - 1);
+  for (int v = 1; v <= 2 * n - 2; v++)
+    for (int s = 0; s < (v <= n ? 1 : 3); s++) {
+      const int r = 3 * v + s, b = back[r];
+      if (b < 3 || b >= len || back[b] != r) return false;
+    }
+  return true;
+}
+
+struct TreeClusters {
+  std::vector<int32_t> pos;     // [n]      DFS position of tip t at pos[t - 1]; tip 1 gets n - 1, outside every interval
+  std::vector<int32_t> order;   // [n - 1]  the tip at each DFS position
+  std::vector<int32_t> lo, hi;  // [n - 3]  cluster ci = the tips with lo <= pos < hi, ci in pre-order of the inner nodes
+  std::vector<int32_t> node;    // [n - 3]  the inner node below the branch (the end away from tip 1)
+};
+
+// The walk of k_split_keys, step for step: an explicit stack of records, a negative entry closes cluster -(x + 1).  The inner
+// node next to tip 1 holds every other tip and is no split; it is entered first and gets no cluster.  false: the records do not
+// form ONE tree over all n tips (the counts run over or fall short)
+inline bool walk_clusters(const int32_t *back, int n, TreeClusters &c)
+{
+  const int C = n - 3;
+  c.pos.assign((size_t)n, 0);
+  c.order.assign((size_t)std::max(n - 1, 0), 0);
+  c.lo.assign((size_t)std::max(C, 0), 0);
+  c.hi.assign((size_t)std::max(C, 0), 0);
+  c.node.assign((size_t)std::max(C, 0), 0);
+  std::vector<int32_t> st;
+  st.reserve((size_t)2 * n + 4);
+  st.push_back(back[3]);
+  int cnt = 0, inner = 0;
+  while (!st.empty()) {
+    const int x = st.back();
+    st.pop_back();
+    if (x < 0) { c.hi[(size_t)(-x - 1)] = cnt; continue; }
+    const int v = x / 3;
+    if (v <= n) {
+      if (v == 1 || cnt >= n - 1) return false;
+      c.pos[(size_t)v - 1] = cnt;
+      c.order[(size_t)cnt++] = v;
+      continue;
+    }
+    if (inner >= n - 2) return false;
+    const int ci = inner++ - 1;
+    if (ci >= 0) {
+      c.lo[(size_t)ci] = cnt;
+      c.node[(size_t)ci] = v;
+      st.push_back(-(ci + 1));
+    }
+    st.push_back(back[nxt(nxt(x))]);
+    st.push_back(back[nxt(x)]);
+  }
+  c.pos[0] = n - 1;
+  return cnt == n - 1 && inner == n - 2;
+}
+
+inline void cluster_bits(const TreeClusters &c, int ci, int words, uint32_t *out)
+{
+  std::fill(out, out + words, 0u);
+  for (int p = c.lo[(size_t)ci]; p < c.hi[(size_t)ci]; p++) {
+    const int t = c.order[(size_t)p] - 1;
+    out[t >> 5] |= 1u << (t & 31);
+  }
+}
+
+// exact map from a set to its index in a table of sets kept by the caller; the hash routes, equality is word by word
+class SetIndex {
+ public:
+  explicit SetIndex(int words) : words_(words) {}
+  static uint64_t hash(const uint32_t *w, int words)
+  {
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    for (int i = 0; i < words; i++) { h ^= w[i]; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 29; }
+    return h;
+  }
+  // index of `w` in table (rows of `words` words), or -1
+  int64_t find(const std::vector<uint32_t> &table, const uint32_t *w) const
+  {
+    auto rg = map_.equal_range(hash(w, words_));
+    for (auto it = rg.first; it != rg.second; ++it)
+      if (!std::memcmp(table.data() + (size_t)it->second * (size_t)words_, w, (size_t)words_ * sizeof(uint32_t))) return it->second;
+    return -1;
+  }
+  void insert(const uint32_t *w, int64_t index) { map_.emplace(hash(w, words_), index); }
+  void reserve(size_t k) { map_.reserve(k); }
+
+ private:
+  int words_;
+  std::unordered_multimap<uint64_t, int64_t> map_;
+};
+
+struct SplitTable {
+  int n = 0, words = 0;
+  int64_t total = 0;
+  std::vector<uint32_t> bits;    // [count.size()][words]
+  std::vector<int64_t> count;
+  size_t size() const { return count.size(); }
+  const uint32_t *row(size_t i) const { return bits.data() + i * (size_t)words; }
+};
+
+// MTreeSet::convertSplits (reference mtreeset.cpp:288-470) without the strings: every tree's splits into one table, weighted.
+// weights may be null (all 1); a tree of weight 0 contributes nothing.  false: a tree is not a complete tree on n taxa
+inline bool count_splits(int n, int n_trees, const int32_t *backs, const int32_t *weights, SplitTable &out)
+{
+  const size_t len = 3 * (size_t)(2 * n - 1);
+  out.n = n;
+  out.words = words_of(n);
+  out.total = 0;
+  out.bits.clear();
+  out.count.clear();
+  SetIndex idx(out.words);
+  TreeClusters c;
+  std::vector<uint32_t> w((size_t)out.words);
+  for (int t = 0; t < n_trees; t++) {
+    const int64_t wt = weights ? weights[t] : 1;
+    const int32_t *back = backs + (size_t)t * len;
+    if (!links_ok(back, n) || !walk_clusters(back, n, c)) return false;
+    if (wt == 0) continue;
+    out.total += wt;
+    for (int ci = 0; ci < n - 3; ci++) {
+      cluster_bits(c, ci, out.words, w.data());
+      int64_t k = idx.find(out.bits, w.data());
+      if (k < 0) {
+        k = (int64_t)out.count.size();
+        out.bits.insert(out.bits.end(), w.begin(), w.end());
+        out.count.push_back(0);
+        idx.insert(w.data(), k);
+      }
+      out.count[(size_t)k] += wt;
+    }
+  }
+  return true;
+}
+
+// the contract order: count descending, then the set's words ascending as unsigned, word 0 first
+inline std::vector<int64_t> order_splits(const SplitTable &t)
+{
+  std::vector<int64_t> p(t.size());
+  std::iota(p.begin(), p.end(), (int64_t)0);
+  std::sort(p.begin(), p.end(), [&](int64_t a, int64_t b) {
+    if (t.count[(size_t)a] != t.count[(size_t)b]) return t.count[(size_t)a] > t.count[(size_t)b];
+    const uint32_t *x = t.row((size_t)a), *y = t.row((size_t)b);
+    for (int i = 0; i < t.words; i++)
+      if (x[i] != y[i]) return x[i] < y[i];
+    return false;
+  });
+  return p;
+}
+
+inline void apply_order(SplitTable &t, const std::vector<int64_t> &p)
+{
+  std::vector<uint32_t> b(t.bits.size());
+  std::vector<int64_t> c(t.count.size());
+  for (size_t i = 0; i < p.size(); i++) {
+    std::copy(t.row((size_t)p[i]), t.row((size_t)p[i]) + t.words, b.begin() + (long)(i * (size_t)t.words));
+    c[i] = t.count[(size_t)p[i]];
+  }
+  t.bits.swap(b);
+  t.count.swap(c);
+}
+
+// both sets leave tip 1 out, so their complements always meet: two splits fit one tree iff the sets are disjoint or nested
+// (Split::compatible, reference split.cpp:170-193, with the fourth intersection never empty)
+inline bool compatible(const uint32_t *a, const uint32_t *b, int words)
+{
+  uint32_t both = 0, a_only = 0, b_only = 0;
+  for (int i = 0; i < words; i++) {
+    both |= a[i] & b[i];
+    a_only |= a[i] & ~b[i];
+    b_only |= b[i] & ~a[i];
+  }
+  return !both || !a_only || !b_only;
+}
+
+// the reference's consensus rule on a table in the contract order: drop count <= threshold * total (mtreeset.cpp:301-312), then
+// findMaxCompatibleSplits.  Returns the kept rows, in table order
+inline std::vector<int64_t> greedy_compatible(const SplitTable &t, double threshold)
+{
+  std::vector<int64_t> kept;
+  const double cut = threshold * (double)t.total;
+  const size_t max_splits = t.n >= 3 ? (size_t)(t.n - 3) : 0;
+  for (size_t i = 0; i < t.size() && kept.size() < max_splits; i++) {
+    if ((double)t.count[i] <= cut) continue;
+    bool ok = true;
+    for (size_t k = 0; k < kept.size() && ok; k++) ok = compatible(t.row(i), t.row((size_t)kept[k]), t.words);
+    if (ok) kept.push_back((int64_t)i);
+  }
+  return kept;
+}
+
+struct ListTree {
+  std::vector<int32_t> first, nbr;
+  std::vector<int64_t> support;      // the count of the split above each inner node, -1 for the first (it hangs on tip 1)
+  int n_inner() const { return (int)first.size() - 1; }
+};
+
+// Tips 1 .. n; inner nodes n + 1 .. in pre-order from tip 1; each inner node lists its parent first, then its children by their
+// smallest tip.  The kept sets are pairwise disjoint or nested, so taken by size descending each set's parent is the set that
+// owns its tips at that moment (the smallest superset met so far; none: the node next to tip 1)
+inline void build_lists(const SplitTable &t, const std::vector<int64_t> &kept, ListTree &out)
+{
+  const int n = t.n, K = (int)kept.size();
+  std::vector<int> size((size_t)K, 0), by_size((size_t)K), min_tip((size_t)K + 1, n + 1);
+  for (int k = 0; k < K; k++) {
+    const uint32_t *w = t.row((size_t)kept[(size_t)k]);
+    for (int i = 0; i < t.words; i++) size[(size_t)k] += __builtin_popcount(w[i]);
+    by_size[(size_t)k] = k;
+  }
+  std::stable_sort(by_size.begin(), by_size.end(), [&](int a, int b) { return size[(size_t)a] > size[(size_t)b]; });
+  // set K stands for the node next to tip 1
+  std::vector<int> owner((size_t)n + 1, K), parent((size_t)K, K);
+  for (int k : by_size) {
+    const uint32_t *w = t.row((size_t)kept[(size_t)k]);
+    bool seen = false;
+    for (int tip = 2; tip <= n; tip++)
+      if (w[(tip - 1) >> 5] >> ((tip - 1) & 31) & 1u) {
+        if (!seen) { parent[(size_t)k] = owner[(size_t)tip]; min_tip[(size_t)k] = tip; seen = true; }
+        owner[(size_t)tip] = k;
+      }
+  }
+  min_tip[(size_t)K] = 2;
+  // children of every set: (smallest tip, child), a child set as K + 1 + index so that tips and sets sort together by tip
+  std::vector<std::vector<std::pair<int, int>>> kids((size_t)K + 1);
+  for (int tip = 2; tip <= n; tip++) kids[(size_t)owner[(size_t)tip]].emplace_back(tip, -tip);
+  for (int k = 0; k < K; k++) kids[(size_t)parent[(size_t)k]].emplace_back(min_tip[(size_t)k], k);
+  for (auto &v : kids) std::sort(v.begin(), v.end());
+  // pre-order numbering from tip 1
+  std::vector<int> number((size_t)K + 1, 0), pre;
+  std::vector<int> st{K};
+  while (!st.empty()) {
+    const int s = st.back();
+    st.pop_back();
+    number[(size_t)s] = n + 1 + (int)pre.size();
+    pre.push_back(s);
+    for (size_t i = kids[(size_t)s].size(); i-- > 0;)
+      if (kids[(size_t)s][i].second >= 0) st.push_back(kids[(size_t)s][i].second);
+  }
+  out.first.assign(1, 0);
+  out.nbr.clear();
+  out.support.clear();
+  for (int s : pre) {
+    out.nbr.push_back(s == K ? 1 : number[(size_t)parent[(size_t)s]]);
+    for (const auto &kd : kids[(size_t)s]) out.nbr.push_back(kd.second < 0 ? -kd.second : number[(size_t)kd.second]);
+    out.first.push_back((int32_t)out.nbr.size());
+    out.support.push_back(s == K ? -1 : t.count[(size_t)kept[(size_t)s]]);
+  }
+}
+
+}  // namespace splitsets
+}  // namespace mpf

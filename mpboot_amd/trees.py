@@ -295,3 +295,38 @@ def lists_to_back(first, nbr, n: int) -> np.ndarray:
         else:
             back[r] = pos[(u, v)]
     return back
+
+
+def lists_to_newick(first, nbr, names: list[str], support=None) -> str:
+    """Newick string of a tree given as neighbour lists (tips 1 .. n, inner node i = node n + 1 + i), written from tip 1 with the
+    neighbours in list order.  support[i] (optional, per inner node): written as the label of inner node i where it is >= 0 --
+    the form the consensus tree of the engine (consensus_tree: its split supports) goes to a .contree file in."""
+    n = len(names)
+    first = [int(x) for x in first]
+    nbr = [int(x) for x in nbr]
+    tip_nb = {}
+    for i in range(len(first) - 1):
+        for u in nbr[first[i]:first[i + 1]]:
+            if u <= n:
+                tip_nb[u] = n + 1 + i
+    # iterative post-order from the inner node next to tip 1
+    text = {}
+    root = tip_nb[1]
+    stack = [(root, 1, False)]
+    while stack:
+        v, dad, done = stack.pop()
+        if v <= n:
+            text[v] = names[v - 1]
+            continue
+        i = v - n - 1
+        kids = [u for u in nbr[first[i]:first[i + 1]] if u != dad]
+        if not done:
+            stack.append((v, dad, True))
+            stack.extend((u, v, False) for u in reversed(kids))
+            continue
+        label = "" if support is None or int(support[i]) < 0 else str(int(support[i]))
+        if v == root:
+            text[v] = "(" + ",".join([names[0]] + [text.pop(u) for u in kids]) + ")" + label + ";"
+        else:
+            text[v] = "(" + ",".join(text.pop(u) for u in kids) + ")" + label
+    return text[root]
