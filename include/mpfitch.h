@@ -434,6 +434,40 @@ int mpf_ufboot_summarize(mpf_engine *e, int32_t rule, mpf_bb_summary *s);
 /* ... and the weighted tree set itself: tree_index[cap], weights[cap], backs[cap][3 (2 n_taxa - 1)] (each may be NULL), *n always the
    full number of trees */
 int mpf_ufboot_summary_trees(mpf_engine *e, int32_t rule, int32_t cap, int64_t *tree_index, int32_t *weights, int32_t *backs, int32_t *n);
+/* Robinson-Foulds distances between trees: -rf_all, -rf <treefile2> and -rf_adj of the reference (MTreeSet::computeRFDist,
+   mtreeset.cpp:484-546 for one set, :549-660 for two sets; printed by pda.cpp:1399-1539; the reference's own check of
+   -distinct_iter_top_boot calls it too, iqtree.cpp:2781-2793).  The distance of two trees is the number of non-trivial splits that are
+   in one of them and not in the other: for two complete bifurcating trees on the engine's taxa 2 (n_taxa - 3) - 2 shared.  No split
+   weights and no weight threshold (the reference's default of -1000 lets every split through).
+
+   Trees as in mpf_split_counts: backs[n_trees][3 (2 n_taxa - 1)], each checked as mpf_set_tree checks it and for being ONE tree over
+   all tips (MPF_E_INVALID, the message names the tree; in the second set "second set, tree k").  mode and the layout of rf, which
+   is the reference's:
+     MPF_RF_ALL_PAIRS  rf[i * n_trees + j], symmetric, diagonal 0                                   (mtreeset.cpp:537, pda.cpp:1506-1507)
+     MPF_RF_ADJACENT   rf[i] = d(tree i, tree i + 1), n_trees - 1 entries                           (:535)
+     MPF_RF_TWO_SETS   rf[i * n_trees2 + j] = d(tree i of backs, tree j of backs2)                  (:629-630)
+   n_trees2 / backs2 are 0 / NULL in the other two modes.  cap: the room in rf, in entries.  MPF_E_INVALID: n_trees < 1, an unknown
+   mode, MPF_RF_TWO_SETS with n_trees2 < 1 or NULL backs2, backs2 given in another mode, cap smaller than the number of entries
+   the mode writes.  All pairs of one tree: the single 0; adjacent pairs of one tree: nothing.  With n_taxa = 3 every distance is 0.
+   MPF_E_UNSUPPORTED above 2047 taxa and above 2^27 clusters, (n_trees + n_trees2) (n_taxa - 3), as in the split summary, and when
+   the result would have more than 2^31 - 1 entries.  Either engine (Fitch or weighted).  No current tree is needed, none is changed,
+   an attached tracker books nothing, the tie stream does not move.
+
+   One split pass runs over all trees of the call (k_split_keys, k_split_insert, k_split_count; the second set behind the first),
+   every tree with weight 1.  The table slots that at least two trees hold become the columns of a trees x columns bit matrix
+   (k_rf_columns, k_rf_rows), shared(i, j) is the popcount of row i AND row j (k_rf_shared, a tiled integer matrix product on
+   v_and_b32 / v_bcnt_u32_b32; k_rf_pairs for the adjacent pairs) and k_rf_finish makes the distances.  Exact: a true key collision
+   goes through the overflow list, whose clusters the host groups by whole-set comparison and gives columns of their own.  Memory is
+   bounded: the matrix is built and multiplied in chunks of columns, padded rows x words per chunk within 256 MiB, so the call never
+   refuses for too many distinct splits.  Multifurcating trees (a consensus as neighbour lists, user trees with polytomies) are not
+   taken: the split pass walks record-format trees only.
+   Options: read-only, each about the last call, "rf_columns" (columns of the matrix: the splits that at least two trees hold),
+   "rf_chunks", "rf_launches" (kernel launches, the split pass included) and, under "timing", "rf_rows_ns" / "rf_shared_ns" (HIP-event
+   time of k_rf_rows + k_rf_patch and of k_rf_shared or k_rf_pairs, summed over the chunks; the memset of the chunk's matrix is in neither).  Test option "rf_chunk_columns" (default 0: sized by the memory budget; k > 0: chunks
+   of k columns, rounded up to a multiple of 32).  "split_key_bits" and "split_overflow" apply to this call as to the summary. */
+enum { MPF_RF_ALL_PAIRS = 0, MPF_RF_ADJACENT = 1, MPF_RF_TWO_SETS = 2 };
+int mpf_rf_distances(mpf_engine *e, int32_t mode, int32_t n_trees, const int32_t *backs /* [n_trees][3 (2 n_taxa - 1)] */,
+                     int32_t n_trees2, const int32_t *backs2 /* MPF_RF_TWO_SETS only, else 0 / NULL */, int64_t cap, int32_t *rf);
 /* The same climb under -bb (save_all_trees == 2), with the UFBoot tracker of mpf_ufboot_attach booking every tree the climb looks
    at through IQTree::saveCurrentTree, in the reference's order: at the start of every step that is not a rollback step the current
    tree with curScore (iqtree.cpp:2181-2183), then for every branch the step evaluates, in evaluation order, the tree after move 0

@@ -279,3 +279,20 @@ def bb_summary(eng, best_tree, threshold=0.0, rule=-1):
     return {"node1": s["node1"], "node2": s["node2"], "support": s["support"], "total_weight": s["total_weight"],
             "consensus": (s["first"], s["nbr"]), "consensus_support": s["support_of_inner"],
             "consensus_length": eng.polytomy_parsimony(s["first"], s["nbr"]), "n_distinct_splits": len(s["count"])}
+
+
+def bb_rf(eng, best_tree, rule=-1):
+    """How far the bootstrap trees of a `-bb` run are from best_tree and from each other (the reference's -rf / -rf_all on the tree
+    set of IQTree::summarizeBootstrap; MTreeSet::computeRFDist, mtreeset.cpp:484-660).  Call it while the tracker is attached.
+
+    -> dict: tree_index / weights (the weighted tree set of ufboot_summary_trees(rule)), rf (the Robinson-Foulds distance of each
+    of those trees to best_tree, from ONE two-set call), mean_rf (weighted by `weights`), n_distinct_topologies (trees at distance 0
+    of each other are one topology; from an all-pairs call)."""
+    idx, w, backs = eng.ufboot_summary_trees(rule)
+    rf = eng.rf_distances(backs, [best_tree])[:, 0]
+    total = sum(int(x) for x in w)
+    mean_rf = float(sum(int(a) * int(d) for a, d in zip(w, rf))) / float(total)
+    pairs = eng.rf_distances(backs)
+    # the first tree of every topology: no earlier tree at distance 0
+    n_distinct = len(idx) - int(np.tril(pairs == 0, -1).any(axis=1).sum())
+    return {"tree_index": idx, "weights": w, "rf": rf, "mean_rf": mean_rf, "n_distinct_topologies": int(n_distinct)}

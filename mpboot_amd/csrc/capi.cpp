@@ -490,6 +490,16 @@ int mpf_consensus_tree(mpf_engine *e, int32_t n_trees, const int32_t *backs, con
   return consensus_out(t, n_inner, first, nbr, support_of_inner);
 }
 
+// MTreeSet::computeRFDist (host/rf.cpp)
+static_assert(MPF_RF_ALL_PAIRS == mpf::splitsets::RF_ALL_PAIRS && MPF_RF_ADJACENT == mpf::splitsets::RF_ADJACENT &&
+              MPF_RF_TWO_SETS == mpf::splitsets::RF_TWO_SETS, "the modes of mpf_rf_distances");
+int mpf_rf_distances(mpf_engine *e, int32_t mode, int32_t n_trees, const int32_t *backs, int32_t n_trees2, const int32_t *backs2, int64_t cap,
+                     int32_t *rf)
+{
+  NEED(e);
+  return e->eng.rf_distances(mode, n_trees, backs, n_trees2, backs2, cap, rf);
+}
+
 int mpf_ufboot_summary_trees(mpf_engine *e, int32_t rule, int32_t cap, int64_t *tree_index, int32_t *weights, int32_t *backs, int32_t *n)
 {
   NEED(e);

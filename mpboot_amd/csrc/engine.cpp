@@ -2169,6 +2169,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "brlen_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("brlen_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } brlen_vw_ = (int)v; return MPF_OK; }
   if (key == "poly_tile") { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32) { set_error("poly_tile: 0 (from the row length), 4, 8, 16 or 32 words per workgroup"); return MPF_E_INVALID; } poly_tile_ = (int)v; return MPF_OK; }
   if (key == "split_key_bits") { if (v < 1 || v > 64) { set_error("split_key_bits: 1 .. 64"); return MPF_E_INVALID; } split_key_bits_ = (int)v; return MPF_OK; }
+  if (key == "rf_chunk_columns") { if (v < 0 || v > (1ll << 31)) { set_error("rf_chunk_columns: 0 (sized by the memory budget) or a number of columns"); return MPF_E_INVALID; } rf_chunk_columns_ = v; return MPF_OK; }
   if (key == "nni_weighted") { nni_weighted_ = v ? 1 : 0; return MPF_OK; }     // the -cost NNI climb (host/nni.cpp); no effect on a Fitch engine
   if (key == "nni_weighted_tracked") { nni_weighted_tracked_ = v ? 1 : 0; return MPF_OK; }   // ... under -bb; no effect on a Fitch engine
   if (key == "nni_tracked_rules") { nni_tracked_rules_ = v ? 1 : 0; return MPF_OK; }         // ... with the optional update rules and on a sharded tracker
@@ -2299,6 +2300,12 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "split_keys_ns") *v = (int64_t)split_keys_ns_;
   else if (key == "split_count_ns") *v = (int64_t)split_count_ns_;
   else if (key == "split_bits_ns") *v = (int64_t)split_bits_ns_;
+  else if (key == "rf_chunk_columns") *v = rf_chunk_columns_;
+  else if (key == "rf_columns") *v = (int64_t)rf_columns_;
+  else if (key == "rf_chunks") *v = (int64_t)rf_chunks_;
+  else if (key == "rf_launches") *v = (int64_t)rf_launches_;
+  else if (key == "rf_rows_ns") *v = (int64_t)rf_rows_ns_;
+  else if (key == "rf_shared_ns") *v = (int64_t)rf_shared_ns_;
   else if (key == "nni_booked") *v = ufb_ ? (int64_t)ufb_->nni_booked : 0;
   else if (key == "grow_steps") *v = (int64_t)grow_steps_;
   else if (key == "grow_us") *v = (int64_t)(grow_ms_total_ * 1000.0);

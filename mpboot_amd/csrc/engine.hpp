@@ -13,6 +13,7 @@
 #include <cmath>
 #include <chrono>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <unordered_map>
 #include <memory>
@@ -358,6 +359,10 @@ class Engine {
                     std::vector<int64_t> &support, int64_t *total);
   int consensus_tree(int n_trees, const int32_t *backs, const int32_t *weights, double threshold, splitsets::ListTree &out, int64_t *total);
   int ufboot_summary_trees(int rule, std::vector<int32_t> &backs, std::vector<int32_t> &weights, std::vector<int64_t> &index);
+  // ---- Robinson-Foulds distances between trees (host/rf.cpp, splits.hip; reference MTreeSet::computeRFDist, mtreeset.cpp:484-660):
+  // all pairs of one set, adjacent pairs, or every tree of one set against every tree of another, on the split table of ONE pass over
+  // all the trees.  mode: splitsets::RF_*.  Stateless towards the engine's own tree, its vectors, the tracker and the tie stream
+  int rf_distances(int mode, int n_trees, const int32_t *backs, int n_trees2, const int32_t *backs2, int64_t cap, int32_t *rf);
 
   // ---- online UFBoot-MP bookkeeping (host/ufboot.cpp; reference IQTree::saveCurrentTree, iqtree.cpp:3271-3785)
   int ufboot_attach(int n_samples, const uint16_t *samples, double epsilon, int n_local = -1, const int32_t *sample_ids = nullptr,
@@ -561,12 +566,18 @@ class Engine {
   // insert + count + compact + gather, of k_split_bits)
   struct SplitRun { splitsets::SplitTable table; splitsets::TreeClusters target; std::vector<int64_t> target_support; } split_run_;
   int split_run(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, bool want_sets, double threshold, SplitRun &r);
+  // what the front half of a call leaves (split_pass): T trees, M clusters, a table of tsize slots of which D are used, n_ovf
+  // clusters on the overflow list, rf_columns slots held by at least two trees (only with rf)
+  struct SplitPass { size_t T; uint32_t M, tsize, n_ovf, D, rf_columns; unsigned long long *trep, *tcount; };
+  int split_pass(const char *what, const std::vector<const int32_t *> &trees, const std::vector<int32_t> &hw,
+                 const std::function<std::string(size_t)> &name, bool gather_last, bool rf, SplitPass &p);
+  int split_fetch_sets(size_t first, size_t m);
   struct SplitBufs {
     PinBuf<int32_t> h_backs, h_flags;
     DevBuf<int32_t> backs, pos, order, flags, w;
     DevBuf<SplitCluster> cl;
     DevBuf<unsigned long long> table;              // keys | representatives | counts
-    DevBuf<uint32_t> slot_of, ovf, counters, ids, bits;
+    DevBuf<uint32_t> slot_of, ovf, counters, ids, bits, col_of_slot;
     DevBuf<SplitEntry> entries;
     PinBuf<SplitEntry> h_entries;
     PinBuf<uint32_t> h_ids, h_bits;
@@ -574,6 +585,16 @@ class Engine {
     PinBuf<long long> h_tsup;
   } split_;
   std::vector<int32_t> split_hw_, split_pick_;
+  std::vector<const int32_t *> split_trees_;
+  // Robinson-Foulds distances: test option "rf_chunk_columns" (0 = chunks sized by kRfBudgetBytes; k > 0 = chunks of k columns
+  // rounded up to a multiple of 32); read-only, each about the last call: rf_columns (columns of the incidence matrix: splits that
+  // at least two trees hold), rf_chunks, rf_launches (kernel launches, the split pass included) and, under "timing", rf_rows_ns /
+  // rf_shared_ns (HIP-event time of k_rf_rows + k_rf_patch / of k_rf_shared or k_rf_pairs, summed over the chunks; the memset of
+  // the chunk's matrix is in neither)
+  DevBuf<uint32_t> rf_bits_, rf_patch_;
+  DevBuf<int32_t> rf_out_;
+  int64_t rf_chunk_columns_ = 0;
+  uint64_t rf_columns_ = 0, rf_chunks_ = 0, rf_launches_ = 0, rf_rows_ns_ = 0, rf_shared_ns_ = 0;
   int split_key_bits_ = 64;
   uint64_t split_overflow_ = 0, split_launches_ = 0, split_keys_ns_ = 0, split_count_ns_ = 0, split_bits_ns_ = 0;
   // multifurcating trees: the rooted shape of the tree handed over and the items of its view launch; option "poly_tile" (0 = from

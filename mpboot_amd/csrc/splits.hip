@@ -18,6 +18,25 @@
 //   k_split_gather   the counts of one tree's clusters (the supports of a target tree).
 //   k_split_bits     the n-bit sets of the clusters that are handed out: a lane makes a word from 32 pos comparisons.
 //
+// Robinson-Foulds distances between the trees of a call (MTreeSet::computeRFDist, mtreeset.cpp:484-660) on the same table.  Every
+// tree has weight 1 there, so a slot's count is the number of trees that hold its split, and RF(i, j) = 2 (n - 3) - 2 shared(i, j):
+//
+//   k_rf_columns     one thread per slot: a used slot with count >= 2 gets a dense column number (a split of one tree is shared
+//                    by no pair and gets none, which bounds the columns by half the clusters).
+//   k_rf_rows        the trees x columns incidence matrix B of a chunk of columns [c0, c1) as bits: one thread per cluster,
+//                    atomicOr of its column's bit into its tree's row.  Rows are padded with zero words to kRfKStep words and the
+//                    row count with zero rows to kRfTile, so that the product has no edge branches on its loads.
+//   k_rf_patch       the same for the (cluster, column) pairs the host made of the overflow list (true key collisions).
+//   k_rf_shared      shared[i][j] (+)= popcount(B[i][k] & B'[j][k]) over the chunk's words: a tiled integer matrix product on
+//                    v_and_b32 + v_bcnt_u32_b32.  64 x 64 outputs per 256-thread workgroup, 4 x 4 per lane, 32-word K slices of both
+//                    operands in LDS (8 KiB each, stored word-major: [k][64 rows], so that a lane's four rows of one word are one
+//                    ds_read_b128 -- the A read is a broadcast of 4 addresses per wave, the B' read touches 16 distinct 16-byte
+//                    slots per 16-lane group: all 64 banks once), the next slice's global loads issued before the current slice's
+//                    arithmetic.  All pairs: only tiles on or above the diagonal, each writes its mirror image.  The first chunk
+//                    stores, later chunks add; no atomics on the result.
+//   k_rf_pairs       adjacent pairs (i, i + 1) only: one wave per pair strides over the two rows.
+//   k_rf_finish      shared -> 2 (n - 3) - 2 shared, the diagonal of an all-pairs matrix 0.
+//
 // The key only routes; what decides is the set comparison.  No kernel waits for another workgroup: every atomic either returns
 // at once or is not looked at again before the next launch.
 #include "splits.hpp"
@@ -208,6 +227,151 @@ __global__ void __launch_bounds__(256) k_split_bits(const SplitCluster *__restri
   bits[idx] = w;
 }
 
+// ---- Robinson-Foulds distances
+
+// one thread per slot.  counters[2]: number of columns
+__global__ void __launch_bounds__(256) k_rf_columns(const unsigned long long *__restrict__ trep, const unsigned long long *__restrict__ tcount,
+                                                    uint32_t tsize, uint32_t *__restrict__ col_of_slot, uint32_t *counters)
+{
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= tsize) return;
+  uint32_t c = kRfNoColumn;
+  if (trep[s] != kSplitEmpty && tcount[s] >= 2ull) c = atomicAdd(&counters[2], 1u);
+  col_of_slot[s] = c;
+}
+
+// row of tree t in B: the second set starts on a tile edge of its own
+__device__ __forceinline__ uint32_t rf_row(uint32_t t, uint32_t n1, uint32_t row2) { return t < n1 ? t : row2 + (t - n1); }
+
+// one thread per cluster; B (rows x row_words, zeroed before) gets the bits of the columns in [c0, c1)
+__global__ void __launch_bounds__(256) k_rf_rows(const uint32_t *__restrict__ slot_of, uint32_t n_clusters, uint32_t C,
+                                                 const uint32_t *__restrict__ col_of_slot, uint32_t c0, uint32_t c1, uint32_t n1, uint32_t row2,
+                                                 uint32_t row_words, uint32_t *B)
+{
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_clusters) return;
+  const uint32_t h = slot_of[g];
+  if (h == kSplitNoSlot) return;
+  const uint32_t c = col_of_slot[h];
+  if (c == kRfNoColumn || c < c0 || c >= c1) return;
+  const uint32_t b = c - c0;
+  atomicOr(&B[(size_t)rf_row(g / C, n1, row2) * row_words + (b >> 5)], 1u << (b & 31));
+}
+
+// one thread per (cluster, column) pair of the overflow groups
+__global__ void __launch_bounds__(256) k_rf_patch(const uint32_t *__restrict__ patch, uint32_t m, uint32_t C, uint32_t c0, uint32_t c1,
+                                                  uint32_t n1, uint32_t row2, uint32_t row_words, uint32_t *B)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const uint32_t g = patch[2 * i], c = patch[2 * i + 1];
+  if (c < c0 || c >= c1) return;
+  const uint32_t b = c - c0;
+  atomicOr(&B[(size_t)rf_row(g / C, n1, row2) * row_words + (b >> 5)], 1u << (b & 31));
+}
+
+// grid: the tiles (all pairs: nt (nt + 1) / 2 of them, on or above the diagonal; two sets: nt_a * nt_b).  block: 256.
+// A = B + a_row0 * row_words, B' = B + b_row0 * row_words; both have whole tiles of rows and row_words % kRfKStep == 0.
+// out[i * ld + j], i < na, j < nb.  accumulate = 0: store, 1: add to what is there
+__global__ void __launch_bounds__(256) k_rf_shared(const uint32_t *__restrict__ B, uint32_t a_row0, uint32_t b_row0, uint32_t row_words,
+                                                   uint32_t nt_b, int symmetric, uint32_t na, uint32_t nb, uint32_t ld, int accumulate,
+                                                   int32_t *out)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t sa[kRfKStep * kRfTile];
+  __shared__ __attribute__((aligned(16))) uint32_t sb[kRfKStep * kRfTile];
+  uint32_t ti, tj;
+  if (symmetric) {
+    // tile number -> (ti, tj), ti <= tj, rows of the upper triangle one after the other: row r starts at r nt - r (r - 1) / 2
+    const uint32_t t = blockIdx.x, nt = nt_b;
+    uint32_t r = (uint32_t)(((double)(2 * nt + 1) - sqrt((double)(2 * nt + 1) * (double)(2 * nt + 1) - 8.0 * (double)t)) * 0.5);
+    if (r >= nt) r = nt - 1;
+    while (r > 0 && (unsigned long long)r * nt - (unsigned long long)r * (r - 1) / 2 > t) r--;
+    while (r + 1 < nt && (unsigned long long)(r + 1) * nt - (unsigned long long)(r + 1) * r / 2 <= t) r++;
+    ti = r;
+    tj = r + (t - (uint32_t)((unsigned long long)r * nt - (unsigned long long)r * (r - 1) / 2));
+  } else {
+    ti = blockIdx.x / nt_b;
+    tj = blockIdx.x - ti * nt_b;
+  }
+  const uint32_t tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  // staging: thread -> row tid / 4 of the tile, words 8 (tid % 4) .. + 8 of the slice (two 16-byte loads per operand)
+  const uint32_t lr = tid >> 2, lq = (tid & 3) * 8;
+  const uint32_t *ga = B + ((size_t)a_row0 + (size_t)ti * kRfTile + lr) * row_words + lq;
+  const uint32_t *gb = B + ((size_t)b_row0 + (size_t)tj * kRfTile + lr) * row_words + lq;
+  uint4 ra0 = *reinterpret_cast<const uint4 *>(ga), ra1 = *reinterpret_cast<const uint4 *>(ga + 4);
+  uint4 rb0 = *reinterpret_cast<const uint4 *>(gb), rb1 = *reinterpret_cast<const uint4 *>(gb + 4);
+  uint32_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[i][j] = 0;
+  for (uint32_t k0 = 0; k0 < row_words; k0 += kRfKStep) {
+    __syncthreads();                               // the last slice has been read by everybody
+    {
+      const uint32_t wa[8] = {ra0.x, ra0.y, ra0.z, ra0.w, ra1.x, ra1.y, ra1.z, ra1.w};
+      const uint32_t wb[8] = {rb0.x, rb0.y, rb0.z, rb0.w, rb1.x, rb1.y, rb1.z, rb1.w};
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        sa[(lq + q) * kRfTile + lr] = wa[q];
+        sb[(lq + q) * kRfTile + lr] = wb[q];
+      }
+    }
+    __syncthreads();
+    if (k0 + kRfKStep < row_words) {               // the next slice is on its way while this one is multiplied
+      ga += kRfKStep;
+      gb += kRfKStep;
+      ra0 = *reinterpret_cast<const uint4 *>(ga);
+      ra1 = *reinterpret_cast<const uint4 *>(ga + 4);
+      rb0 = *reinterpret_cast<const uint4 *>(gb);
+      rb1 = *reinterpret_cast<const uint4 *>(gb + 4);
+    }
+#pragma unroll 8
+    for (int k = 0; k < kRfKStep; k++) {
+      const uint4 a = *reinterpret_cast<const uint4 *>(&sa[k * kRfTile + 4 * ty]);
+      const uint4 b = *reinterpret_cast<const uint4 *>(&sb[k * kRfTile + 4 * tx]);
+      const uint32_t av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[i][j] += (uint32_t)__popc(av[i] & bv[j]);
+    }
+  }
+  const uint32_t i0 = ti * kRfTile + 4 * ty, j0 = tj * kRfTile + 4 * tx;
+  const bool mirror = symmetric && ti != tj;       // (the diagonal tile holds both halves itself)
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t gi = i0 + i, gj = j0 + j;
+      if (gi >= na || gj >= nb) continue;
+      int32_t *o = out + (size_t)gi * ld + gj;
+      const int32_t v = (int32_t)acc[i][j] + (accumulate ? *o : 0);
+      *o = v;
+      if (mirror) out[(size_t)gj * ld + gi] = v;
+    }
+}
+
+// adjacent pairs: one wave per pair (i, i + 1) of the first n_pairs + 1 rows.  block: 256 = 4 pairs
+__global__ void __launch_bounds__(256) k_rf_pairs(const uint32_t *__restrict__ B, uint32_t row_words, uint32_t n_pairs, int accumulate, int32_t *out)
+{
+  const uint32_t p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (p >= n_pairs) return;
+  const uint32_t *x = B + (size_t)p * row_words, *y = x + row_words;
+  uint32_t s = 0;
+  for (uint32_t k = lane; k < row_words; k += 64) s += (uint32_t)__popc(x[k] & y[k]);
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+  if (lane == 0) out[p] = (int32_t)s + (accumulate ? out[p] : 0);
+}
+
+// one thread per entry: shared -> 2 C - 2 shared; diag > 0: entries i * diag + i (the diagonal of an all-pairs matrix) are 0
+__global__ void __launch_bounds__(256) k_rf_finish(int32_t *out, unsigned long long entries, int32_t C, uint32_t diag)
+{
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= entries) return;
+  const bool on_diag = diag && (i / diag) == (i % diag);
+  out[i] = on_diag ? 0 : 2 * C - 2 * out[i];
+}
+
 inline unsigned blocks_for(unsigned long long items) { return (unsigned)((items + 255) / 256); }
 
 }  // namespace
@@ -255,6 +419,59 @@ hipError_t launch_split_bits(hipStream_t st, const SplitCluster *cl, const uint3
 {
   if (!m) return hipSuccess;
   hipLaunchKernelGGL(k_split_bits, dim3(blocks_for((unsigned long long)m * (unsigned)((n + 31) / 32))), dim3(256), 0, st, cl, ids, m, n, pos, bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_rf_columns(hipStream_t st, const unsigned long long *trep, const unsigned long long *tcount, uint32_t tsize, uint32_t *col_of_slot,
+                             uint32_t *counters)
+{
+  hipLaunchKernelGGL(k_rf_columns, dim3(blocks_for(tsize)), dim3(256), 0, st, trep, tcount, tsize, col_of_slot, counters);
+  return hipGetLastError();
+}
+
+hipError_t launch_rf_rows(hipStream_t st, const uint32_t *slot_of, uint32_t n_clusters, int n, const uint32_t *col_of_slot, uint32_t c0, uint32_t c1,
+                          uint32_t n1, uint32_t row2, uint32_t row_words, uint32_t *B)
+{
+  if (n < 4 || !n_clusters || c1 < c0 || (uint64_t)(c1 - c0) > 32ull * row_words) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_rf_rows, dim3(blocks_for(n_clusters)), dim3(256), 0, st, slot_of, n_clusters, (uint32_t)(n - 3), col_of_slot, c0, c1, n1, row2,
+                     row_words, B);
+  return hipGetLastError();
+}
+
+hipError_t launch_rf_patch(hipStream_t st, const uint32_t *patch, uint32_t m, int n, uint32_t c0, uint32_t c1, uint32_t n1, uint32_t row2,
+                           uint32_t row_words, uint32_t *B)
+{
+  if (!m) return hipSuccess;
+  if (n < 4 || c1 < c0 || (uint64_t)(c1 - c0) > 32ull * row_words) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_rf_patch, dim3(blocks_for(m)), dim3(256), 0, st, patch, m, (uint32_t)(n - 3), c0, c1, n1, row2, row_words, B);
+  return hipGetLastError();
+}
+
+hipError_t launch_rf_shared(hipStream_t st, const uint32_t *B, uint32_t a_row0, uint32_t b_row0, uint32_t row_words, bool symmetric, uint32_t na,
+                            uint32_t nb, bool accumulate, int32_t *out)
+{
+  if (!na || !nb || !row_words || row_words % kRfKStep || a_row0 % kRfTile || b_row0 % kRfTile || (symmetric && (na != nb || a_row0 != b_row0)))
+    return hipErrorInvalidValue;
+  const unsigned long long nt_a = rf_tiles(na), nt_b = rf_tiles(nb);
+  const unsigned long long tiles = symmetric ? nt_a * (nt_a + 1) / 2 : nt_a * nt_b;
+  if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_rf_shared, dim3((unsigned)tiles), dim3(256), 0, st, B, a_row0, b_row0, row_words, (uint32_t)nt_b, symmetric ? 1 : 0, na, nb,
+                     nb, accumulate ? 1 : 0, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_rf_pairs(hipStream_t st, const uint32_t *B, uint32_t row_words, uint32_t n_pairs, bool accumulate, int32_t *out)
+{
+  if (!n_pairs) return hipSuccess;
+  hipLaunchKernelGGL(k_rf_pairs, dim3((n_pairs + 3) / 4), dim3(256), 0, st, B, row_words, n_pairs, accumulate ? 1 : 0, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_rf_finish(hipStream_t st, int32_t *out, unsigned long long entries, int n, uint32_t diag)
+{
+  if (!entries) return hipSuccess;
+  if (entries > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_rf_finish, dim3(blocks_for(entries)), dim3(256), 0, st, out, entries, (int32_t)(n - 3), diag);
   return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-// splits.hpp -- launchers of splits.hip: the bipartitions of a set of complete trees, counted exactly on the device.
+// splits.hpp -- launchers of splits.hip: the bipartitions of a set of complete trees, counted exactly on the device, and the
+// Robinson-Foulds distances between the trees on the same table.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,14 @@ constexpr uint32_t kSplitNoSlot = 0xFFFFFFFFu;           // slot_of[] of a clust
 constexpr int kSplitMaxTaxa = 2047;
 inline size_t split_keys_lds_bytes(int n) { return sizeof(int32_t) * ((size_t)3 * (2 * (size_t)n - 1) + 2 * (size_t)n + 4); }
 
+// Robinson-Foulds distances: the incidence matrix B (trees x columns, bits) is multiplied in tiles of kRfTile x kRfTile outputs over
+// slices of kRfKStep words; its rows are padded to both.  B is built and multiplied in chunks of columns so that rows x words of a
+// chunk stay within kRfBudgetBytes, whatever the number of distinct splits
+constexpr uint32_t kRfNoColumn = 0xFFFFFFFFu;            // col_of_slot[] of a slot whose split fewer than two trees hold
+constexpr int kRfTile = 64, kRfKStep = 32;
+constexpr size_t kRfBudgetBytes = (size_t)256 << 20;
+inline unsigned long long rf_tiles(unsigned long long rows) { return (rows + kRfTile - 1) / kRfTile; }
+
 hipError_t launch_split_keys(hipStream_t st, const int32_t *backs, int n_trees, int n, int key_bits, int32_t *pos, int32_t *order,
                              SplitCluster *cl, int32_t *bad);
 hipError_t launch_split_insert(hipStream_t st, const SplitCluster *cl, uint32_t n_clusters, unsigned long long *tkey, unsigned long long *trep,
@@ -30,5 +39,16 @@ hipError_t launch_split_compact(hipStream_t st, const unsigned long long *trep, 
                                 uint32_t *counters);
 hipError_t launch_split_gather(hipStream_t st, const uint32_t *slot_of, uint32_t first, uint32_t m, const unsigned long long *tcount, long long *out);
 hipError_t launch_split_bits(hipStream_t st, const SplitCluster *cl, const uint32_t *ids, uint32_t m, int n, const int32_t *pos, uint32_t *bits);
+hipError_t launch_rf_columns(hipStream_t st, const unsigned long long *trep, const unsigned long long *tcount, uint32_t tsize, uint32_t *col_of_slot,
+                             uint32_t *counters /* [2]: number of columns */);
+// tree t's row: t < n1 ? t : row2 + (t - n1) (the second set of a two-set call starts on a tile edge)
+hipError_t launch_rf_rows(hipStream_t st, const uint32_t *slot_of, uint32_t n_clusters, int n, const uint32_t *col_of_slot, uint32_t c0, uint32_t c1,
+                          uint32_t n1, uint32_t row2, uint32_t row_words, uint32_t *B);
+hipError_t launch_rf_patch(hipStream_t st, const uint32_t *patch /* [m][2]: cluster, column */, uint32_t m, int n, uint32_t c0, uint32_t c1,
+                           uint32_t n1, uint32_t row2, uint32_t row_words, uint32_t *B);
+hipError_t launch_rf_shared(hipStream_t st, const uint32_t *B, uint32_t a_row0, uint32_t b_row0, uint32_t row_words, bool symmetric, uint32_t na,
+                            uint32_t nb, bool accumulate, int32_t *out /* [na][nb] */);
+hipError_t launch_rf_pairs(hipStream_t st, const uint32_t *B, uint32_t row_words, uint32_t n_pairs, bool accumulate, int32_t *out);
+hipError_t launch_rf_finish(hipStream_t st, int32_t *out, unsigned long long entries, int n, uint32_t diag);
 
 }  // namespace mpf

@@ -38,6 +38,7 @@ EXPORTS = [
     "mpf_branch_substitutions", "mpf_branch_lengths",
     "mpf_polytomy_parsimony", "mpf_polytomy_branch_substitutions", "mpf_polytomy_branch_lengths",
     "mpf_split_counts", "mpf_split_support", "mpf_consensus_tree", "mpf_ufboot_summarize", "mpf_ufboot_summary_trees",
+    "mpf_rf_distances",
 ]
 
 
@@ -88,6 +89,7 @@ class BbSummary(C.Structure):
 
 
 SUMMARY_AUTO, SUMMARY_DEFAULT, SUMMARY_MULHITS, SUMMARY_TOPBOOT = -1, 0, 1, 2
+RF_ALL_PAIRS, RF_ADJACENT, RF_TWO_SETS = 0, 1, 2       # MPF_RF_* (include/mpfitch.h)
 
 
 def load_library():
@@ -196,6 +198,7 @@ def load_library():
         L.mpf_consensus_tree.argtypes = [vp, C.c_int32, vp, vp, C.c_double, vp, vp, vp, vp, vp]
         L.mpf_ufboot_summarize.argtypes = [vp, C.c_int32, C.POINTER(BbSummary)]
         L.mpf_ufboot_summary_trees.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.mpf_rf_distances.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]
         _lib = L
     return _lib
 
@@ -773,6 +776,27 @@ class FitchEngine:
                "first": first[:k + 1].copy(), "nbr": nbr[:int(first[k])].copy(), "support_of_inner": isup[:k].copy()}
         if t is not None:
             out.update(node1=a, node2=c, support=sup)
+        return out
+
+    def rf_distances(self, backs, backs2=None, mode: str = "all"):
+        """Robinson-Foulds distances between trees (MTreeSet::computeRFDist; -rf_all, -rf_adj, -rf of the reference): the number of
+        non-trivial splits in one tree and not in the other, int32.  backs[T][3 (2n - 1)] alone: mode "all" -> [T][T] (symmetric,
+        diagonal 0), mode "adjacent" -> [T - 1], d(tree i, tree i + 1).  With backs2[T2][...]: [T][T2], tree i of backs against
+        tree j of backs2.  Exact: one split pass over all the trees on the device, then a binary matrix product."""
+        if mode not in ("all", "adjacent"):
+            raise ValueError("mode: 'all' or 'adjacent'")
+        b, _ = self._tree_set(backs, None)
+        T = len(b)
+        if backs2 is not None:
+            if mode != "all":
+                raise ValueError("two sets: every tree of the first against every tree of the second (mode 'all')")
+            b2, _ = self._tree_set(backs2, None)
+            out = np.zeros((T, len(b2)), dtype=np.int32)
+            _chk(load_library().mpf_rf_distances(self.h, RF_TWO_SETS, T, _p(b), len(b2), _p(b2), out.size, _p(out)))
+            return out
+        out = np.zeros((T, T) if mode == "all" else (max(T - 1, 0),), dtype=np.int32)
+        _chk(load_library().mpf_rf_distances(self.h, RF_ALL_PAIRS if mode == "all" else RF_ADJACENT, T, _p(b), 0, None, out.size,
+                                             _p(out) if out.size else None))
         return out
 
     def nni_pattern_terms(self, root_taxon: int = 1):

@@ -12,6 +12,12 @@
 //   greedy_compatible SplitGraph::findMaxCompatibleSplits (reference splitgraph.cpp:615-648): walk the splits in that order and
 //                     keep each one that is compatible with all kept so far; at most n - 3 non-trivial ones fit a tree
 //   build_lists       the kept (pairwise compatible) sets as the CSR neighbour lists mpf_polytomy_* takes
+//
+// ... and of the Robinson-Foulds distances (Engine::rf_distances; host/rf_host_main.cpp, tests/test_rf_host.py):
+//   overflow_columns  the clusters of the overflow list grouped as sets: a group of two or more gets a column of its own
+//   rf_chunk_plan     the column chunks the incidence matrix is built and multiplied in
+//   host_rf           MTreeSet::computeRFDist (reference mtreeset.cpp:484-660) on the host: one sorted list of split ids per tree,
+//                     a merge per pair (the CPU yardstick of tools/rf_timing.py and a second witness)
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -277,6 +283,133 @@ inline void build_lists(const SplitTable &t, const std::vector<int64_t> &kept, L
     out.first.push_back((int32_t)out.nbr.size());
     out.support.push_back(s == K ? -1 : t.count[(size_t)kept[(size_t)s]]);
   }
+}
+
+// ---- Robinson-Foulds distances
+
+enum { RF_ALL_PAIRS = 0, RF_ADJACENT = 1, RF_TWO_SETS = 2 };
+
+// sets[m][words]: the sets of the clusters on the overflow list (true key collisions: none of them is the set its table slot
+// stands for, so none of them equals a split that has a device-numbered column).  Equal sets form a group; a group of two or more
+// gets the next column from first_col on, in the order its first member appears; a set that stands alone gets none (-1): no pair
+// of trees shares it.  Two clusters of one tree are different sets, so a group never holds one tree twice.  Returns the number of
+// columns handed out
+inline int64_t overflow_columns(const std::vector<uint32_t> &sets, size_t m, int words, int64_t first_col, std::vector<int64_t> &col)
+{
+  std::vector<int64_t> group(m, -1), size, first;
+  std::vector<uint32_t> reps;
+  SetIndex idx(words);
+  idx.reserve(m);
+  for (size_t i = 0; i < m; i++) {
+    const uint32_t *w = sets.data() + i * (size_t)words;
+    int64_t g = idx.find(reps, w);
+    if (g < 0) {
+      g = (int64_t)size.size();
+      reps.insert(reps.end(), w, w + words);
+      size.push_back(0);
+      idx.insert(w, g);
+    }
+    size[(size_t)g]++;
+    group[i] = g;
+  }
+  std::vector<int64_t> col_of_group(size.size(), -1);
+  int64_t next = first_col;
+  col.assign(m, -1);
+  for (size_t i = 0; i < m; i++) {
+    const size_t g = (size_t)group[i];
+    if (size[g] < 2) continue;
+    if (col_of_group[g] < 0) col_of_group[g] = next++;
+    col[i] = col_of_group[g];
+  }
+  return next - first_col;
+}
+
+struct RfChunk { int64_t c0, c1; };
+inline int64_t rf_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// The chunks [c0, c1) that cover columns 0 .. columns once, in order.  forced > 0: chunks of `forced` columns rounded up to a
+// multiple of 32 (a test option).  Else the widest chunk whose matrix -- rows x words, the words of a row padded to k_step --
+// stays within budget_bytes, at least k_step words.  Every chunk but the last is a multiple of 32 columns.  No columns: no chunk
+inline std::vector<RfChunk> rf_chunk_plan(int64_t columns, int64_t rows, int64_t forced, int64_t budget_bytes, int64_t k_step)
+{
+  std::vector<RfChunk> plan;
+  if (columns <= 0) return plan;
+  int64_t per;
+  if (forced > 0) per = rf_round_up(forced, 32);
+  else {
+    const int64_t words = std::max<int64_t>(k_step, budget_bytes / (4 * std::max<int64_t>(rows, 1)) / k_step * k_step);
+    per = 32 * words;
+  }
+  for (int64_t c = 0; c < columns; c += per) plan.push_back(RfChunk{c, std::min(columns, c + per)});
+  return plan;
+}
+
+// every tree's splits as a sorted list of ids into one exact table.  false: a tree is not a complete tree on n taxa
+inline bool rf_id_lists(int n, int n_trees, const int32_t *backs, SetIndex &idx, std::vector<uint32_t> &table, std::vector<int64_t> &ids)
+{
+  const size_t len = 3 * (size_t)(2 * n - 1);
+  const int words = words_of(n), C = std::max(n - 3, 0);
+  TreeClusters c;
+  std::vector<uint32_t> w((size_t)words);
+  for (int t = 0; t < n_trees; t++) {
+    const int32_t *back = backs + (size_t)t * len;
+    if (!links_ok(back, n) || !walk_clusters(back, n, c)) return false;
+    const size_t at = ids.size();
+    for (int ci = 0; ci < C; ci++) {
+      cluster_bits(c, ci, words, w.data());
+      int64_t k = idx.find(table, w.data());
+      if (k < 0) {
+        k = (int64_t)(table.size() / (size_t)words);
+        table.insert(table.end(), w.begin(), w.end());
+        idx.insert(w.data(), k);
+      }
+      ids.push_back(k);
+    }
+    std::sort(ids.begin() + (long)at, ids.end());
+  }
+  return true;
+}
+
+// MTreeSet::computeRFDist without the strings and without weights: the number of splits in one tree and not in the other.
+// out: the layout of the mode (all pairs [T][T]; adjacent [T - 1]; two sets [T][T2]).  false: a tree is broken (*bad_tree: which,
+// counted through both sets) or the mode is unknown
+inline bool host_rf(int n, int mode, int n_trees, const int32_t *backs, int n_trees2, const int32_t *backs2, std::vector<int32_t> &out,
+                    int *bad_tree = nullptr)
+{
+  const int C = std::max(n - 3, 0), words = words_of(n);
+  SetIndex idx(words);
+  std::vector<uint32_t> table;
+  std::vector<int64_t> ids, ids2;
+  if (mode != RF_ALL_PAIRS && mode != RF_ADJACENT && mode != RF_TWO_SETS) return false;
+  for (int t = 0; t < n_trees; t++)
+    if (!rf_id_lists(n, 1, backs + (size_t)t * 3 * (size_t)(2 * n - 1), idx, table, ids)) { if (bad_tree) *bad_tree = t; return false; }
+  if (mode == RF_TWO_SETS)
+    for (int t = 0; t < n_trees2; t++)
+      if (!rf_id_lists(n, 1, backs2 + (size_t)t * 3 * (size_t)(2 * n - 1), idx, table, ids2)) { if (bad_tree) *bad_tree = n_trees + t; return false; }
+  auto dist = [&](const int64_t *a, const int64_t *b) {
+    int shared = 0;
+    for (int i = 0, j = 0; i < C && j < C;) {
+      if (a[i] == b[j]) { shared++; i++; j++; }
+      else if (a[i] < b[j]) i++;
+      else j++;
+    }
+    return (int32_t)(2 * C - 2 * shared);
+  };
+  out.clear();
+  if (mode == RF_ALL_PAIRS) {
+    out.assign((size_t)n_trees * (size_t)n_trees, 0);
+    for (int i = 0; i < n_trees; i++)
+      for (int j = i + 1; j < n_trees; j++)
+        out[(size_t)i * (size_t)n_trees + (size_t)j] = out[(size_t)j * (size_t)n_trees + (size_t)i] =
+            dist(ids.data() + (size_t)i * (size_t)C, ids.data() + (size_t)j * (size_t)C);
+  } else if (mode == RF_ADJACENT) {
+    for (int i = 0; i + 1 < n_trees; i++) out.push_back(dist(ids.data() + (size_t)i * (size_t)C, ids.data() + (size_t)(i + 1) * (size_t)C));
+  } else {
+    out.reserve((size_t)n_trees * (size_t)n_trees2);
+    for (int i = 0; i < n_trees; i++)
+      for (int j = 0; j < n_trees2; j++) out.push_back(dist(ids.data() + (size_t)i * (size_t)C, ids2.data() + (size_t)j * (size_t)C));
+  }
+  return true;
 }
 
 }  // namespace splitsets

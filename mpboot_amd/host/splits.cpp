@@ -9,6 +9,7 @@
 // keys -> insert -> count -> compact); the host checks the trees, resolves the overflow list of true key collisions through whole-set
 // comparison, puts the distinct splits in the contract order and runs the consensus rule on the kept sets (host/split_sets.hpp,
 // which holds everything that needs no device and is tested stand-alone under a sanitizer).
+#include <functional>
 #include <string>
 
 #include "split_sets.hpp"
@@ -29,6 +30,105 @@ namespace mpf {
 namespace {
 int bad(const std::string &what) { set_error("split summary: " + what); return MPF_E_INVALID; }
 }  // namespace
+
+// The front half of every call on a tree set: the trees (already checked link by link by the caller) are staged, walked
+// (k_split_keys; a tree whose records do not form one tree ends the call, named by `name`), and their clusters inserted and counted
+// (k_split_insert, k_split_count, k_split_compact); the counters and the overflow list of true key collisions come back.
+// hw[i]: the weight of trees[i].  gather_last: the counts of the last tree's clusters go to split_.h_tsup (a target tree).
+// rf: k_rf_columns numbers the slots that at least two trees hold (p.rf_columns).  Afterwards split_.h_entries holds the p.D used
+// slots and split_.h_ids[p.D .. p.D + p.n_ovf) the overflow clusters, sorted
+int Engine::split_pass(const char *what, const std::vector<const int32_t *> &trees, const std::vector<int32_t> &hw,
+                       const std::function<std::string(size_t)> &name, bool gather_last, bool rf, SplitPass &p)
+{
+  const int n = n_, C = n - 3;
+  const size_t len = 3 * (size_t)(2 * n - 1);
+  const size_t T = trees.size();
+  if ((uint64_t)T * (uint64_t)C > (1ull << 27)) { set_error(std::string(what) + ": more than 2^27 clusters in one call"); return MPF_E_UNSUPPORTED; }
+  const uint32_t M = (uint32_t)(T * (size_t)C);
+  uint32_t tsize = 64;
+  while ((uint64_t)tsize < 2ull * M) tsize <<= 1;
+  SplitBufs &b = split_;
+  HIPCHK(b.h_backs.reserve(T * len));
+  for (size_t i = 0; i < T; i++) std::memcpy(b.h_backs.p + i * len, trees[i], len * sizeof(int32_t));
+  HIPCHK(b.backs.reserve(T * len));
+  HIPCHK(b.pos.reserve(T * (size_t)n));
+  HIPCHK(b.order.reserve(T * (size_t)(n - 1)));
+  HIPCHK(b.cl.reserve(M));
+  HIPCHK(b.flags.reserve(T));
+  HIPCHK(b.h_flags.reserve(T + 4));
+  HIPCHK(b.w.reserve(T));
+  HIPCHK(b.table.reserve(3 * (size_t)tsize));
+  HIPCHK(b.slot_of.reserve(M));
+  HIPCHK(b.ovf.reserve(M));
+  HIPCHK(b.counters.reserve(4));
+  HIPCHK(b.entries.reserve(M));
+  if (rf) HIPCHK(b.col_of_slot.reserve(tsize));
+  unsigned long long *tkey = b.table.p, *trep = tkey + tsize, *tcount = trep + tsize;
+  HIPCHK(hipMemcpyAsync(b.backs.p, b.h_backs.p, T * len * sizeof(int32_t), hipMemcpyHostToDevice, st_));
+  HIPCHK(hipMemcpyAsync(b.w.p, hw.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st_));
+  HIPCHK(hipMemsetAsync(tkey, 0xFF, 2 * (size_t)tsize * sizeof(unsigned long long), st_));      // keys and representatives: empty
+  HIPCHK(hipMemsetAsync(tcount, 0, (size_t)tsize * sizeof(unsigned long long), st_));
+  HIPCHK(hipMemsetAsync(b.counters.p, 0, 4 * sizeof(uint32_t), st_));
+  if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
+  HIPCHK(launch_split_keys(st_, b.backs.p, (int)T, n, split_key_bits_, b.pos.p, b.order.p, b.cl.p, b.flags.p));
+  if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
+  HIPCHK(hipMemcpyAsync(b.h_flags.p, b.flags.p, T * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+  // the later kernels index through what the walk wrote: they start only behind a walk that ended well on every tree
+  HIPCHK(hipStreamSynchronize(st_));
+  for (size_t i = 0; i < T; i++)
+    if (b.h_flags.p[i]) { set_error(std::string(what) + ": " + name(i) + ": the records do not form one tree"); return MPF_E_INVALID; }
+  if (timing_) HIPCHK(hipEventRecord(ev2_, st_));
+  HIPCHK(launch_split_insert(st_, b.cl.p, M, tkey, trep, tsize, b.slot_of.p));
+  HIPCHK(launch_split_count(st_, b.cl.p, M, n, b.pos.p, b.order.p, trep, b.slot_of.p, b.w.p, tcount, b.ovf.p, b.counters.p));
+  HIPCHK(launch_split_compact(st_, trep, tcount, tsize, b.entries.p, b.counters.p));
+  if (gather_last) {
+    HIPCHK(b.tsup.reserve((size_t)C));
+    HIPCHK(b.h_tsup.reserve((size_t)C));
+    HIPCHK(launch_split_gather(st_, b.slot_of.p, M - (uint32_t)C, (uint32_t)C, tcount, b.tsup.p));
+    HIPCHK(hipMemcpyAsync(b.h_tsup.p, b.tsup.p, (size_t)C * sizeof(long long), hipMemcpyDeviceToHost, st_));
+  }
+  if (timing_) HIPCHK(hipEventRecord(ev3_, st_));
+  if (rf) HIPCHK(launch_rf_columns(st_, trep, tcount, tsize, b.col_of_slot.p, b.counters.p));
+  HIPCHK(hipMemcpyAsync(b.h_flags.p, b.counters.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+  HIPCHK(hipStreamSynchronize(st_));
+  float ms = 0.f;
+  if (timing_ && hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) split_keys_ns_ += (uint64_t)((double)ms * 1e6);
+  if (timing_ && hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) split_count_ns_ += (uint64_t)((double)ms * 1e6);
+  split_launches_++;
+  const uint32_t n_ovf = (uint32_t)b.h_flags.p[0], D = (uint32_t)b.h_flags.p[1], cols = (uint32_t)b.h_flags.p[2];
+  if (n_ovf > M || D > M || cols > D) { set_error(std::string(what) + ": inconsistent counters"); return MPF_E_STATE; }
+  split_overflow_ = n_ovf;
+  HIPCHK(b.h_entries.reserve(D + 1));
+  HIPCHK(hipMemcpyAsync(b.h_entries.p, b.entries.p, (size_t)D * sizeof(SplitEntry), hipMemcpyDeviceToHost, st_));
+  HIPCHK(b.h_ids.reserve((size_t)D + n_ovf + 1));
+  if (n_ovf) HIPCHK(hipMemcpyAsync(b.h_ids.p + D, b.ovf.p, (size_t)n_ovf * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+  HIPCHK(hipStreamSynchronize(st_));
+  // in cluster order, so that nothing depends on the order the device appended them in
+  std::sort(b.h_ids.p + D, b.h_ids.p + D + n_ovf);
+  for (uint32_t k = 0; k < n_ovf; k++)
+    if (b.h_ids.p[D + k] >= M) { set_error(std::string(what) + ": overflow entry out of range"); return MPF_E_STATE; }
+  p = SplitPass{T, M, tsize, n_ovf, D, cols, trep, tcount};
+  return MPF_OK;
+}
+
+// the sets of the clusters split_.h_ids[first .. first + m), made on the device, into split_.h_bits
+int Engine::split_fetch_sets(size_t first, size_t m)
+{
+  SplitBufs &b = split_;
+  const int words = splitsets::words_of(n_);
+  HIPCHK(b.ids.reserve(m));
+  HIPCHK(b.bits.reserve(m * (size_t)words));
+  HIPCHK(b.h_bits.reserve(m * (size_t)words));
+  HIPCHK(hipMemcpyAsync(b.ids.p, b.h_ids.p + first, m * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+  if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
+  HIPCHK(launch_split_bits(st_, b.cl.p, b.ids.p, (uint32_t)m, n_, b.pos.p, b.bits.p));
+  if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
+  HIPCHK(hipMemcpyAsync(b.h_bits.p, b.bits.p, m * (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+  HIPCHK(hipStreamSynchronize(st_));
+  float t = 0.f;
+  if (timing_ && hipEventElapsedTime(&t, ev0_, ev1_) == hipSuccess) split_bits_ns_ += (uint64_t)((double)t * 1e6);
+  return MPF_OK;
+}
 
 // One pass over the trees.  r.table: the distinct splits with count > max(0, threshold * total) and, if want_sets, their sets -- in
 // no particular order.  target (may be null): one more tree of weight 0 whose clusters' counts come back in r.target_support,
@@ -53,8 +153,10 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
   // the checks of mpf_set_tree on every tree; trees of weight 0 are left out here
   std::vector<int32_t> &hw = split_hw_;
   std::vector<int32_t> &pick = split_pick_;
+  std::vector<const int32_t *> &trees = split_trees_;
   hw.clear();
   pick.clear();
+  trees.clear();
   for (int t = 0; t < n_trees; t++) {
     const int32_t w = weights ? weights[t] : 1;
     if (w < 0) return bad("tree " + std::to_string(t) + " has a negative weight");
@@ -63,104 +165,35 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
     tab.total += w;
     hw.push_back(w);
     pick.push_back(t);
+    trees.push_back(backs + (size_t)t * len);
   }
   if (target) {
     if (!splitsets::links_ok(target, n)) return bad("target tree: inconsistent back links (a complete tree on n_taxa taxa is needed)");
     if (!splitsets::walk_clusters(target, n, r.target)) return bad("target tree: the records do not form one tree");
     r.target_support.assign((size_t)std::max(C, 0), 0);
     hw.push_back(0);
+    trees.push_back(target);
   }
-  const size_t T = hw.size();
-  if (C < 1 || !T) return MPF_OK;
-  if ((uint64_t)T * (uint64_t)C > (1ull << 27)) { set_error("split summary: more than 2^27 clusters in one call"); return MPF_E_UNSUPPORTED; }
-  const uint32_t M = (uint32_t)(T * (size_t)C);
-  uint32_t tsize = 64;
-  while ((uint64_t)tsize < 2ull * M) tsize <<= 1;
+  if (C < 1 || hw.empty()) return MPF_OK;
+  SplitPass ps;
+  int rc = split_pass("split summary", trees, hw,
+                      [&](size_t i) { return i < pick.size() ? "tree " + std::to_string(pick[i]) : std::string("target tree"); }, target != nullptr,
+                      false, ps);
+  if (rc) return rc;
   SplitBufs &b = split_;
-  HIPCHK(b.h_backs.reserve(T * len));
-  for (size_t i = 0; i < pick.size(); i++) std::memcpy(b.h_backs.p + i * len, backs + (size_t)pick[i] * len, len * sizeof(int32_t));
-  if (target) std::memcpy(b.h_backs.p + pick.size() * len, target, len * sizeof(int32_t));
-  HIPCHK(b.backs.reserve(T * len));
-  HIPCHK(b.pos.reserve(T * (size_t)n));
-  HIPCHK(b.order.reserve(T * (size_t)(n - 1)));
-  HIPCHK(b.cl.reserve(M));
-  HIPCHK(b.flags.reserve(T));
-  HIPCHK(b.h_flags.reserve(T + 2));
-  HIPCHK(b.w.reserve(T));
-  HIPCHK(b.table.reserve(3 * (size_t)tsize));
-  HIPCHK(b.slot_of.reserve(M));
-  HIPCHK(b.ovf.reserve(M));
-  HIPCHK(b.counters.reserve(2));
-  HIPCHK(b.entries.reserve(M));
-  unsigned long long *tkey = b.table.p, *trep = tkey + tsize, *tcount = trep + tsize;
-  HIPCHK(hipMemcpyAsync(b.backs.p, b.h_backs.p, T * len * sizeof(int32_t), hipMemcpyHostToDevice, st_));
-  HIPCHK(hipMemcpyAsync(b.w.p, hw.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st_));
-  HIPCHK(hipMemsetAsync(tkey, 0xFF, 2 * (size_t)tsize * sizeof(unsigned long long), st_));      // keys and representatives: empty
-  HIPCHK(hipMemsetAsync(tcount, 0, (size_t)tsize * sizeof(unsigned long long), st_));
-  HIPCHK(hipMemsetAsync(b.counters.p, 0, 2 * sizeof(uint32_t), st_));
-  if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
-  HIPCHK(launch_split_keys(st_, b.backs.p, (int)T, n, split_key_bits_, b.pos.p, b.order.p, b.cl.p, b.flags.p));
-  if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
-  HIPCHK(hipMemcpyAsync(b.h_flags.p, b.flags.p, T * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-  // the later kernels index through what the walk wrote: they start only behind a walk that ended well on every tree
-  HIPCHK(hipStreamSynchronize(st_));
-  for (size_t i = 0; i < T; i++)
-    if (b.h_flags.p[i]) return bad((i < pick.size() ? "tree " + std::to_string(pick[i]) : std::string("target tree")) + ": the records do not form one tree");
-  if (timing_) HIPCHK(hipEventRecord(ev2_, st_));
-  HIPCHK(launch_split_insert(st_, b.cl.p, M, tkey, trep, tsize, b.slot_of.p));
-  HIPCHK(launch_split_count(st_, b.cl.p, M, n, b.pos.p, b.order.p, trep, b.slot_of.p, b.w.p, tcount, b.ovf.p, b.counters.p));
-  HIPCHK(launch_split_compact(st_, trep, tcount, tsize, b.entries.p, b.counters.p));
-  if (target) {
-    HIPCHK(b.tsup.reserve((size_t)C));
-    HIPCHK(b.h_tsup.reserve((size_t)C));
-    HIPCHK(launch_split_gather(st_, b.slot_of.p, M - (uint32_t)C, (uint32_t)C, tcount, b.tsup.p));
-    HIPCHK(hipMemcpyAsync(b.h_tsup.p, b.tsup.p, (size_t)C * sizeof(long long), hipMemcpyDeviceToHost, st_));
-  }
-  if (timing_) HIPCHK(hipEventRecord(ev3_, st_));
-  HIPCHK(hipMemcpyAsync(b.h_flags.p, b.counters.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-  HIPCHK(hipStreamSynchronize(st_));
-  float ms = 0.f;
-  if (timing_ && hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) split_keys_ns_ += (uint64_t)((double)ms * 1e6);
-  if (timing_ && hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) split_count_ns_ += (uint64_t)((double)ms * 1e6);
-  split_launches_++;
-  const uint32_t n_ovf = (uint32_t)b.h_flags.p[0], D = (uint32_t)b.h_flags.p[1];
-  if (n_ovf > M || D > M) { set_error("split summary: inconsistent counters"); return MPF_E_STATE; }
-  split_overflow_ = n_ovf;
-  HIPCHK(b.h_entries.reserve(D + 1));
-  HIPCHK(hipMemcpyAsync(b.h_entries.p, b.entries.p, (size_t)D * sizeof(SplitEntry), hipMemcpyDeviceToHost, st_));
-  if (n_ovf) {
-    HIPCHK(b.h_ids.reserve((size_t)D + n_ovf));
-    HIPCHK(hipMemcpyAsync(b.h_ids.p + D, b.ovf.p, (size_t)n_ovf * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-  }
-  HIPCHK(hipStreamSynchronize(st_));
+  const uint32_t M = ps.M, n_ovf = ps.n_ovf, D = ps.D;
   const SplitEntry *ent = b.h_entries.p;
   const double cut = threshold * (double)tab.total;
   auto passes = [&](int64_t c) { return c > 0 && (double)c > cut; };
-  // the sets of a list of clusters, made on the device
-  auto fetch_sets = [&](size_t m) -> int {
-    HIPCHK(b.ids.reserve(m));
-    HIPCHK(b.bits.reserve(m * (size_t)words));
-    HIPCHK(b.h_bits.reserve(m * (size_t)words));
-    HIPCHK(hipMemcpyAsync(b.ids.p, b.h_ids.p, m * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
-    if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
-    HIPCHK(launch_split_bits(st_, b.cl.p, b.ids.p, (uint32_t)m, n, b.pos.p, b.bits.p));
-    if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
-    HIPCHK(hipMemcpyAsync(b.h_bits.p, b.bits.p, m * (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-    HIPCHK(hipStreamSynchronize(st_));
-    float t = 0.f;
-    if (timing_ && hipEventElapsedTime(&t, ev0_, ev1_) == hipSuccess) split_bits_ns_ += (uint64_t)((double)t * 1e6);
-    return MPF_OK;
-  };
   if (!n_ovf) {
     // no collision: every slot is one split and its count is final
     if (target)
       for (int ci = 0; ci < C; ci++) r.target_support[(size_t)ci] = b.h_tsup.p[ci];
     size_t m = 0;
-    HIPCHK(b.h_ids.reserve((size_t)D + 1));
     for (uint32_t i = 0; i < D; i++)
       if (passes((int64_t)ent[i].count)) { b.h_ids.p[m++] = ent[i].rep; tab.count.push_back((int64_t)ent[i].count); }
     if (want_sets && m) {
-      int rc = fetch_sets(m);
+      rc = split_fetch_sets(0, m);
       if (rc) return rc;
       tab.bits.assign(b.h_bits.p, b.h_bits.p + m * (size_t)words);
     }
@@ -169,9 +202,8 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
   // true key collisions (in practice only under the test option split_key_bits): the sets of every representative and of every
   // cluster on the overflow list, then the overflow clusters one by one through an exact index -- in cluster order, so that the
   // result does not depend on the order the device appended them in
-  std::sort(b.h_ids.p + D, b.h_ids.p + D + n_ovf);
   for (uint32_t i = 0; i < D; i++) b.h_ids.p[i] = ent[i].rep;
-  int rc = fetch_sets((size_t)D + n_ovf);
+  rc = split_fetch_sets(0, (size_t)D + n_ovf);
   if (rc) return rc;
   std::vector<uint32_t> rows(b.h_bits.p, b.h_bits.p + (size_t)D * (size_t)words);
   std::vector<int64_t> cnt((size_t)D);
@@ -182,7 +214,6 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
   std::vector<int64_t> target_row((size_t)std::max(C, 0), -1);
   for (uint32_t k = 0; k < n_ovf; k++) {
     const uint32_t g = b.h_ids.p[D + k];
-    if (g >= M) { set_error("split summary: overflow entry out of range"); return MPF_E_STATE; }
     const uint32_t *w = b.h_bits.p + ((size_t)D + k) * (size_t)words;
     int64_t row = idx.find(rows, w);
     if (row < 0) {
