@@ -16,6 +16,8 @@
 
 namespace mpf {
 
+static_assert(sizeof(PlanOp) == sizeof(NvOp) && offsetof(PlanOp, pad) == offsetof(NvOp, pad), "refresh_stage sizes the ops as NvOp");
+
 static inline double now_ms()
 {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -181,8 +183,7 @@ int Engine::init(const mpf_config &cfg, const uint8_t *codes, const int32_t *wei
   reset_node_order();                              // (nodep[i] = node i's first record, as the reference's tree set-up leaves it: a caller need not ask for it)
   sc_.assign(back_.size(), 0);
   valid_.assign(back_.size(), 0);
-  lev_.assign(back_.size(), 0);
-  lev_epoch_.assign(back_.size(), 0);
+  plan_.bind(n_, back_.data(), valid_.data(), back_.size());
   nvis_val_.assign(back_.size() * 16, 0);
   nvis_epoch_.assign(back_.size() * 16, 0);
   reset_node_order();
@@ -412,7 +413,7 @@ void Engine::node_rectifier()
 {
   start_ = nodep_[1];
   int count = 0;
-  std::vector<int> &stack = sv_stack_;             // (a member: this runs once per sweep, an allocation would show)
+  std::vector<int> &stack = plan_.stack;           // (a member: this runs once per sweep, an allocation would show)
   stack.clear();
   stack.push_back(back_[start_]);
   while (!stack.empty()) {
@@ -570,101 +571,6 @@ int Engine::count_visits(int q, int m)
   return v;
 }
 
-// Cut the refresh's dependency graph (ops = `order`, topologically sorted) into chains for k_newview_chain: op j continues
-// the chain of op d when d is j's ONLY stale input (its other input is valid already, so the wave can prefetch it); of the
-// up to two consumers of d the one with the longer path above it continues, the other starts a chain of the next level.
-// A chain's level is one more than the deepest chain it takes an input from; per level the chains are spread over the 16
-// waves of a workgroup, longest first.
-void Engine::build_chains(const std::vector<int> &order)
-{
-  const int N = (int)order.size();
-  if (sv_idx_.size() != back_.size()) sv_idx_.assign(back_.size(), 0);
-  for (int i = 0; i < N; i++) sv_idx_[(size_t)order[(size_t)i]] = i;
-  auto dep_of = [&](int x) { return (!tip(x) && lev_epoch_[x] == epoch_) ? sv_idx_[(size_t)x] : -1; };
-  ch_d0_.resize((size_t)N); ch_d1_.resize((size_t)N); ch_h_.assign((size_t)N, 0); ch_next_.assign((size_t)N, -1);
-  ch_chain_.resize((size_t)N);
-  for (int i = 0; i < N; i++) {
-    const int r = order[(size_t)i];
-    ch_d0_[(size_t)i] = dep_of(back_[nx(r)]);
-    ch_d1_[(size_t)i] = dep_of(back_[nx(nx(r))]);
-  }
-  for (int i = N - 1; i >= 0; i--) {
-    const int h = ch_h_[(size_t)i] + 1;
-    const int d0 = ch_d0_[(size_t)i], d1 = ch_d1_[(size_t)i];
-    if (d0 >= 0 && ch_h_[(size_t)d0] < h) ch_h_[(size_t)d0] = h;
-    if (d1 >= 0 && ch_h_[(size_t)d1] < h) ch_h_[(size_t)d1] = h;
-  }
-  auto single = [&](int j) { const int d0 = ch_d0_[(size_t)j], d1 = ch_d1_[(size_t)j]; return (d0 >= 0) != (d1 >= 0) ? (d0 >= 0 ? d0 : d1) : -1; };
-  for (int j = 0; j < N; j++) {
-    const int d = single(j);
-    if (d >= 0 && (ch_next_[(size_t)d] < 0 || ch_h_[(size_t)j] > ch_h_[(size_t)ch_next_[(size_t)d]])) ch_next_[(size_t)d] = j;
-  }
-  // chains in order of their heads; level of a chain from its head's inputs
-  ch_head_.clear(); ch_len_.clear(); ch_slev_.clear();
-  int nlev = 0;
-  for (int j = 0; j < N; j++) {
-    const int d = single(j);
-    if (d >= 0 && ch_next_[(size_t)d] == j) continue;           // a link, reached from its head
-    const int c = (int)ch_head_.size();
-    int lev = 0;
-    if (ch_d0_[(size_t)j] >= 0) lev = std::max(lev, ch_slev_[(size_t)ch_chain_[(size_t)ch_d0_[(size_t)j]]] + 1);
-    if (ch_d1_[(size_t)j] >= 0) lev = std::max(lev, ch_slev_[(size_t)ch_chain_[(size_t)ch_d1_[(size_t)j]]] + 1);
-    int len = 0;
-    for (int k = j; k >= 0; k = ch_next_[(size_t)k]) { ch_chain_[(size_t)k] = c; len++; }
-    ch_head_.push_back(j);
-    ch_len_.push_back(len);
-    ch_slev_.push_back(lev);
-    nlev = std::max(nlev, lev + 1);
-  }
-  const int C = (int)ch_head_.size();
-  // per level: chains longest first onto the least loaded wave
-  ch_lev_off_.assign((size_t)nlev + 1, 0);
-  for (int c = 0; c < C; c++) ch_lev_off_[(size_t)ch_slev_[(size_t)c] + 1]++;
-  for (int l = 0; l < nlev; l++) ch_lev_off_[(size_t)l + 1] += ch_lev_off_[(size_t)l];
-  ch_sorted_.resize((size_t)C);
-  {
-    std::vector<int> &fill = sv_fill_;
-    fill.assign(ch_lev_off_.begin(), ch_lev_off_.end() - 1);
-    for (int c = 0; c < C; c++) ch_sorted_[(size_t)fill[(size_t)ch_slev_[(size_t)c]]++] = c;
-  }
-  ch_wave_.resize((size_t)C);
-  ch_off_.assign((size_t)nlev * 16 + 1, 0);
-  for (int l = 0; l < nlev; l++) {
-    int *b = ch_sorted_.data() + ch_lev_off_[(size_t)l], *e = ch_sorted_.data() + ch_lev_off_[(size_t)l + 1];
-    if (e - b > 16) std::sort(b, e, [&](int x, int y) { return ch_len_[(size_t)x] != ch_len_[(size_t)y] ? ch_len_[(size_t)x] > ch_len_[(size_t)y] : x < y; });
-    int load[16] = {0};
-    for (int *p = b; p < e; p++) {
-      int w = 0;
-      for (int k = 1; k < 16; k++) if (load[k] < load[w]) w = k;
-      ch_wave_[(size_t)*p] = w;
-      load[w] += ch_len_[(size_t)*p];
-    }
-    for (int w = 0; w < 16; w++) ch_off_[(size_t)l * 16 + (size_t)w + 1] = load[w];
-  }
-  for (size_t i = 1; i < ch_off_.size(); i++) ch_off_[i] += ch_off_[i - 1];
-  // emit: position of every op
-  ch_ops_.resize((size_t)N);
-  {
-    std::vector<int> &fill = sv_fill_;
-    fill.assign(ch_off_.begin(), ch_off_.end() - 1);
-    for (int l = 0; l < nlev; l++)
-      for (int i = ch_lev_off_[(size_t)l]; i < ch_lev_off_[(size_t)l + 1]; i++) {
-        const int c = ch_sorted_[(size_t)i];
-        int &at = fill[(size_t)l * 16 + (size_t)ch_wave_[(size_t)c]];
-        bool first = true;
-        for (int k = ch_head_[(size_t)c]; k >= 0; k = ch_next_[(size_t)k]) {
-          const int r = order[(size_t)k];
-          ChainOp &o = ch_ops_[(size_t)at++];
-          o.rec = r;
-          // a link's memory operand is the input that is NOT the previous op
-          o.other = first ? -1 : (ch_d0_[(size_t)k] >= 0 ? back_[nx(nx(r))] : back_[nx(r)]);
-          first = false;
-        }
-      }
-  }
-  ch_levels_ = nlev;
-}
-
 // A new topology, nothing valid, the tree complete: the schedule of the refresh can be made on the device (k_sched)
 bool Engine::dev_sched_usable() const
 {
@@ -679,7 +585,9 @@ bool Engine::dev_sched_usable() const
 int Engine::schedule_views_dev(int sweep_maxtrav)
 {
   ScopedMs timer(stats.host_views_ms_total);
-  const size_t nops = 3 * (size_t)(n_ - 2);
+  RefreshShape s;
+  s.nops = 3 * (size_t)(n_ - 2);
+  s.maxlev = -1;                                   // (the level count stays on the device)
   const size_t n_prune = sweep_maxtrav > 0 ? 2 * (size_t)n_ - 2 : 0;
   if (kids_host_.size() != nslots_) kids_host_.assign(nslots_, make_uint2(0u, 0u));
   for (int v = n_ + 1; v <= 2 * n_ - 2; v++) {
@@ -691,23 +599,18 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
     k[2] = make_uint2(s0, s1);
   }
   kids_list_.clear();
-  // staging layout: [kids][prune records of the sweep][ops][level offsets][level count]; the first two go up in one copy
-  const size_t kids_bytes = nslots_ * sizeof(uint2);
-  const size_t nodep_off = (kids_bytes + 15) & ~(size_t)15;
-  const size_t ops_off = nodep_off + ((n_prune * sizeof(uint32_t) + 15) & ~(size_t)15);
-  const size_t lev_off_b = ops_off + ((nops * sizeof(NvOp) + 15) & ~(size_t)15);
-  const size_t nlev_off = lev_off_b + ((((size_t)n_ + 2) * sizeof(int32_t) + 15) & ~(size_t)15);
-  const size_t total_b = nlev_off + 64;
+  const size_t no_ride[2] = {0, 0};               // (the first two regions of the layout go up in one copy)
+  const RefreshStage sg = refresh_stage(nslots_, s.nops, (size_t)n_ + 2, n_prune, 64, 0, no_ride);
   // the topology array and the prune records stay in pinned host memory of their own (k_sched reads them over the bus: 40 KB,
   // no copy dispatch in front of the launch; nothing else writes this buffer, and a result of the launch is waited for before
   // the next one is prepared)
-  HIPCHK(h_kstage_.reserve(ops_off));
-  HIPCHK(d_vstage_.reserve(total_b));
-  std::memcpy(h_kstage_.p, kids_host_.data(), kids_bytes);
+  HIPCHK(h_kstage_.reserve(sg.ops_off));
+  HIPCHK(d_vstage_.reserve(sg.total));
+  std::memcpy(h_kstage_.p, kids_host_.data(), sg.kids_bytes);
   uint8_t *src = d_vstage_.p;
   SweepDescArgs sw;
   if (n_prune) {
-    uint32_t *np = reinterpret_cast<uint32_t *>(h_kstage_.p + nodep_off);
+    uint32_t *np = reinterpret_cast<uint32_t *>(h_kstage_.p + sg.nodep_off);
     for (size_t i = 0; i < n_prune; i++) np[i] = slot(nodep_[i + 1]);
     const size_t cap = 8 * n_prune;              // a prune node has two neighbourhoods of at most four parts ...
     HIPCHK(d_walk_.reserve(cap));
@@ -715,7 +618,7 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
     HIPCHK(h_dsw_.reserve(4 + cap));
     HIPCHK(d_prog_.reserve(scan_prog_bytes((int)cap)));
     HIPCHK(reserve_results(cap * 63));           // ... of at most 2^6 - 1 insertion tests each (everything the launches below touch is in place now)
-    sw.nodep = reinterpret_cast<const uint32_t *>(h_kstage_.p + nodep_off);
+    sw.nodep = np;
     sw.n_prune = (uint32_t)n_prune;
     sw.maxtrav = (uint32_t)sweep_maxtrav;
     sw.split_cands = (uint32_t)std::max(0, split_cands_);
@@ -723,396 +626,132 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
     sw.parts = d_parts_.p;
     sw.hdr_host = h_dsw_.p;
     sw.part_node = h_dsw_.p + 4;
-    sw.hdr_dev = reinterpret_cast<uint32_t *>(src + nlev_off) + 8;
+    sw.hdr_dev = reinterpret_cast<uint32_t *>(src + sg.nlev_off) + 8;
     __atomic_store_n(h_dsw_.p + 3, 0u, __ATOMIC_RELAXED);
     __atomic_store_n(h_dsw_.p + 2, 0u, __ATOMIC_RELAXED);
     walk_gen_++;                                 // whatever descriptors, program and part table were on the device are gone
     n_walk_ = 0;
     walk_out_ = 0;
     sweep_cache_valid_ = false;
+    s.sw = &sw;
   }
   kids_dirty_ = false;
   kids_upload_ = false;
   kids_dev_ready_ = true;
-  NvOp *dops = reinterpret_cast<NvOp *>(src + ops_off);
-  int32_t *dlo = reinterpret_cast<int32_t *>(src + lev_off_b);
-  int32_t *dnl = reinterpret_cast<int32_t *>(src + nlev_off);
-  const int tiles = std::max(tiles_for(g_), tiles_for_levels(g_));
-  HIPCHK(d_cntp_.reserve((size_t)tiles * nslots_));
-  zeroed_ptr_ = nullptr;
-  zeroed_words_ = 0;
-  for (int i = 0; i < 2; i++) ride_[i].dev = nullptr;
-  cnt_on_host_ = false;
-  HIPCHK(launch_sched(st_, reinterpret_cast<const uint2 *>(h_kstage_.p), (uint32_t)n_, (uint32_t)nops, dops, dlo, dnl, sw,
-                      reinterpret_cast<uint2 *>(src)));
-  if (timing_ >= 2) HIPCHK(hipEventRecord(ev2_, st_));   // (view kernel time = the refresh proper; k_sched reports its own: option sched_ticks)
+  HIPCHK(launch_sched(st_, reinterpret_cast<const uint2 *>(h_kstage_.p), (uint32_t)n_, (uint32_t)s.nops, reinterpret_cast<NvOp *>(src + sg.ops_off),
+                      reinterpret_cast<int32_t *>(src + sg.lev_off), reinterpret_cast<int32_t *>(src + sg.nlev_off), sw, reinterpret_cast<uint2 *>(src)));
+  int rc = launch_refresh(src, sg, s);            // (view kernel time = the refresh proper; k_sched reports its own: option sched_ticks)
+  if (rc) return rc;
+  // what the host still needs is a dependency order for the subtree scores (finish_views): the views looking away from
+  // start_, children first, then the ones looking towards it, parents first -- while the device works
+  const std::vector<int> &all = plan_.all;         // (preorder, three records per node, the first one facing start_)
+  plan_.whole_tree(start_);
+  upd_order_.resize(s.nops);
+  size_t at = 0;
+  if (all.size() != s.nops) { set_error("refresh schedule: the tree is not complete"); return MPF_E_STATE; }
+  for (size_t i = all.size(); i >= 3; i -= 3) upd_order_[at++] = all[i - 3];
+  for (size_t i = 0; i < all.size(); i += 3) { upd_order_[at++] = all[i + 1]; upd_order_[at++] = all[i + 2]; }
+  rc = commit_refresh(sg, s, true, 2, true);
+  if (n_prune) dsw_sched_gen_ = sched_gen_;       // the sweep descriptors belong to this schedule's topology
+  return rc;
+}
+
+// The launch of a refresh whose ops, offsets, topology deltas and rides lie at src + sg on the device, with what goes with it:
+// shared by the device-made schedule, the replay of the stored one and the host's plan (s.generic).
+int Engine::launch_refresh(const uint8_t *src, const RefreshStage &sg, const RefreshShape &s)
+{
+  const NvOp *dops = reinterpret_cast<const NvOp *>(src + sg.ops_off);
+  const int32_t *dlo = reinterpret_cast<const int32_t *>(src + sg.lev_off);
+  HIPCHK(d_cntp_.reserve((size_t)std::max(tiles_for(g_), tiles_for_levels(g_)) * nslots_));
+  if (timing_ >= 2) HIPCHK(hipEventRecord(ev2_, st_));
   RefreshExtra x;
-  x.n_lev_ptr = dnl;
-  if (n_prune && plan_ride_) {
+  if (s.maxlev < 0) x.n_lev_ptr = reinterpret_cast<const int32_t *>(src + sg.nlev_off);      // (made by k_sched: the count lives there)
+  // the word-major copy alone where the kernel has that shape and the copy is current; every other refresh reads rows
+  // (from scratch nothing is valid, the inputs are tips, current in both layouts: rows_ok_ holds and ensure_rows does nothing)
+  x.wm_only = refresh_wm_only(s.chains);
+  if (!x.wm_only) { const int rc = ensure_rows(); if (rc) return rc; }
+  x.rows = rows_ok_;                              // (chained kernel: keeps the rows current as long as they are)
+  // small batch: counts land in the host mirror
+  cnt_on_host_ = s.fold_inside && want_host_results_;
+  if (cnt_on_host_) x.cnt_host = h_cnt();
+  // what rode on this launch's upload, what it clears for the scan that follows: promises of earlier refreshes are void
+  for (int i = 0; i < 2; i++) ride_[i].dev = sg.ride_off[i] ? src + sg.ride_off[i] : nullptr;
+  const bool zero = s.ride && zero_req_ptr_;      // the outputs of the scan that follows, cleared by the refresh launch
+  x.zero_ptr = zeroed_ptr_ = zero ? zero_req_ptr_ : nullptr;
+  x.zero_words = (uint32_t)(zeroed_words_ = zero ? zero_req_words_ : 0);
+  if (s.sw && plan_ride_) {
     // the walk plan of the sweep rides on the refresh launch (extra workgroups on the CUs the refresh leaves idle): no dispatch
     // of its own between refresh and scan.  (The fold of the refresh's mutation counts does NOT ride on the scan launch: its
     // 588 000 strided 4-byte reads beside the scan's first waves made the scan 60 us longer -- measured, dropped.)
     x.wp_kids = reinterpret_cast<const uint2 *>(src);
     x.wp_n = (uint32_t)n_;
     x.wp_desc = d_walk_.p;
-    x.wp_hdr = sw.hdr_dev;
+    x.wp_hdr = s.sw->hdr_dev;
     x.wp_prog = d_prog_.p;
     x.wp_out = d_out();
-    x.wp_max_parts = (uint32_t)(8 * n_prune);
+    x.wp_max_parts = 8 * s.sw->n_prune;
   }
-  x.wm_only = refresh_wm_only(false);             // (nothing is valid: the inputs are tips, current in both layouts)
-  HIPCHK(launch_newview_levels(st_, g_, vec_base(), dops, dlo, 1, d_cntp_.p, (uint32_t)nslots_, d_cnt(), nullptr, x));
-  if (x.wm_only) rows_ok_ = false;
-  stats.view_launches++;
-  HIPCHK(launch_cntsum(st_, g_, dops, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), tiles_for_levels(g_)));
-  if (timing_ >= 2) { HIPCHK(hipEventRecord(ev3_, st_)); view_events_pending_ = true; }
-  cnt_copy_pending_ = true;
-  // what the host still needs is a dependency order for the subtree scores (finish_views): the views looking away from
-  // start_, children first, then the ones looking towards it, parents first -- while the device works
-  std::vector<int> &all = sv_all_, &stack = sv_stack_;
-  all.clear();
-  stack.clear();
-  stack.push_back(back_[start_]);
-  while (!stack.empty()) {
-    const int r = stack.back();
-    stack.pop_back();
-    if (tip(r)) continue;
-    all.push_back(r);
-    stack.push_back(back_[nx(nx(r))]);
-    stack.push_back(back_[nx(r)]);
-  }
-  upd_order_.resize(nops);
-  size_t at = 0;
-  if (3 * all.size() != nops) { set_error("refresh schedule: the tree is not complete"); return MPF_E_STATE; }
-  for (size_t i = all.size(); i-- > 0;) upd_order_[at++] = all[i];
-  for (int u : all) { upd_order_[at++] = nx(u); upd_order_[at++] = nx(nx(u)); }
-  for (int r : upd_order_) valid_[r] = 1;
-  all_invalid_ = false;
-  n_invalid_ = 0;
-  views_valid_ = true;
-  pending_scores_ = true;
-  sched_cache_valid_ = (plan_cache_ & 2) != 0;
-  sched_gen_++;
-  if (n_prune) dsw_sched_gen_ = sched_gen_;       // the sweep descriptors belong to this schedule's topology
-  sc_nlev_off_ = nlev_off;                         // (also where the diagnostics of the last k_sched launch are read from)
-  sched_on_dev_ = true;
-  if (sched_cache_valid_) {
-    sc_nops_ = nops;
-    sc_maxlev_ = -1;
-    sc_ops_off_ = ops_off;
-    sc_lev_off_b_ = lev_off_b;
-    sc_order_ = upd_order_;
-  }
-  stats.newview_ops += nops;
-  stats.algorithmic_bytes += (uint64_t)nops * 3u * (uint64_t)g_.S * (uint64_t)Wref_ * 4u;
-  return MPF_OK;
-}
-
-int Engine::schedule_views(const std::vector<int> *roots)
-{
-  if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
-  ScopedMs timer(stats.host_views_ms_total);
-  if (!roots && all_invalid_ && sched_cache_valid_ && !kids_dirty_ && !sankoff_) {
-    // the same topology as when the last from-scratch schedule was built (the tree was handed over again, re-weighted or
-    // re-evaluated): its ops, level offsets and the topology array are still on the device -- launch, nothing else
-    const uint8_t *src = d_vstage_.p;
-    const NvOp *dops = reinterpret_cast<const NvOp *>(src + sc_ops_off_);
-    const int32_t *dlo = reinterpret_cast<const int32_t *>(src + sc_lev_off_b_);
-    const size_t nops = sc_nops_;
-    const int tiles = std::max(tiles_for(g_), tiles_for_levels(g_));
-    HIPCHK(d_cntp_.reserve((size_t)tiles * nslots_));
-    zeroed_ptr_ = nullptr;
-    zeroed_words_ = 0;
-    for (int i = 0; i < 2; i++) ride_[i].dev = nullptr;
-    cnt_on_host_ = false;
-    if (timing_ >= 2) HIPCHK(hipEventRecord(ev2_, st_));
-    RefreshExtra x;
-    if (sc_maxlev_ < 0) x.n_lev_ptr = reinterpret_cast<const int32_t *>(src + sc_nlev_off_);      // (made by k_sched: the count lives there)
-    x.wm_only = refresh_wm_only(false);           // (nothing is valid: the inputs are tips, current in both layouts)
-    HIPCHK(launch_newview_levels(st_, g_, vec_base(), dops, dlo, sc_maxlev_ < 0 ? 1 : sc_maxlev_, d_cntp_.p, (uint32_t)nslots_, d_cnt(), nullptr, x));
-    if (x.wm_only) rows_ok_ = false;
-    stats.view_launches++;
-    HIPCHK(launch_cntsum(st_, g_, dops, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), tiles_for_levels(g_)));
-    if (timing_ >= 2) { HIPCHK(hipEventRecord(ev3_, st_)); view_events_pending_ = true; }
-    cnt_copy_pending_ = true;
-    if (!(g_.vw == 1 && g_.nv_pipe)) shadow_ok_ = false;          // (another refresh kernel than k_newview_wgq: row-major store only)
-    upd_order_ = sc_order_;
-    for (int r : upd_order_) valid_[r] = 1;
-    all_invalid_ = false;
-    n_invalid_ = 0;
-    views_valid_ = true;
-    pending_scores_ = true;
-    stats.newview_ops += nops;
-    stats.algorithmic_bytes += (uint64_t)nops * 3u * (uint64_t)g_.S * (uint64_t)Wref_ * 4u;
-    return MPF_OK;
-  }
-  if (!roots && dev_sched_usable()) return schedule_views_dev(0);
-  // scratch vectors are members: this runs once per scan batch, allocations would show
-  std::vector<int> &all = sv_all_;
-  all.clear();
-  if (!roots) {
-    // every record of the component containing start_
-    std::vector<int> &stack = sv_stack_;
-    std::vector<char> &seen = sv_seen_;
-    stack.clear();
-    seen.assign(2 * (size_t)n_ + 1, 0);
-    stack.push_back(back_[start_]);
-    while (!stack.empty()) {
-      const int r = stack.back();                  // the record by which the node is entered: it faces the root (start_)
-      stack.pop_back();
-      if (r < 0 || tip(r) || seen[num(r)]) continue;
-      seen[num(r)] = 1;
-      all.push_back(r);
-      all.push_back(nx(r));
-      all.push_back(nx(nx(r)));
-      stack.push_back(back_[nx(nx(r))]);
-      stack.push_back(back_[nx(r)]);
-    }
-    roots = &all;
-  }
-  // closure of invalid inputs, post-order, with dependency levels (epoch-stamped scratch arrays)
-  epoch_++;
-  std::vector<int> &order = sv_order_;
-  std::vector<std::pair<int, int>> &stack = sv_pairs_;
-  order.clear();
-  stack.clear();
-  auto lev_of = [&](int r) { return (tip(r) || lev_epoch_[r] != epoch_) ? 0 : lev_[r]; };
-  const bool from_scratch = roots == &all && all_invalid_;
-  if (from_scratch) {
-    // nothing is valid (new topology): two sweeps over the tree rooted at start_ instead of the generic closure.
-    // `all` lists the nodes in preorder, three records each, the first one facing the root.
-    // views looking away from the root, children first: level = height
-    for (size_t i = all.size(); i >= 3; i -= 3) {
-      const int u = all[i - 3];
-      const int a = back_[nx(u)], b = back_[nx(nx(u))];
-      lev_[u] = 1 + std::max(tip(a) ? 0 : lev_[a], tip(b) ? 0 : lev_[b]);
-      lev_epoch_[u] = epoch_;
-      order.push_back(u);
-    }
-    // views looking towards the root, parents first: inputs are the parent's view towards us and the sibling's subtree
-    for (size_t i = 0; i < all.size(); i += 3) {
-      const int u = all[i], r1 = nx(u), r2 = nx(r1);
-      const int p = back_[u], c1 = back_[r1], c2 = back_[r2];
-      const int lp = tip(p) ? 0 : lev_[p];
-      lev_[r1] = 1 + std::max(lp, tip(c2) ? 0 : lev_[c2]);
-      lev_[r2] = 1 + std::max(lp, tip(c1) ? 0 : lev_[c1]);
-      lev_epoch_[r1] = lev_epoch_[r2] = epoch_;
-      order.push_back(r1);
-      order.push_back(r2);
-    }
-  }
-  for (int r0 : *roots) {
-    if (from_scratch) break;
-    if (r0 < 0 || tip(r0) || valid_[r0] || lev_epoch_[r0] == epoch_) continue;
-    stack.emplace_back(r0, 0);
-    while (!stack.empty()) {
-      auto &top = stack.back();
-      const int r = top.first;
-      const int a = back_[nx(r)], b = back_[nx(nx(r))];
-      if (top.second == 0) {
-        top.second = 1;
-        if (!tip(a) && !valid_[a] && lev_epoch_[a] != epoch_) { stack.emplace_back(a, 0); continue; }
-      }
-      if (top.second == 1) {
-        top.second = 2;
-        if (!tip(b) && !valid_[b] && lev_epoch_[b] != epoch_) { stack.emplace_back(b, 0); continue; }
-      }
-      if (lev_epoch_[r] != epoch_) {
-        lev_[r] = 1 + std::max(lev_of(a), lev_of(b));
-        lev_epoch_[r] = epoch_;
-        order.push_back(r);
-      }
-      stack.pop_back();
-    }
-  }
-  const size_t nops = order.size();
-  const bool full = roots == &all;
-  if (kids_host_.size() != nslots_) kids_host_.assign(nslots_, make_uint2(0u, 0u));
-  // chained refresh for the incremental case (few ops, deep and narrow: paths away from an edit); a refresh of most of the
-  // tree is wide, the level kernel's two-ops-in-flight loop suits it and cutting it into chains would cost the host more
-  // than it saves the device
-  const bool chains = views_mode_ == 2 && !sankoff_ && nops > 0 && (long)nops <= chain_max_ops_ && g_.S * g_.vw <= 8;   // (wider tiles would not fit four register sets)
-  // ... and then the kernel reads its few KB of input (ops, offsets, topology updates) straight from the pinned staging
-  // buffer: no copy dispatch in front of it
-  const bool direct = chains && kids_dev_ready_ && (kids_dirty_ ? roots->size() + nops : kids_list_.size()) <= 4096;
-  kid_upd_.clear();
-  if (!kids_dirty_ && !kids_list_.empty()) {
-    for (int r : kids_list_) {
-      if (back_[r] < 0) continue;
-      const uint2 k = make_uint2(slot(back_[nx(r)]), slot(back_[nx(nx(r))]));
-      kids_host_[slot(r)] = k;
-      if (direct) { kid_upd_.push_back(slot(r)); kid_upd_.push_back(k.x); kid_upd_.push_back(k.y); }
-    }
-    kids_list_.clear();
-    kids_upload_ = !direct;                        // the mirror changed: a non-direct refresh uploads it whole
-  }
-  if (kids_dirty_) {
-    // topology for the device-walked scans: kids[cid] = the two records behind an inner record
-    auto put = [&](int r) {
-      const uint2 k = make_uint2(slot(back_[nx(r)]), slot(back_[nx(nx(r))]));
-      kids_host_[slot(r)] = k;
-      if (direct) { kid_upd_.push_back(slot(r)); kid_upd_.push_back(k.x); kid_upd_.push_back(k.y); }
-    };
-    for (int r : *roots)
-      if (r >= 0 && !tip(r)) put(r);
-    if (!full)                                     // (a full refresh's roots contain every op)
-      for (int r : order) put(r);
-  }
-  int maxlev = 0;
-  for (int r : order) maxlev = std::max(maxlev, lev_[r]);
-  if (chains) build_chains(order);                 // -> ch_ops_ (op order), ch_off_ (per level and wave), ch_levels_
-  // staging layout: [kids][ops][level offsets], one upload
-  const size_t kids_bytes = nslots_ * sizeof(uint2);
-  const size_t ops_off = (kids_bytes + 15) & ~(size_t)15;
-  const size_t lev_off_b = ops_off + ((nops * sizeof(NvOp) + 15) & ~(size_t)15);
-  const size_t n_off = chains ? ch_off_.size() : (size_t)maxlev + 2;
-  const size_t total_b = lev_off_b + ((n_off * sizeof(int32_t) + 15) & ~(size_t)15);
-  const size_t upd_b = (kid_upd_.size() * sizeof(uint32_t) + 15) & ~(size_t)15;
-  // the following scan's input rides along (Fitch refresh kernels also clear its outputs); not without a launch
-  const bool can_ride = !sankoff_ && nops > 0 && views_mode_ >= 1;
-  zeroed_ptr_ = nullptr;                           // (a promise from an earlier refresh that nobody collected is void)
-  zeroed_words_ = 0;
-  size_t ride_off[2] = {0, 0}, tail = total_b + upd_b;
-  for (int i = 0; i < 2; i++) {
-    ride_[i].dev = nullptr;
-    if (can_ride && ride_[i].src && ride_[i].bytes) { ride_off[i] = tail; tail += (ride_[i].bytes + 15) & ~(size_t)15; }
-  }
-  HIPCHK(h_vstage_.reserve(tail));
-  for (int i = 0; i < 2; i++)
-    if (ride_off[i]) std::memcpy(h_vstage_.p + ride_off[i], ride_[i].src, ride_[i].bytes);
-  if (direct) {
-    if (!kid_upd_.empty()) std::memcpy(h_vstage_.p + total_b, kid_upd_.data(), kid_upd_.size() * sizeof(uint32_t));
-    HIPCHK(d_cstage_.reserve(tail - ops_off));
-  } else {
-    HIPCHK(d_vstage_.reserve(tail));               // (may move: the whole topology is uploaded again below)
-    std::memcpy(h_vstage_.p, kids_host_.data(), kids_bytes);
-  }
-  NvOp *hops = reinterpret_cast<NvOp *>(h_vstage_.p + ops_off);
-  int32_t *lo = reinterpret_cast<int32_t *>(h_vstage_.p + lev_off_b);   // lo[0..maxlev]: offsets of levels 1..maxlev
-  if (chains) {
-    upd_order_.resize(nops);
-    for (size_t at = 0; at < nops; at++) {
-      const ChainOp &c = ch_ops_[at];
-      const int r = c.rec;
-      NvOp &o = hops[at];
-      o.dst = slot(r);
-      o.a = c.other < 0 ? slot(back_[nx(r)]) : 0xFFFFFFFFu;        // a link takes the previous result from registers
-      o.b = c.other < 0 ? slot(back_[nx(nx(r))]) : slot(c.other);
-      o.pad = (uint32_t)r;
-      upd_order_[at] = r;
-    }
-    std::memcpy(lo, ch_off_.data(), ch_off_.size() * sizeof(int32_t));
-  } else if (nops) {
-    for (int l = 0; l <= maxlev + 1; l++) lo[l] = 0;
-    for (int r : order) lo[lev_[r]]++;
-    int acc = 0;
-    for (int l = 1; l <= maxlev; l++) { const int c = lo[l]; lo[l] = acc; acc += c; }
-    lo[0] = 0;
-    std::vector<int> &fill = sv_fill_;
-    fill.assign(lo, lo + maxlev + 1);
-    upd_order_.resize(nops);
-    for (int r : order) {
-      const int at = fill[lev_[r]]++;
-      NvOp &o = hops[at];
-      o.dst = slot(r);
-      o.a = slot(back_[nx(r)]);
-      o.b = slot(back_[nx(nx(r))]);
-      o.pad = (uint32_t)r;
-      upd_order_[(size_t)at] = r;
-    }
-    for (int l = 1; l <= maxlev; l++) lo[l - 1] = lo[l];
-    lo[maxlev] = (int32_t)nops;
-  }
-  if (direct) {
-    // one small upload (ops, offsets, topology deltas, scan descriptors); the topology array itself stays where it is
-    // (letting the kernels read the pinned buffer itself instead costs more than this copy: 25 workgroups fetching their
-    //  descriptors over PCIe -- a C3 climb takes 0.35 s instead of 0.29 s)
-    HIPCHK(hipMemcpyAsync(d_cstage_.p, h_vstage_.p + ops_off, tail - ops_off, hipMemcpyHostToDevice, st_));
-    if (full) kids_dirty_ = false;
-  } else if (kids_dirty_ || kids_upload_ || nops) {
-    kids_upload_ = false;
-    const size_t up = nops ? tail : kids_bytes;
-    HIPCHK(hipMemcpyAsync(d_vstage_.p, h_vstage_.p, up, hipMemcpyHostToDevice, st_));
-    kids_dev_ready_ = true;
-    if (full) kids_dirty_ = false;
-  }
-  if (nops == 0) {
-    if (!direct) sched_cache_valid_ = false;       // (d_vstage_ may have been rewritten above)
-    if (full) { n_invalid_ = 0; views_valid_ = true; }
-    return MPF_OK;
-  }
-  const uint8_t *src = direct ? d_cstage_.p - ops_off : d_vstage_.p;      // (same offsets in both layouts)
-  const NvOp *dops = reinterpret_cast<const NvOp *>(src + ops_off);
-  const int32_t *dlo = reinterpret_cast<const int32_t *>(src + lev_off_b);
-  const int tiles = std::max(tiles_for(g_), tiles_for_levels(g_));
-  HIPCHK(d_cntp_.reserve((size_t)tiles * nslots_));
-  if (timing_ >= 2) HIPCHK(hipEventRecord(ev2_, st_));
-  // the per-tile mutation counts are folded by the refresh kernel's last workgroup when there are few ops, by a separate
-  // chip-wide launch when there are many (one workgroup would need longer than the launch costs)
-  const bool fold_inside = views_mode_ >= 1 && !sankoff_ && nops <= 512;   // (independent of chain_max_ops_)
-  RefreshExtra x;
-  // the word-major copy alone where the kernel has that shape and the copy is current; every other refresh reads rows
-  x.wm_only = refresh_wm_only(chains);
-  if (!x.wm_only) { const int rc = ensure_rows(); if (rc) return rc; }
   uint32_t *const vec = vec_base();
-  x.rows = rows_ok_;                              // (chained kernel: keeps the rows current as long as they are)
-  cnt_on_host_ = false;
-  if (fold_inside && want_host_results_) { x.cnt_host = h_cnt(); cnt_on_host_ = true; }   // small batch: counts land in the host mirror
-  for (int i = 0; i < 2; i++)
-    if (ride_off[i]) ride_[i].dev = src + ride_off[i];
-  bool can_ride_used = ride_off[0] || ride_off[1];
-  if (can_ride && zero_req_ptr_) {
-    x.zero_ptr = zero_req_ptr_;                   // the outputs of the scan that follows, cleared by the refresh launch
-    x.zero_words = (uint32_t)zero_req_words_;
-    zeroed_ptr_ = zero_req_ptr_;
-    zeroed_words_ = zero_req_words_;
-    can_ride_used = true;
-  }
-  if (chains) {
-    if (direct) {
-      x.kid_upd = reinterpret_cast<const uint32_t *>(src + total_b);
-      x.n_kid_upd = (int)(kid_upd_.size() / 3);
+  uint32_t *const done = s.fold_inside ? d_done_.p : nullptr;
+  if (s.chains) {
+    if (s.direct) {
+      x.kid_upd = reinterpret_cast<const uint32_t *>(src + sg.upd_off);
+      x.n_kid_upd = (int)(plan_.kid_upd.size() / 3);
       x.kids = reinterpret_cast<uint2 *>(d_vstage_.p);
     }
-    HIPCHK(launch_newview_chains(st_, g_, vec, dops, dlo, ch_levels_, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), fold_inside ? d_done_.p : nullptr, x));
+    HIPCHK(launch_newview_chains(st_, g_, vec, dops, dlo, plan_.ch_levels, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), done, x));
     stats.view_launches++;
-  } else if (views_mode_ >= 1) {
+  } else if (views_mode_ >= 1) {                  // (always so for a device-made or stored schedule)
     // narrow levels (the partial trees of the addition phase, small refreshes): fewer waves per workgroup -- a wave of the
-    // one-word-per-lane kernel takes 64 / tile ops per round, so 2 x (ops per level) x tile / 64 waves cover a level in two rounds
-    if (nv_waves_ > 0) x.waves_hint = nv_waves_;
-    else if (nv_waves_ == 0 && maxlev > 0 && g_.vw == 1 && g_.nv_pipe && !sankoff_) {
-      const long per_level = ((long)nops + maxlev - 1) / maxlev;
+    // one-word-per-lane kernel takes 64 / tile ops per round, so 2 x (ops per level) x tile / 64 waves cover a level in two rounds.
+    // (the host's plan only: a device-made schedule's level count is not known here; the replay of a host-made one never had the hint)
+    if (s.generic && nv_waves_ > 0) x.waves_hint = nv_waves_;
+    else if (s.generic && nv_waves_ == 0 && s.maxlev > 0 && g_.vw == 1 && g_.nv_pipe && !sankoff_) {
+      const long per_level = ((long)s.nops + s.maxlev - 1) / s.maxlev;
       const long need = (2 * per_level * newview_tile(g_) + 63) / 64;
       x.waves_hint = need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
     }
-    HIPCHK(launch_newview_levels(st_, g_, vec, dops, dlo, maxlev, d_cntp_.p, (uint32_t)nslots_, d_cnt(), fold_inside ? d_done_.p : nullptr, x));
+    HIPCHK(launch_newview_levels(st_, g_, vec, dops, dlo, s.maxlev < 0 ? 1 : s.maxlev, d_cntp_.p, (uint32_t)nslots_, d_cnt(), done, x));
     if (x.wm_only) rows_ok_ = false;              // (k_newview_wgq's word-major shape writes no rows)
     stats.view_launches++;
   } else {
-    for (int l = 0; l < maxlev; l++) {
+    const int32_t *lo = reinterpret_cast<const int32_t *>(h_vstage_.p + sg.lev_off);
+    for (int l = 0; l < s.maxlev; l++) {
       HIPCHK(launch_newview(st_, g_, vec, dops + lo[l], lo[l + 1] - lo[l], d_cntp_.p, (uint32_t)nslots_));
       stats.view_launches++;
     }
   }
-  if (!fold_inside)
+  // the per-tile mutation counts are folded by the refresh kernel's last workgroup when there are few ops (s.fold_inside), by a
+  // separate chip-wide launch when there are many (one workgroup would need longer than the launch costs)
+  if (!s.fold_inside)
     // (no host mirror here: hundreds of scattered 4-byte writes over PCIe cost more than the one copy-back they would save)
-    HIPCHK(launch_cntsum(st_, g_, dops, (int)nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(),
-                         (views_mode_ >= 1 && !chains) ? tiles_for_levels(g_) : 0));   // rows of cntp the refresh kernel wrote
+    HIPCHK(launch_cntsum(st_, g_, dops, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(),
+                         (views_mode_ >= 1 && !s.chains) ? tiles_for_levels(g_) : 0));   // rows of cntp the refresh kernel wrote
   if (timing_ >= 2) { HIPCHK(hipEventRecord(ev3_, st_)); view_events_pending_ = true; }
   cnt_copy_pending_ = true;                 // copied back together with the scan results (or by update_views)
-  {
-    // shadow_ok_ = "every valid vector is current in the word-major copy": true whenever nothing is valid (invalidate_all /
-    // _vectors), kept by k_newview_wgq and k_newview_chain, which always write that copy, lost when any other kernel writes vectors.
-    // rows_ok_ = the same for the row-major layout of the inner vectors: lost behind a refresh that wrote the word-major copy alone
-    // (above: k_newview_wgq's word-major shape; the chained kernel writes rows as long as they are current), restored by ensure_rows
-    const bool both = views_mode_ >= 1 && !sankoff_ && g_.vw == 1 && g_.shoff != 0 && (chains || g_.nv_pipe);
-    if (!both) shadow_ok_ = false;
-  }
-  for (int r : order) valid_[r] = 1;
+  return MPF_OK;
+}
+
+// The books behind a launched refresh of the vectors in upd_order_.  made: who wrote the schedule in d_vstage_ -- 0 nobody (a
+// replay, or the small upload beside it), 1 the host, 2 k_sched; cacheable: it may be replayed while the topology stays.
+int Engine::commit_refresh(const RefreshStage &sg, const RefreshShape &s, bool full, int made, bool cacheable)
+{
+  // shadow_ok_ = "every valid vector is current in the word-major copy": true whenever nothing is valid (invalidate_all /
+  // _vectors), kept by k_newview_wgq and k_newview_chain, which always write that copy, lost when any other kernel writes vectors.
+  // rows_ok_ = the same for the row-major layout of the inner vectors: lost behind a refresh that wrote the word-major copy alone
+  // (launch_refresh: k_newview_wgq's word-major shape; the chained kernel writes rows as long as they are current), restored by
+  // ensure_rows.
+  // One predicate for the three routes.  The device route used to leave shadow_ok_ alone: dev_sched_usable() gives views_mode_ >= 1,
+  // !sankoff_, vw == 1 and nv_pipe, so `both` is shoff != 0 there, and with all_invalid_ shadow_ok_ is at most shoff != 0 already.
+  // The replay used to test vw == 1 && nv_pipe only: it runs with !sankoff_, the options views_mode / views_pipe / views_tile /
+  // dev_sched / plan_cache drop the stored schedule, so views_mode_ >= 1 as when it was stored, and shoff as before.
+  const bool both = views_mode_ >= 1 && !sankoff_ && g_.vw == 1 && g_.shoff != 0 && (s.chains || g_.nv_pipe);
+  if (!both) shadow_ok_ = false;
+  for (int r : upd_order_) valid_[r] = 1;
   all_invalid_ = false;
   if (full) { n_invalid_ = 0; views_valid_ = true; }
   else if (n_invalid_ > 0) {
-    n_invalid_ -= (long)nops;
+    n_invalid_ -= (long)s.nops;
     if (n_invalid_ <= 0) {
       n_invalid_ = 0;
       views_valid_ = true;
@@ -1122,24 +761,102 @@ int Engine::schedule_views(const std::vector<int> *roots)
     }
   }
   pending_scores_ = true;
-  if (!direct) {
-    // d_vstage_ was (re)written: it holds a reusable schedule only if this was the from-scratch refresh of the whole tree
-    // on the level kernel with the per-tile counts folded by the separate launch (the shape the fast path above replays)
-    sched_cache_valid_ = (plan_cache_ & 2) && from_scratch && full && !chains && views_mode_ >= 1 && !fold_inside && !sankoff_ && !can_ride_used;
+  if (made) {
+    // d_vstage_ was (re)written: a replay finds the layout, the level count (-1: on the device) and the order of the ops here
+    sched_cache_valid_ = (plan_cache_ & 2) && cacheable;
     sched_gen_++;
-    sched_on_dev_ = false;                         // (d_vstage_ was rewritten by the host's schedule)
-    if (sched_cache_valid_) {
-      sc_nops_ = nops;
-      sc_maxlev_ = maxlev;
-      sc_ops_off_ = ops_off;
-      sc_lev_off_b_ = lev_off_b;
-      sc_order_ = upd_order_;
-    }
+    sched_on_dev_ = made == 2;
+    sc_stage_ = sg;
+    if (sched_cache_valid_) { sc_maxlev_ = s.maxlev; sc_order_ = upd_order_; }
   }
-  stats.newview_ops += nops;
-  dbg_levels_ += (uint64_t)(chains ? ch_levels_ : maxlev);
-  stats.algorithmic_bytes += (uint64_t)nops * 3u * (uint64_t)g_.S * (uint64_t)Wref_ * 4u;
+  stats.newview_ops += s.nops;
+  if (s.maxlev >= 0) dbg_levels_ += (uint64_t)(s.chains ? plan_.ch_levels : s.maxlev);   // (a device-made schedule's are not known here)
+  stats.algorithmic_bytes += (uint64_t)s.nops * 3u * (uint64_t)g_.S * (uint64_t)Wref_ * 4u;
   return MPF_OK;
+}
+
+int Engine::schedule_views(const std::vector<int> *roots)
+{
+  if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
+  ScopedMs timer(stats.host_views_ms_total);
+  RefreshShape s;
+  if (!roots && all_invalid_ && sched_cache_valid_ && !kids_dirty_ && !sankoff_) {
+    // the same topology as when the last from-scratch schedule was built (the tree was handed over again, re-weighted or
+    // re-evaluated): its ops, level offsets and the topology array are still on the device -- launch, nothing else
+    s.nops = sc_order_.size();
+    s.maxlev = sc_maxlev_;
+    const int rc = launch_refresh(d_vstage_.p, sc_stage_, s);
+    if (rc) return rc;
+    upd_order_ = sc_order_;
+    return commit_refresh(sc_stage_, s, true, 0, false);
+  }
+  if (!roots && dev_sched_usable()) return schedule_views_dev(0);
+  const bool full = !roots;
+  if (full) { plan_.whole_tree(start_); roots = &plan_.all; }
+  const bool from_scratch = full && all_invalid_;  // nothing is valid (new topology): two sweeps instead of the generic closure
+  plan_.close(*roots, from_scratch);
+  if (kids_host_.size() != nslots_) kids_host_.assign(nslots_, make_uint2(0u, 0u));
+  s.generic = true;
+  const size_t nops = s.nops = plan_.order.size();
+  s.maxlev = plan_.maxlev;
+  // chained refresh for the incremental case (few ops, deep and narrow: paths away from an edit); a refresh of most of the
+  // tree is wide, the level kernel's two-ops-in-flight loop suits it and cutting it into chains would cost the host more
+  // than it saves the device
+  s.chains = views_mode_ == 2 && !sankoff_ && nops > 0 && (long)nops <= chain_max_ops_ && g_.S * g_.vw <= 8;   // (wider tiles would not fit four register sets)
+  // ... and then the kernel reads its few KB of input (ops, offsets, topology updates) straight from the pinned staging
+  // buffer: no copy dispatch in front of it
+  s.direct = s.chains && kids_dev_ready_ && (kids_dirty_ ? roots->size() + nops : kids_list_.size()) <= 4096;
+  s.fold_inside = views_mode_ >= 1 && !sankoff_ && nops <= 512;   // (independent of chain_max_ops_)
+  // the following scan's input rides along (Fitch refresh kernels also clear its outputs); not without a launch
+  s.ride = !sankoff_ && nops > 0 && views_mode_ >= 1;
+  const auto slot_of = [this](int r) { return slot(r); };
+  // topology for the device-walked scans: kids[cid] = the two records behind an inner record (wholesale, or the edited records)
+  if (plan_.topo_delta(reinterpret_cast<uint32_t *>(kids_host_.data()), kids_list_, kids_dirty_, *roots, full, s.direct, slot_of))
+    kids_upload_ = !s.direct;                      // the mirror changed: a non-direct refresh uploads it whole
+  kids_list_.clear();
+  if (s.chains) plan_.build_chains();
+  const size_t ride_bytes[2] = {s.ride && ride_[0].src ? ride_[0].bytes : 0, s.ride && ride_[1].src ? ride_[1].bytes : 0};
+  const RefreshStage sg = refresh_stage(nslots_, nops, s.chains ? plan_.ch_off.size() : (size_t)plan_.maxlev + 2, 0, 0, plan_.kid_upd.size(), ride_bytes);
+  HIPCHK(h_vstage_.reserve(sg.total));
+  for (int i = 0; i < 2; i++)
+    if (sg.ride_off[i]) std::memcpy(h_vstage_.p + sg.ride_off[i], ride_[i].src, ride_[i].bytes);
+  if (s.direct) {
+    if (!plan_.kid_upd.empty()) std::memcpy(h_vstage_.p + sg.upd_off, plan_.kid_upd.data(), plan_.kid_upd.size() * sizeof(uint32_t));
+    HIPCHK(d_cstage_.reserve(sg.total - sg.ops_off));
+  } else {
+    HIPCHK(d_vstage_.reserve(sg.total));           // (may move: the whole topology is uploaded again below)
+    std::memcpy(h_vstage_.p, kids_host_.data(), sg.kids_bytes);
+  }
+  NvOp *hops = reinterpret_cast<NvOp *>(h_vstage_.p + sg.ops_off);
+  int32_t *lo = reinterpret_cast<int32_t *>(h_vstage_.p + sg.lev_off);   // lo[0..maxlev]: offsets of levels 1..maxlev
+  if (s.chains) plan_.emit_chains(hops, lo, upd_order_, slot_of);
+  else if (nops) plan_.emit_levels(hops, lo, upd_order_, slot_of);
+  if (s.direct) {
+    // one small upload (ops, offsets, topology deltas, scan descriptors); the topology array itself stays where it is
+    // (letting the kernels read the pinned buffer itself instead costs more than this copy: 25 workgroups fetching their
+    //  descriptors over PCIe -- a C3 climb takes 0.35 s instead of 0.29 s)
+    HIPCHK(hipMemcpyAsync(d_cstage_.p, h_vstage_.p + sg.ops_off, sg.total - sg.ops_off, hipMemcpyHostToDevice, st_));
+    if (full) kids_dirty_ = false;
+  } else if (kids_dirty_ || kids_upload_ || nops) {
+    kids_upload_ = false;
+    HIPCHK(hipMemcpyAsync(d_vstage_.p, h_vstage_.p, nops ? sg.total : sg.kids_bytes, hipMemcpyHostToDevice, st_));
+    kids_dev_ready_ = true;
+    if (full) kids_dirty_ = false;
+  }
+  if (nops == 0) {
+    if (!s.direct) sched_cache_valid_ = false;     // (d_vstage_ may have been rewritten above)
+    if (full) { n_invalid_ = 0; views_valid_ = true; }
+    zeroed_ptr_ = nullptr;                         // (no launch: a promise from an earlier refresh that nobody collected is void, ...
+    zeroed_words_ = 0;
+    ride_[0].dev = ride_[1].dev = nullptr;         //  ... and nothing rode)
+    return MPF_OK;
+  }
+  const int rc = launch_refresh(s.direct ? d_cstage_.p - sg.ops_off : d_vstage_.p, sg, s);   // (same offsets in both layouts)
+  if (rc) return rc;
+  // d_vstage_ holds a reusable schedule only if this was the from-scratch refresh of the whole tree on the level kernel with
+  // the per-tile counts folded by the separate launch and nothing riding (the shape the fast path above replays)
+  const bool rode = zeroed_ptr_ || sg.ride_off[0] || sg.ride_off[1];
+  return commit_refresh(sg, s, full, s.direct ? 0 : 1, from_scratch && !s.chains && views_mode_ >= 1 && !s.fold_inside && !sankoff_ && !rode);
 }
 
 // subtree scores in dependency order (reference: tr->parsimonyScore[p] = total + score[q] + score[r], :874);
@@ -2265,7 +1982,7 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "sched_levels" || key == "sched_ticks" || key == "sched_desc_ticks") {
     // diagnostics of the last device-made schedule: dependency levels, duration of k_sched's two workgroups (10 ns ticks)
     int32_t w[16] = {0};
-    if (sched_on_dev_ && d_vstage_.p) { (void)hipStreamSynchronize(st_); (void)hipMemcpy(w, d_vstage_.p + sc_nlev_off_, 64, hipMemcpyDeviceToHost); }
+    if (sched_on_dev_ && d_vstage_.p) { (void)hipStreamSynchronize(st_); (void)hipMemcpy(w, d_vstage_.p + sc_stage_.nlev_off, 64, hipMemcpyDeviceToHost); }
     *v = w[key == "sched_levels" ? 0 : key == "sched_ticks" ? 1 : 2];
   }
   else if (key == "split_below") *v = split_below_;

@@ -27,6 +27,7 @@
 #include "../host/rng.hpp"
 #include "../host/ufb_books.hpp"
 #include "../host/split_sets.hpp"
+#include "../host/refresh_plan.hpp"
 #include "climb.hpp"
 #include "kernels.hpp"
 #include "ufboot.hpp"
@@ -285,6 +286,11 @@ class Engine {
   int schedule_views(const std::vector<int> *roots);   // enqueue (no sync); nullptr = every record of the tree
   bool dev_sched_usable() const;
   int schedule_views_dev(int sweep_maxtrav);
+  // one refresh as its route describes it to the shared tail (launch_refresh, commit_refresh); maxlev < 0: the level count is on the device
+  struct RefreshShape { size_t nops = 0; int maxlev = 0; bool chains = false, direct = false, fold_inside = false, generic = false, ride = false;
+                        const SweepDescArgs *sw = nullptr; };
+  int launch_refresh(const uint8_t *src, const RefreshStage &sg, const RefreshShape &s);
+  int commit_refresh(const RefreshStage &sg, const RefreshShape &s, bool full, int made, bool cacheable);
   int sweep_scan_dev(int maxtrav, uint64_t *n_tests, uint32_t *min_mp);
   void finish_views();                         // after a stream sync: subtree scores of the refreshed vectors
   void collect_scan_roots(int p, int mintrav, int maxtrav, std::vector<int> &roots) const;
@@ -776,23 +782,13 @@ private:
   DevBuf<uint32_t> d_done_;                      // finished-workgroup counter of k_newview_wg (zero between launches)
   const uint2 *d_kids() const { return reinterpret_cast<const uint2 *>(d_vstage_.p); }
   std::vector<uint8_t> valid_;
-  std::vector<int32_t> lev_, lev_epoch_;
-  int32_t epoch_ = 0;
+  RefreshPlanner plan_;                         // the host's refresh schedule and its scratch (host/refresh_plan.hpp)
   std::vector<int> upd_order_;
-  std::vector<int> sv_all_, sv_stack_, sv_order_, sv_fill_;      // schedule_views scratch
-  std::vector<char> sv_seen_;
-  std::vector<std::pair<int, int>> sv_pairs_;
   bool pending_scores_ = false, kids_dirty_ = true, view_events_pending_ = false;
   long n_invalid_ = -1;                         // -1 = unknown/many, 0 = every vector valid
   int split_below_ = 64;                        // batches of at most this many prune nodes are cut into 4 parts per scan
   int split_cands_ = 64;                        // larger batches: only neighbourhoods with more insertion tests than this are cut
   int views_mode_ = 2;                          // 2 = chained refresh, 1 = all levels in one launch, 0 = one launch per level
-  struct ChainOp { int rec, other; };           // other < 0: chain head (both operands from memory)
-  void build_chains(const std::vector<int> &order);
-  std::vector<int> sv_idx_, ch_d0_, ch_d1_, ch_h_, ch_next_, ch_chain_, ch_head_, ch_len_, ch_slev_, ch_lev_off_, ch_sorted_, ch_wave_;
-  std::vector<int32_t> ch_off_;
-  std::vector<ChainOp> ch_ops_;
-  int ch_levels_ = 0;
   long chain_max_ops_ = 512;                    // refreshes with more ops use the level kernel
   // small refreshes upload only ops, offsets, topology DELTAS and the following scan's descriptors (d_cstage_); the device
   // copy of the topology (d_vstage_) must have been uploaded whole once before
@@ -802,7 +798,6 @@ private:
   // refresh's own upload when one happens; dev = where it landed, nullptr if the scan has to upload it itself
   struct Ride { const void *src = nullptr; size_t bytes = 0; const void *dev = nullptr; };
   Ride ride_[2];
-  std::vector<uint32_t> kid_upd_;
   std::vector<int> kids_list_;                  // records whose kids[] entry changed since the device copy was last complete
   bool kids_upload_ = false;
   // sweep_scan wants the best candidate per prune node only: the device reduces every scan part and writes the minima to the
@@ -835,8 +830,8 @@ private:
   // refresh (ops by level, in d_vstage_) and the plans / descriptors / device program of a whole sweep
   int plan_cache_ = 7;
   bool sched_cache_valid_ = false;
-  size_t sc_nops_ = 0, sc_ops_off_ = 0, sc_lev_off_b_ = 0, sc_nlev_off_ = 0;
-  int sc_maxlev_ = 0;                           // < 0: the schedule was made on the device, its level count lives at sc_nlev_off_
+  RefreshStage sc_stage_ = {};                  // layout of the schedule in d_vstage_ (the cached one; also where k_sched's diagnostics are read)
+  int sc_maxlev_ = 0;                           // < 0: the schedule was made on the device, its level count lives at sc_stage_.nlev_off
   bool dev_sched_ = true;                       // option dev_sched
   bool dev_plan_ = true;                        // option dev_plan: a whole sweep's scan descriptors laid out on the device too
   PinBuf<uint8_t> h_kstage_;                    // topology array + prune records of a device-scheduled refresh (read by k_sched from host memory)

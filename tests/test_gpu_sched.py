@@ -45,25 +45,69 @@ def test_device_schedule_equals_host_schedule(mods, n, P, alpha):
     trees.validate(back, n)
     shapes.append(back)
     o = po.Oracle(codes, datatype=dt)
+    nops = 3 * (n - 2)
     for back in shapes:
         got = []
+        books = []
         for dev in (1, 0):
             e = engine.FitchEngine(codes, datatype=dt)
             e.set_option("dev_sched", dev)
             e.set_option("plan_cache", 0)
+            seen = {"newview_ops": 0, "view_launches": 0}
+            trace = []
+
+            def note(step):
+                # the books a refresh leaves behind: which layouts of the vectors are current, and what it recomputed in how many launches
+                st = e.stats()
+                row = (step, e.get_option("rows_ok"), e.get_option("refresh_wm_active"),
+                       st["newview_ops"] - seen["newview_ops"], st["view_launches"] - seen["view_launches"])
+                seen.update(newview_ops=st["newview_ops"], view_launches=st["view_launches"])
+                print("books n=%d dev_sched=%d" % (n, dev), row)
+                trace.append(row)
+
             s = e.score_tree(back)
+            note("first")
             ptn, tot = e.pattern_scores()
+            note("patterns")
             rad = min(6, n - 3)
             if rad >= 1:
                 k, mp, offs = e.sweep_costs(1, rad)
                 got.append((s, tot, ptn.tolist(), mp.tolist(), offs.tolist(), k))
             else:
                 got.append((s, tot, ptn.tolist()))
+            note("sweep")
             # the same topology again (the cached schedule is replayed) and a different one after it
             assert e.score_tree(back) == s
+            note("again")
             assert e.score_tree(shapes[0]) == o.score_tree(shapes[0])
+            note("other")
+            # ... and with the plan cache on: the second hand-over of a topology replays the stored schedule
+            e.set_option("plan_cache", 7)
+            assert e.score_tree(back) == s
+            note("stored")
+            assert e.score_tree(back) == s
+            note("replayed")
+            books.append(trace)
         assert got[0] == got[1]
         assert got[0][0] == o.score_tree(back)
+        dev_books, host_books = books
+        wm = 1 if alpha == "DNA" else 0                # the word-major copy serves refreshes of DNA alone
+        for d, h in zip(dev_books, host_books):
+            step = d[0]
+            assert d[2] == h[2] == wm, step
+            # the same vectors are recomputed whoever made the schedule, in one launch (views_mode 2: k_newview_wgq or k_newview_chain)
+            refresh = step in ("first", "again", "other", "stored", "replayed")
+            assert d[3] == h[3] == (nops if refresh else 0), (step, d, h)
+            assert d[4] == h[4] == (1 if refresh else 0), (step, d, h)
+            if refresh:
+                # a device-made schedule and its replay run on k_newview_wgq, which on the word-major copy alone writes no rows; the host
+                # cuts a refresh of up to chain_max_ops (512) ops into chains, and k_newview_chain keeps the rows current: the routes
+                # legitimately differ there, each has its own constant.  (The host's schedule is stored, and replayed on k_newview_wgq,
+                # only when it was made for that kernel: above 512 ops, here n = 300.)
+                assert d[1] == 1 - wm, (step, d)
+                assert h[1] == (1 if nops <= 512 else 1 - wm), (step, h)
+            else:
+                assert d[1] == h[1] == 1, (step, d, h)     # (pattern lengths and scans read rows: ensure_rows brought them back)
 
 
 def test_device_schedule_after_moves_and_reweighting(mods):
