@@ -389,6 +389,7 @@ int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *f
    clusters, n_trees (n_taxa - 3), in one call.  No current tree is needed, none is changed, an attached tracker books nothing.
    Test option "split_key_bits" (default 64; 1 .. 63 masks the keys so that they collide), read-only options "split_overflow" (length
    of the last call's overflow list), "split_launches" and, under "timing", "split_keys_ns" / "split_count_ns" / "split_bits_ns".
+   Trees that are not fully resolved (the consensus tree itself, user trees with polytomies) go through the mpf_*_set calls below.
 
    mpf_split_counts (MTreeSet::convertSplits with SW_COUNT): the distinct splits ordered by count descending, then by their words
    ascending as unsigned, word 0 first -- that order is the contract.  *n_distinct is always the full number; the first
@@ -459,8 +460,8 @@ int mpf_ufboot_summary_trees(mpf_engine *e, int32_t rule, int32_t cap, int64_t *
    v_and_b32 / v_bcnt_u32_b32; k_rf_pairs for the adjacent pairs) and k_rf_finish makes the distances.  Exact: a true key collision
    goes through the overflow list, whose clusters the host groups by whole-set comparison and gives columns of their own.  Memory is
    bounded: the matrix is built and multiplied in chunks of columns, padded rows x words per chunk within 256 MiB, so the call never
-   refuses for too many distinct splits.  Multifurcating trees (a consensus as neighbour lists, user trees with polytomies) are not
-   taken: the split pass walks record-format trees only.
+   refuses for too many distinct splits.  Multifurcating trees (a consensus as neighbour lists, user trees with polytomies) go
+   through mpf_rf_distances_set below.
    Options: read-only, each about the last call, "rf_columns" (columns of the matrix: the splits that at least two trees hold),
    "rf_chunks", "rf_launches" (kernel launches, the split pass included) and, under "timing", "rf_rows_ns" / "rf_shared_ns" (HIP-event
    time of k_rf_rows + k_rf_patch and of k_rf_shared or k_rf_pairs, summed over the chunks; the memset of the chunk's matrix is in neither).  Test option "rf_chunk_columns" (default 0: sized by the memory budget; k > 0: chunks
@@ -468,6 +469,48 @@ int mpf_ufboot_summary_trees(mpf_engine *e, int32_t rule, int32_t cap, int64_t *
 enum { MPF_RF_ALL_PAIRS = 0, MPF_RF_ADJACENT = 1, MPF_RF_TWO_SETS = 2 };
 int mpf_rf_distances(mpf_engine *e, int32_t mode, int32_t n_trees, const int32_t *backs /* [n_trees][3 (2 n_taxa - 1)] */,
                      int32_t n_trees2, const int32_t *backs2 /* MPF_RF_TWO_SETS only, else 0 / NULL */, int64_t cap, int32_t *rf);
+/* The four split products on sets that mix record-format trees and trees given as neighbour lists: what back[] cannot hold -- the
+   consensus tree mpf_consensus_tree returns, user trees with polytomies (the reference takes them through MTree::convertSplits,
+   which has no degree limit) -- beside the trees of a run.  A list tree is handed over as the mpf_polytomy_* calls take it: tips
+   are nodes 1 .. n_taxa, inner node i is node n_taxa + 1 + i, with the same conditions (MPF_E_INVALID): 1 <= n_inner <= n_taxa - 2,
+   every inner degree >= 3, symmetric adjacency, every tip exactly once, n_taxa + n_inner - 1 edges, connected.  It has exactly
+   n_inner - 1 non-trivial splits: one for every inner node other than the node next to tip 1, the tips on that node's side away
+   from tip 1.  A star (n_inner = 1) has none; a list tree with n_inner = n_taxa - 2 is fully resolved and gives in every call, bit
+   for bit, what its record form gives.  Everything is integer and exact, true key collisions included ("split_key_bits").
+
+   The index of a tree within a set counts the records first, then the lists; weights[] runs in that order.  The contracts are those
+   of mpf_split_counts, mpf_split_support, mpf_consensus_tree and mpf_rf_distances: the contract order, the sizing protocol, weights
+   >= 0 with NULL = all 1 and weight-0 trees contributing nothing, the modes and result layouts, the MPF_E_INVALID /
+   MPF_E_UNSUPPORTED conditions.  A message names a record-format tree "tree k" and a list tree "list tree k", k counted from 0
+   within the records and within the lists ("second set, list tree k" in the second set of mpf_rf_distances_set).  The limits:
+   2047 taxa, and 2^27 cluster slots, (trees of the call) (n_taxa - 3): a list tree takes as many slots as a record-format one.
+   The differences:
+     mpf_split_support_set  the target is a list tree; the branches come back in the walk order of mpf_polytomy_branch_substitutions
+                            from root_taxon = 1, so that the two calls' arrays line up; *n = n_taxa + n_inner - 1; -1 on a leaf
+                            branch and on the branch at tip 1, whose inner end holds every other tip and is no split.
+     mpf_rf_distances_set   RF(i, j) = c_i + c_j - 2 shared(i, j), c_t the number of non-trivial splits of tree t (the reference's
+                            size(A) + size(B) - 2 common, mtreeset.cpp:484-660).  s2 is NULL unless mode is MPF_RF_TWO_SETS.
+   The device: k_split_keys walks the record-format trees and k_split_keys_lists the list trees (one workgroup per tree, the lists
+   in LDS, children in list order -- a resolved list tree has its record form's splits, not its DFS order --) into the same arrays; then insert, count and compact run once over all of them.  A call without
+   list trees launches what the record calls launch.  No current tree is needed and none is changed, an attached tracker books
+   nothing, the tie stream does not move; either engine (Fitch or weighted) serves the calls.
+   Not served: unequal taxon sets (RF_TWO_TREE_SETS_EXTENDED), split-weight thresholds, incompatible-split counts, .rfinfo / .rftree,
+   more than 2047 taxa. */
+typedef struct mpf_tree_set {
+  int32_t n_records; const int32_t *backs;    /* [n_records][3 (2 n_taxa - 1)] as mpf_split_counts takes them; 0 / NULL = none */
+  int32_t n_lists;   const int32_t *n_inner;  /* [n_lists]; 0 / NULL = none */
+  const int32_t *first;   /* the trees' first[] one behind the other: n_inner[t] + 1 entries each, each starting at 0 */
+  const int32_t *nbr;     /* the trees' nbr[] one behind the other: first[n_inner[t]] entries each */
+} mpf_tree_set;
+int mpf_split_counts_set(mpf_engine *e, const mpf_tree_set *s, const int32_t *weights, int32_t cap,
+                         uint32_t *bits /* [cap][ceil(n_taxa / 32)] */, int64_t *count /* [cap] */, int32_t *n_distinct, int64_t *total_weight);
+int mpf_split_support_set(mpf_engine *e, const mpf_tree_set *s, const int32_t *weights, int32_t target_n_inner, const int32_t *target_first,
+                          const int32_t *target_nbr, int32_t cap, int32_t *node1, int32_t *node2, int64_t *support, int32_t *n,
+                          int64_t *total_weight);
+int mpf_consensus_tree_set(mpf_engine *e, const mpf_tree_set *s, const int32_t *weights, double threshold, int32_t *n_inner, int32_t *first,
+                           int32_t *nbr, int64_t *support_of_inner, int64_t *total_weight);
+int mpf_rf_distances_set(mpf_engine *e, int32_t mode, const mpf_tree_set *s1, const mpf_tree_set *s2 /* MPF_RF_TWO_SETS only, else NULL */,
+                         int64_t cap, int32_t *rf);
 /* The same climb under -bb (save_all_trees == 2), with the UFBoot tracker of mpf_ufboot_attach booking every tree the climb looks
    at through IQTree::saveCurrentTree, in the reference's order: at the start of every step that is not a rollback step the current
    tree with curScore (iqtree.cpp:2181-2183), then for every branch the step evaluates, in evaluation order, the tree after move 0

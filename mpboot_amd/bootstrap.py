@@ -281,13 +281,17 @@ def bb_summary(eng, best_tree, threshold=0.0, rule=-1):
             "consensus_length": eng.polytomy_parsimony(s["first"], s["nbr"]), "n_distinct_splits": len(s["count"])}
 
 
-def bb_rf(eng, best_tree, rule=-1):
+def bb_rf(eng, best_tree, rule=-1, consensus=False):
     """How far the bootstrap trees of a `-bb` run are from best_tree and from each other (the reference's -rf / -rf_all on the tree
     set of IQTree::summarizeBootstrap; MTreeSet::computeRFDist, mtreeset.cpp:484-660).  Call it while the tracker is attached.
 
     -> dict: tree_index / weights (the weighted tree set of ufboot_summary_trees(rule)), rf (the Robinson-Foulds distance of each
     of those trees to best_tree, from ONE two-set call), mean_rf (weighted by `weights`), n_distinct_topologies (trees at distance 0
-    of each other are one topology; from an all-pairs call)."""
+    of each other are one topology; from an all-pairs call).
+
+    consensus=True: the greedy consensus of the weighted set (threshold 0, what goes to .contree) is made as well and the result
+    additionally carries consensus (first, nbr, support_of_inner), rf_consensus (each summary tree's distance to it), mean_rf_consensus
+    (weighted) and best_rf_consensus (best_tree's distance to it) -- the consensus is a tree with polytomies, handed over as lists."""
     idx, w, backs = eng.ufboot_summary_trees(rule)
     rf = eng.rf_distances(backs, [best_tree])[:, 0]
     total = sum(int(x) for x in w)
@@ -295,4 +299,10 @@ def bb_rf(eng, best_tree, rule=-1):
     pairs = eng.rf_distances(backs)
     # the first tree of every topology: no earlier tree at distance 0
     n_distinct = len(idx) - int(np.tril(pairs == 0, -1).any(axis=1).sum())
-    return {"tree_index": idx, "weights": w, "rf": rf, "mean_rf": mean_rf, "n_distinct_topologies": int(n_distinct)}
+    out = {"tree_index": idx, "weights": w, "rf": rf, "mean_rf": mean_rf, "n_distinct_topologies": int(n_distinct)}
+    if consensus:
+        first, nbr, sup, _ = eng.consensus_tree(backs, w, 0.0)
+        d = eng.rf_distances(np.concatenate([backs, np.asarray(best_tree, dtype=np.int32).reshape(1, -1)]), None, lists2=[(first, nbr)])[:, 0]
+        out.update(consensus=(first, nbr, sup), rf_consensus=d[:-1],
+                   mean_rf_consensus=float(sum(int(a) * int(x) for a, x in zip(w, d[:-1]))) / float(total), best_rf_consensus=int(d[-1]))
+    return out

@@ -500,6 +500,73 @@ int mpf_rf_distances(mpf_engine *e, int32_t mode, int32_t n_trees, const int32_t
   return e->eng.rf_distances(mode, n_trees, backs, n_trees2, backs2, cap, rf);
 }
 
+// ---- the same four results on sets that mix record-format trees and trees given as neighbour lists (host/splits.cpp, host/rf.cpp)
+static mpf::splitsets::TreeSet tree_set_of(const mpf_tree_set *s)
+{
+  mpf::splitsets::TreeSet t;
+  if (!s) return t;
+  t.n_records = s->n_records;
+  t.backs = s->backs;
+  t.n_lists = s->n_lists;
+  t.n_inner = s->n_inner;
+  t.first = s->first;
+  t.nbr = s->nbr;
+  return t;
+}
+
+int mpf_split_counts_set(mpf_engine *e, const mpf_tree_set *s, const int32_t *weights, int32_t cap, uint32_t *bits, int64_t *count,
+                         int32_t *n_distinct, int64_t *total_weight)
+{
+  NEED(e);
+  if (!n_distinct) { set_error("null output"); return MPF_E_INVALID; }
+  mpf::splitsets::SplitTable t;
+  const int rc = e->eng.split_counts(tree_set_of(s), weights, t);
+  if (rc) return rc;
+  if (total_weight) *total_weight = t.total;
+  return split_counts_out(t, cap, bits, count, n_distinct);
+}
+
+int mpf_split_support_set(mpf_engine *e, const mpf_tree_set *s, const int32_t *weights, int32_t target_n_inner, const int32_t *target_first,
+                          const int32_t *target_nbr, int32_t cap, int32_t *node1, int32_t *node2, int64_t *support, int32_t *n,
+                          int64_t *total_weight)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<int64_t> sup;
+  mpf::splitsets::TreeRef target;
+  target.n_inner = target_n_inner;
+  target.first = target_first;
+  target.nbr = target_nbr;
+  const int rc = e->eng.split_support(tree_set_of(s), weights, target, br, sup, total_weight);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (cap < *n) return MPF_OK;
+  if (*n && (!node1 || !node2 || !support)) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+    support[i] = sup[i];
+  }
+  return MPF_OK;
+}
+
+int mpf_consensus_tree_set(mpf_engine *e, const mpf_tree_set *s, const int32_t *weights, double threshold, int32_t *n_inner, int32_t *first,
+                           int32_t *nbr, int64_t *support_of_inner, int64_t *total_weight)
+{
+  NEED(e);
+  mpf::splitsets::ListTree t;
+  const int rc = e->eng.consensus_tree(tree_set_of(s), weights, threshold, t, total_weight);
+  if (rc) return rc;
+  return consensus_out(t, n_inner, first, nbr, support_of_inner);
+}
+
+int mpf_rf_distances_set(mpf_engine *e, int32_t mode, const mpf_tree_set *s1, const mpf_tree_set *s2, int64_t cap, int32_t *rf)
+{
+  NEED(e);
+  return e->eng.rf_distances(mode, tree_set_of(s1), tree_set_of(s2), cap, rf);
+}
+
 int mpf_ufboot_summary_trees(mpf_engine *e, int32_t rule, int32_t cap, int64_t *tree_index, int32_t *weights, int32_t *backs, int32_t *n)
 {
   NEED(e);

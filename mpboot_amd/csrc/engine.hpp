@@ -364,11 +364,20 @@ class Engine {
   int split_support(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, std::vector<NniBranch> &br,
                     std::vector<int64_t> &support, int64_t *total);
   int consensus_tree(int n_trees, const int32_t *backs, const int32_t *weights, double threshold, splitsets::ListTree &out, int64_t *total);
+  // the same on a set that mixes record-format trees and trees given as neighbour lists of any inner degree >= 3 (the hand-over of
+  // the polytomy calls); weights run over the set in its order, the records first.  The target of split_support is one tree of
+  // either form; a list target's branches come in the order of polytomy_branch_substitutions from tip 1
+  int split_counts(const splitsets::TreeSet &set, const int32_t *weights, splitsets::SplitTable &out);
+  int split_support(const splitsets::TreeSet &set, const int32_t *weights, const splitsets::TreeRef &target, std::vector<NniBranch> &br,
+                    std::vector<int64_t> &support, int64_t *total);
+  int consensus_tree(const splitsets::TreeSet &set, const int32_t *weights, double threshold, splitsets::ListTree &out, int64_t *total);
   int ufboot_summary_trees(int rule, std::vector<int32_t> &backs, std::vector<int32_t> &weights, std::vector<int64_t> &index);
   // ---- Robinson-Foulds distances between trees (host/rf.cpp, splits.hip; reference MTreeSet::computeRFDist, mtreeset.cpp:484-660):
   // all pairs of one set, adjacent pairs, or every tree of one set against every tree of another, on the split table of ONE pass over
   // all the trees.  mode: splitsets::RF_*.  Stateless towards the engine's own tree, its vectors, the tracker and the tie stream
   int rf_distances(int mode, int n_trees, const int32_t *backs, int n_trees2, const int32_t *backs2, int64_t cap, int32_t *rf);
+  // ... between the trees of mixed sets: RF(i, j) = c_i + c_j - 2 shared(i, j), c_t the number of non-trivial splits of tree t
+  int rf_distances(int mode, const splitsets::TreeSet &s1, const splitsets::TreeSet &s2, int64_t cap, int32_t *rf);
 
   // ---- online UFBoot-MP bookkeeping (host/ufboot.cpp; reference IQTree::saveCurrentTree, iqtree.cpp:3271-3785)
   int ufboot_attach(int n_samples, const uint16_t *samples, double epsilon, int n_local = -1, const int32_t *sample_ids = nullptr,
@@ -571,16 +580,18 @@ class Engine {
   // split_launches and, under "timing", split_keys_ns / split_count_ns / split_bits_ns (HIP-event time of k_split_keys, of
   // insert + count + compact + gather, of k_split_bits)
   struct SplitRun { splitsets::SplitTable table; splitsets::TreeClusters target; std::vector<int64_t> target_support; } split_run_;
-  int split_run(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, bool want_sets, double threshold, SplitRun &r);
-  // what the front half of a call leaves (split_pass): T trees, M clusters, a table of tsize slots of which D are used, n_ovf
-  // clusters on the overflow list, rf_columns slots held by at least two trees (only with rf)
-  struct SplitPass { size_t T; uint32_t M, tsize, n_ovf, D, rf_columns; unsigned long long *trep, *tcount; };
-  int split_pass(const char *what, const std::vector<const int32_t *> &trees, const std::vector<int32_t> &hw,
+  int split_run(const splitsets::TreeSet &set, const int32_t *weights, const splitsets::TreeRef *target, bool want_sets, double threshold,
+                SplitRun &r);
+  // what the front half of a call leaves (split_pass): T trees, M cluster slots, a table of tsize slots of which D are used, n_ovf
+  // clusters on the overflow list, rf_columns slots held by at least two trees (only with rf), the launches of the two walks
+  // (one for a call of record-format trees alone) and, if the call has list trees, every tree's number of splits on the device
+  struct SplitPass { size_t T; uint32_t M, tsize, n_ovf, D, rf_columns; unsigned long long *trep, *tcount; uint32_t key_launches; const int32_t *n_splits; };
+  int split_pass(const char *what, const std::vector<splitsets::TreeRef> &trees, const std::vector<int32_t> &hw,
                  const std::function<std::string(size_t)> &name, bool gather_last, bool rf, SplitPass &p);
   int split_fetch_sets(size_t first, size_t m);
   struct SplitBufs {
-    PinBuf<int32_t> h_backs, h_flags;
-    DevBuf<int32_t> backs, pos, order, flags, w;
+    PinBuf<int32_t> h_backs, h_flags, h_lists, h_n_splits;
+    DevBuf<int32_t> backs, pos, order, flags, w, lists, n_splits;     // lists: SplitListDesc per list tree, then their first[] and nbr[]
     DevBuf<SplitCluster> cl;
     DevBuf<unsigned long long> table;              // keys | representatives | counts
     DevBuf<uint32_t> slot_of, ovf, counters, ids, bits, col_of_slot;
@@ -591,7 +602,7 @@ class Engine {
     PinBuf<long long> h_tsup;
   } split_;
   std::vector<int32_t> split_hw_, split_pick_;
-  std::vector<const int32_t *> split_trees_;
+  std::vector<splitsets::TreeRef> split_trees_, split_all_;
   // Robinson-Foulds distances: test option "rf_chunk_columns" (0 = chunks sized by kRfBudgetBytes; k > 0 = chunks of k columns
   // rounded up to a multiple of 32); read-only, each about the last call: rf_columns (columns of the incidence matrix: splits that
   // at least two trees hold), rf_chunks, rf_launches (kernel launches, the split pass included) and, under "timing", rf_rows_ns /

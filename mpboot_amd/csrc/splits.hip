@@ -8,6 +8,10 @@
 //                    cluster, the side without tip 1 (the normal form of trees.splits).  The cluster's 64-bit key is the wrapping
 //                    sum of a per-taxon constant (splitmix64 of the taxon number) over its tips, taken as the difference of the
 //                    running sum at hi and at lo.  It depends on the SET alone: not on node numbers, slot order or walk order.
+//   k_split_keys_lists  the same for a tree given as CSR neighbour lists, inner nodes of any degree >= 3 (a consensus tree, a user
+//                    tree with polytomies): the lists go into LDS, the walk goes through the children in list order.  A tree with m
+//                    inner nodes has m - 1 clusters; the rest of its n - 3 cluster slots are dead (key kSplitEmpty) and skipped by
+//                    every later kernel, so that tree = cluster / (n - 3) holds for both forms.
 //   k_split_insert   every cluster claims a slot of an open-addressing table in HBM by a 64-bit atomicCAS on the key (linear
 //                    probing, bounded by the table size); the slot's representative is the smallest cluster number (atomicMin).
 //   k_split_count    a launch of its own behind the insert launch: every cluster is compared with its slot's representative AS A
@@ -35,7 +39,8 @@
 //                    arithmetic.  All pairs: only tiles on or above the diagonal, each writes its mirror image.  The first chunk
 //                    stores, later chunks add; no atomics on the result.
 //   k_rf_pairs       adjacent pairs (i, i + 1) only: one wave per pair strides over the two rows.
-//   k_rf_finish      shared -> 2 (n - 3) - 2 shared, the diagonal of an all-pairs matrix 0.
+//   k_rf_finish      shared -> 2 (n - 3) - 2 shared, the diagonal of an all-pairs matrix 0; with list trees in the call
+//                    c_i + c_j - 2 shared from the per-tree split counts (the reference's size(A) + size(B) - 2 common).
 //
 // The key only routes; what decides is the set comparison.  No kernel waits for another workgroup: every atomic either returns
 // at once or is not looked at again before the next launch.
@@ -111,6 +116,92 @@ __global__ void __launch_bounds__(256) k_split_keys(const int32_t *__restrict__ 
   bad[t] = (err || cnt != n - 1 || inner != n - 2) ? 1 : 0;
 }
 
+// grid: n_lists; any block size.  LDS: split_keys_lists_lds_bytes(n).  The counterpart of k_split_keys for a tree given as neighbour
+// lists.  A fully resolved tree gets the same clusters as its record form AS SETS AND KEYS only: the children are taken in list
+// order here and in ring order behind the entering record there, so pos[], order[], the intervals and the cluster numbers differ.  A stack entry is dad << 16 | node (node numbers are below 2 n <= 4094), a negative one closes cluster -(x + 1).  The host
+// has checked the lists; all the same every number read from them is checked before it indexes anything, and the walk is bounded by
+// the node counts of a tree: a malformed list ends it with bad[t] = 1
+__global__ void __launch_bounds__(256) k_split_keys_lists(const SplitListDesc *__restrict__ desc, const int32_t *__restrict__ data, int n, int key_bits,
+                                                          int32_t *__restrict__ pos, int32_t *__restrict__ order, SplitCluster *__restrict__ cl,
+                                                          int32_t *__restrict__ bad)
+{
+  extern __shared__ int32_t lds[];
+  const SplitListDesc d = desc[blockIdx.x];
+  const int C = n - 3, m = d.n_inner, E = d.n_nbr, N = n + m;
+  const size_t t = (size_t)d.tree;
+  SplitCluster *my_cl = cl + t * (size_t)C;
+  // (the launcher's host has sized the staging by these numbers; out of range: nothing is read)
+  const bool sizes_ok = m >= 1 && m <= n - 2 && E >= 0 && E <= 3 * (n - 2);
+  // the slots no cluster of this tree will fill
+  for (int i = (sizes_ok ? m - 1 : 0) + (int)threadIdx.x; i < C; i += blockDim.x) my_cl[i] = SplitCluster{0u, 0u, kSplitEmpty};
+  if (!sizes_ok) { if (threadIdx.x == 0) bad[t] = 1; return; }
+  int32_t *fi = lds, *nb = lds + (m + 1), *stk = nb + E;
+  const int cap = (int)split_lists_stack_words(n, m);
+  for (int i = threadIdx.x; i <= m; i += blockDim.x) fi[i] = data[(size_t)d.first_at + i];
+  for (int i = threadIdx.x; i < E; i += blockDim.x) nb[i] = data[(size_t)d.nbr_at + i];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  int32_t *my_pos = pos + t * (size_t)n, *my_order = order + t * (size_t)(n - 1);
+  const unsigned long long mask = key_bits >= 64 ? ~0ull : ((1ull << key_bits) - 1ull);
+  int sp = 0, cnt = 0, inner = 0, err = 0;
+  unsigned long long acc = 0;
+  {
+    // the walk starts at the inner node next to tip 1, which must list tip 1
+    const int r = d.root;
+    bool has1 = false;
+    if (r > n && r <= N) {
+      const int f0 = fi[r - n - 1], f1 = fi[r - n];
+      if (f0 >= 0 && f1 >= f0 && f1 <= E)
+        for (int k = f0; k < f1; k++) has1 = has1 || nb[k] == 1;
+    }
+    if (has1) stk[sp++] = (1 << 16) | r;
+    else err = 1;
+  }
+  while (sp > 0) {
+    const int x = stk[--sp];
+    if (x < 0) {                                   // the cluster opened at -(x + 1) closes: its key is the sum since then
+      SplitCluster &c = my_cl[-x - 1];
+      unsigned long long k = (acc - c.key) & mask;
+      if (k == kSplitEmpty) k = kSplitEmpty - 1;
+      c.hi = (uint32_t)cnt;
+      c.key = k;
+      continue;
+    }
+    const int v = x & 0xFFFF, dad = x >> 16;
+    if (v < 1 || v > N) { err = 1; break; }
+    if (v <= n) {
+      if (v == 1 || cnt >= n - 1) { err = 1; break; }
+      my_pos[v - 1] = cnt;
+      my_order[cnt++] = v;
+      acc += splitmix64(kTaxonSalt ^ (unsigned long long)v);
+      continue;
+    }
+    if (inner >= m) { err = 1; break; }
+    const int f0 = fi[v - n - 1], f1 = fi[v - n];
+    if (f0 < 0 || f1 < f0 || f1 > E || sp + (f1 - f0) + 1 > cap) { err = 1; break; }
+    const int ci = inner++ - 1;                    // the node next to tip 1 holds every other tip: no split
+    if (ci >= 0) {
+      my_cl[ci].lo = (uint32_t)cnt;
+      my_cl[ci].key = acc;                         // (parked here until the cluster closes)
+      stk[sp++] = -(ci + 1);
+    }
+    for (int k = f1 - 1; k >= f0; k--) {           // children in list order: the first one on top
+      const int u = nb[k];
+      if (u == dad) continue;
+      if (u < 1 || u > N) { err = 1; break; }
+      stk[sp++] = (v << 16) | u;
+    }
+    if (err) break;
+  }
+  my_pos[0] = n - 1;                               // tip 1: outside every interval
+  err = err || cnt != n - 1 || inner != m;
+  // a walk that ended early may have left a cluster open (a parked sum as its key): no slot of a bad tree is looked at, but mark
+  // them all the same so that nothing depends on it
+  if (err)
+    for (int i = 0; i < C; i++) my_cl[i] = SplitCluster{0u, 0u, kSplitEmpty};
+  bad[t] = err ? 1 : 0;
+}
+
 __device__ __forceinline__ uint32_t slot_hash(unsigned long long k) { return (uint32_t)(splitmix64(k) >> 17); }
 
 // one thread per cluster
@@ -120,6 +211,7 @@ __global__ void __launch_bounds__(256) k_split_insert(const SplitCluster *__rest
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n_clusters) return;
   const unsigned long long k = cl[g].key;
+  if (k == kSplitEmpty) { slot_of[g] = kSplitNoSlot; return; }      // a dead slot of a list tree: no cluster
   const uint32_t tmask = tsize - 1;
   uint32_t h = slot_hash(k) & tmask, got = kSplitNoSlot;
   for (uint32_t i = 0; i < tsize; i++) {
@@ -142,13 +234,15 @@ __global__ void __launch_bounds__(256) k_split_count(const SplitCluster *__restr
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const uint32_t C = (uint32_t)(n - 3);
-  const bool live = g < n_clusters;
+  bool live = g < n_clusters;
   uint32_t lo = 0, hi = 0, tg = 0, tr = 0, rlo = 0, rhi = 0, h = kSplitNoSlot;
   bool eq = false, need = false;
   if (live) {
     h = slot_of[g];
-    lo = cl[g].lo;
-    hi = cl[g].hi;
+    const SplitCluster c = cl[g];
+    lo = c.lo;
+    hi = c.hi;
+    live = c.key != kSplitEmpty;                   // a dead slot of a list tree: counted nowhere, never on the overflow list
     tg = g / C;
     if (h != kSplitNoSlot) {
       const uint32_t r = (uint32_t)trep[h];
@@ -363,13 +457,24 @@ __global__ void __launch_bounds__(256) k_rf_pairs(const uint32_t *__restrict__ B
   if (lane == 0) out[p] = (int32_t)s + (accumulate ? out[p] : 0);
 }
 
-// one thread per entry: shared -> 2 C - 2 shared; diag > 0: entries i * diag + i (the diagonal of an all-pairs matrix) are 0
-__global__ void __launch_bounds__(256) k_rf_finish(int32_t *out, unsigned long long entries, int32_t C, uint32_t diag)
+// one thread per entry: shared -> 2 C - 2 shared; diag > 0: entries i * diag + i (the diagonal of an all-pairs matrix) are 0.
+// COUNTS: trees of the call have fewer than C splits (list trees): c_a + c_b - 2 shared, a and b from the result's layout
+template <bool COUNTS>
+__global__ void __launch_bounds__(256) k_rf_finish(int32_t *out, unsigned long long entries, int32_t C, uint32_t diag,
+                                                   const int32_t *__restrict__ n_splits, uint32_t n1, uint32_t n2)
 {
   const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= entries) return;
   const bool on_diag = diag && (i / diag) == (i % diag);
-  out[i] = on_diag ? 0 : 2 * C - 2 * out[i];
+  int32_t both = 2 * C;
+  if (COUNTS) {
+    uint32_t a, b;
+    if (diag) { a = (uint32_t)(i / diag); b = (uint32_t)(i % diag); }
+    else if (n2) { a = (uint32_t)(i / n2); b = n1 + (uint32_t)(i % n2); }
+    else { a = (uint32_t)i; b = a + 1; }
+    both = n_splits[a] + n_splits[b];
+  }
+  out[i] = on_diag ? 0 : both - 2 * out[i];
 }
 
 inline unsigned blocks_for(unsigned long long items) { return (unsigned)((items + 255) / 256); }
@@ -381,6 +486,15 @@ hipError_t launch_split_keys(hipStream_t st, const int32_t *backs, int n_trees, 
 {
   if (n < 4 || n > kSplitMaxTaxa || n_trees < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_split_keys, dim3((unsigned)n_trees), dim3(256), split_keys_lds_bytes(n), st, backs, n, key_bits, pos, order, cl, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_split_keys_lists(hipStream_t st, const SplitListDesc *desc, int n_lists, const int32_t *data, int n, int key_bits, int32_t *pos,
+                                   int32_t *order, SplitCluster *cl, int32_t *bad)
+{
+  if (n < 4 || n > kSplitMaxTaxa || n_lists < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_split_keys_lists, dim3((unsigned)n_lists), dim3(256), split_keys_lists_lds_bytes(n), st, desc, data, n, key_bits, pos, order,
+                     cl, bad);
   return hipGetLastError();
 }
 
@@ -467,11 +581,13 @@ hipError_t launch_rf_pairs(hipStream_t st, const uint32_t *B, uint32_t row_words
   return hipGetLastError();
 }
 
-hipError_t launch_rf_finish(hipStream_t st, int32_t *out, unsigned long long entries, int n, uint32_t diag)
+hipError_t launch_rf_finish(hipStream_t st, int32_t *out, unsigned long long entries, int n, uint32_t diag, const int32_t *n_splits, uint32_t n1,
+                            uint32_t n2)
 {
   if (!entries) return hipSuccess;
   if (entries > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_rf_finish, dim3(blocks_for(entries)), dim3(256), 0, st, out, entries, (int32_t)(n - 3), diag);
+  if (n_splits) hipLaunchKernelGGL(k_rf_finish<true>, dim3(blocks_for(entries)), dim3(256), 0, st, out, entries, (int32_t)(n - 3), diag, n_splits, n1, n2);
+  else hipLaunchKernelGGL(k_rf_finish<false>, dim3(blocks_for(entries)), dim3(256), 0, st, out, entries, (int32_t)(n - 3), diag, n_splits, n1, n2);
   return hipGetLastError();
 }
 

@@ -39,6 +39,7 @@ EXPORTS = [
     "mpf_polytomy_parsimony", "mpf_polytomy_branch_substitutions", "mpf_polytomy_branch_lengths",
     "mpf_split_counts", "mpf_split_support", "mpf_consensus_tree", "mpf_ufboot_summarize", "mpf_ufboot_summary_trees",
     "mpf_rf_distances",
+    "mpf_split_counts_set", "mpf_split_support_set", "mpf_consensus_tree_set", "mpf_rf_distances_set",
 ]
 
 
@@ -86,6 +87,12 @@ class BbSummary(C.Structure):
                 ("threshold", C.c_double), ("first", C.c_void_p), ("nbr", C.c_void_p), ("support_of_inner", C.c_void_p),
                 ("n_trees", C.c_int32), ("n_distinct", C.c_int32), ("n_branches", C.c_int32), ("n_inner", C.c_int32),
                 ("total_weight", C.c_int64)]
+
+
+class TreeSet(C.Structure):
+    """mpf_tree_set (include/mpfitch.h): record-format trees, then trees given as neighbour lists"""
+    _fields_ = [("n_records", C.c_int32), ("backs", C.c_void_p), ("n_lists", C.c_int32), ("n_inner", C.c_void_p),
+                ("first", C.c_void_p), ("nbr", C.c_void_p)]
 
 
 SUMMARY_AUTO, SUMMARY_DEFAULT, SUMMARY_MULHITS, SUMMARY_TOPBOOT = -1, 0, 1, 2
@@ -199,6 +206,11 @@ def load_library():
         L.mpf_ufboot_summarize.argtypes = [vp, C.c_int32, C.POINTER(BbSummary)]
         L.mpf_ufboot_summary_trees.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.mpf_rf_distances.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]
+        ts = C.POINTER(TreeSet)
+        L.mpf_split_counts_set.argtypes = [vp, ts, vp, C.c_int32, vp, vp, vp, vp]
+        L.mpf_split_support_set.argtypes = [vp, ts, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.mpf_consensus_tree_set.argtypes = [vp, ts, vp, C.c_double, vp, vp, vp, vp, vp]
+        L.mpf_rf_distances_set.argtypes = [vp, C.c_int32, ts, ts, C.c_int64, vp]
         _lib = L
     return _lib
 
@@ -693,14 +705,51 @@ class FitchEngine:
         assert w is None or len(w) == len(b)
         return b, w
 
-    def split_counts(self, backs, weights=None, counts_only: bool = False):
+    def _mixed_set(self, backs, lists, weights=None):
+        """(TreeSet, its number of trees, weights or None, the arrays it points into) of record-format trees `backs` (may be None or
+        empty) followed by the list-form trees lists = [(first, nbr), ...]"""
+        keep = []
+        s = TreeSet()
+        T = 0
+        if backs is not None and len(backs):
+            b = np.ascontiguousarray(backs, dtype=np.int32).reshape(-1, 3 * (2 * self.n - 1))
+            keep.append(b)
+            s.n_records, s.backs, T = len(b), b.ctypes.data, len(b)
+        if lists is not None and len(lists):
+            fs = [np.ascontiguousarray(f, dtype=np.int32).reshape(-1) for f, _ in lists]
+            ns = [np.ascontiguousarray(x, dtype=np.int32).reshape(-1) for _, x in lists]
+            ni = np.array([len(f) - 1 for f in fs], dtype=np.int32)
+            first = np.ascontiguousarray(np.concatenate(fs), dtype=np.int32)
+            nbr = np.ascontiguousarray(np.concatenate(ns + [np.zeros(1, dtype=np.int32)]), dtype=np.int32)
+            keep += [ni, first, nbr]
+            s.n_lists, s.n_inner, s.first, s.nbr = len(lists), ni.ctypes.data, first.ctypes.data, nbr.ctypes.data
+            T += len(lists)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32)
+        assert w is None or len(w) == T
+        return s, T, w, keep
+
+    def split_counts(self, backs, weights=None, counts_only: bool = False, *, lists=None):
         """The distinct non-trivial splits of the trees backs[T][3 (2n - 1)] with the summed weights of the trees that hold them
         (weights int32 >= 0, None = all 1): (bits[D][ceil(n / 32)] uint32, count[D] int64, total_weight), ordered by count
         descending, then by the words ascending.  Bit (t - 1) % 32 of word (t - 1) / 32 = tip t is on the side without tip 1.
-        counts_only: (D, total_weight).  Exact: counted on the device, sets compared as whole sets."""
-        b, w = self._tree_set(backs, weights)
+        counts_only: (D, total_weight).  Exact: counted on the device, sets compared as whole sets.
+        lists=[(first, nbr), ...]: trees given as neighbour lists (any inner degree >= 3; trees.collapse_branches, consensus_tree)
+        behind the record-format ones, which may then be None; weights run over the records, then the lists."""
         nd, tot = C.c_int32(), C.c_int64()
         L = load_library()
+        if lists is not None:
+            ts, _, w, _keep = self._mixed_set(backs, lists, weights)
+            wp = None if w is None else _p(w)
+            _chk(L.mpf_split_counts_set(self.h, C.byref(ts), wp, 0, None, None, C.byref(nd), C.byref(tot)))
+            if counts_only:
+                return int(nd.value), int(tot.value)
+            D, words = int(nd.value), (self.n + 31) // 32
+            bits = np.zeros((max(D, 1), words), dtype=np.uint32)
+            cnt = np.zeros(max(D, 1), dtype=np.int64)
+            _chk(L.mpf_split_counts_set(self.h, C.byref(ts), wp, D, _p(bits), _p(cnt), C.byref(nd), C.byref(tot)))
+            assert nd.value == D
+            return bits[:D], cnt[:D], int(tot.value)
+        b, w = self._tree_set(backs, weights)
         _chk(L.mpf_split_counts(self.h, len(b), _p(b), None if w is None else _p(w), 0, None, None, C.byref(nd), C.byref(tot)))
         if counts_only:
             return int(nd.value), int(tot.value)
@@ -711,9 +760,28 @@ class FitchEngine:
         assert nd.value == D
         return bits[:D], cnt[:D], int(tot.value)
 
-    def split_support(self, backs, target, weights=None):
+    def split_support(self, backs, target=None, weights=None, *, lists=None, target_lists=None):
         """(node1[m], node2[m], support[m] int64, total_weight) for the m = 2 n - 3 branches of `target` in the order of
-        branch_substitutions(root_taxon=1): the summed weight of the trees that hold the branch's split, -1 on a leaf branch"""
+        branch_substitutions(root_taxon=1): the summed weight of the trees that hold the branch's split, -1 on a leaf branch.
+        target_lists=(first, nbr) instead of target: the target is given as neighbour lists, m = n + n_inner - 1 branches in the
+        order of polytomy_branch_substitutions(root_taxon=1), -1 also on the branch at tip 1; lists= as in split_counts."""
+        if target is None and target_lists is None:
+            raise ValueError("target or target_lists is needed")
+        if target_lists is not None or lists is not None:
+            if target_lists is None:
+                from . import trees
+                target_lists = trees.back_to_lists(target, self.n)
+            elif target is not None:
+                raise ValueError("target or target_lists, not both")
+            ts, _, w, _keep = self._mixed_set(backs, lists, weights)
+            f, nb, k = self._lists(*target_lists)
+            m = self.n + k - 1
+            n, tot = C.c_int32(), C.c_int64()
+            a, c, s = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+            _chk(load_library().mpf_split_support_set(self.h, C.byref(ts), None if w is None else _p(w), k, _p(f), _p(nb), m, _p(a), _p(c), _p(s),
+                                                      C.byref(n), C.byref(tot)))
+            assert n.value == m
+            return a, c, s, int(tot.value)
         b, w = self._tree_set(backs, weights)
         t = np.ascontiguousarray(target, dtype=np.int32)
         m = 2 * self.n - 3
@@ -724,15 +792,21 @@ class FitchEngine:
         assert n.value == m
         return a, c, s, int(tot.value)
 
-    def consensus_tree(self, backs, weights=None, threshold: float = 0.0):
+    def consensus_tree(self, backs, weights=None, threshold: float = 0.0, *, lists=None):
         """The reference's consensus of the weighted trees: splits with count <= threshold * total dropped, then the greedy maximal
         compatible set (threshold 0: the greedy consensus of .contree; >= 0.5: majority rule).  -> (first, nbr, support_of_inner,
         total_weight): the neighbour lists polytomy_parsimony / polytomy_branch_lengths take, inner nodes in pre-order from tip 1,
-        support_of_inner[i] = the count of the split above inner node n + 1 + i (-1 for the first)."""
-        b, w = self._tree_set(backs, weights)
+        support_of_inner[i] = the count of the split above inner node n + 1 + i (-1 for the first).  lists= as in split_counts."""
         n = self.n
         ni, tot = C.c_int32(), C.c_int64()
         first, nbr, sup = np.zeros(n - 1, dtype=np.int32), np.zeros(3 * n - 6, dtype=np.int32), np.zeros(n - 2, dtype=np.int64)
+        if lists is not None:
+            ts, _, w, _keep = self._mixed_set(backs, lists, weights)
+            _chk(load_library().mpf_consensus_tree_set(self.h, C.byref(ts), None if w is None else _p(w), float(threshold), C.byref(ni),
+                                                       _p(first), _p(nbr), _p(sup), C.byref(tot)))
+            k = int(ni.value)
+            return first[:k + 1].copy(), nbr[:int(first[k])].copy(), sup[:k].copy(), int(tot.value)
+        b, w = self._tree_set(backs, weights)
         _chk(load_library().mpf_consensus_tree(self.h, len(b), _p(b), None if w is None else _p(w), float(threshold), C.byref(ni), _p(first),
                                                _p(nbr), _p(sup), C.byref(tot)))
         k = int(ni.value)
@@ -778,13 +852,28 @@ class FitchEngine:
             out.update(node1=a, node2=c, support=sup)
         return out
 
-    def rf_distances(self, backs, backs2=None, mode: str = "all"):
+    def rf_distances(self, backs, backs2=None, mode: str = "all", *, lists=None, lists2=None):
         """Robinson-Foulds distances between trees (MTreeSet::computeRFDist; -rf_all, -rf_adj, -rf of the reference): the number of
         non-trivial splits in one tree and not in the other, int32.  backs[T][3 (2n - 1)] alone: mode "all" -> [T][T] (symmetric,
         diagonal 0), mode "adjacent" -> [T - 1], d(tree i, tree i + 1).  With backs2[T2][...]: [T][T2], tree i of backs against
-        tree j of backs2.  Exact: one split pass over all the trees on the device, then a binary matrix product."""
+        tree j of backs2.  Exact: one split pass over all the trees on the device, then a binary matrix product.
+        lists=[(first, nbr), ...] / lists2=: trees given as neighbour lists behind the record-format trees of the first / second set
+        (either part of a set may be None); the distance is then c_i + c_j - 2 shared for trees with c_i and c_j splits."""
         if mode not in ("all", "adjacent"):
             raise ValueError("mode: 'all' or 'adjacent'")
+        if lists is not None or lists2 is not None:
+            s1, T, _, _k1 = self._mixed_set(backs, lists)
+            if backs2 is not None or lists2 is not None:
+                if mode != "all":
+                    raise ValueError("two sets: every tree of the first against every tree of the second (mode 'all')")
+                s2, T2, _, _k2 = self._mixed_set(backs2, lists2)
+                out = np.zeros((T, T2), dtype=np.int32)
+                _chk(load_library().mpf_rf_distances_set(self.h, RF_TWO_SETS, C.byref(s1), C.byref(s2), out.size, _p(out)))
+                return out
+            out = np.zeros((T, T) if mode == "all" else (max(T - 1, 0),), dtype=np.int32)
+            _chk(load_library().mpf_rf_distances_set(self.h, RF_ALL_PAIRS if mode == "all" else RF_ADJACENT, C.byref(s1), None, out.size,
+                                                     _p(out) if out.size else None))
+            return out
         b, _ = self._tree_set(backs, None)
         T = len(b)
         if backs2 is not None:

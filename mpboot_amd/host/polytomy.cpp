@@ -32,6 +32,7 @@ constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 int bad(const std::string &what) { set_error("polytomy tree: " + what); return MPF_E_INVALID; }
 }  // namespace
 
+// (splitsets::lists_ok of host/split_sets.hpp restates these conditions device-free for the mpf_*_set calls: change both together.)
 // The checks of the hand-over (include/mpfitch.h) and the rooted shape: parent and pre-order of every node from the root leaf,
 // neighbours in list order (fixNegativeBranch's walk: FOR_NEIGHBOR_IT(node, dad, it))
 int Engine::polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, PolyTree &t) const

@@ -7,7 +7,8 @@
 // Here ONE split pass runs over all trees of the call (split_pass of host/splits.cpp: keys -> insert -> count, every tree weight 1,
 // the second set behind the first), which gives every inner branch an exact identity: the table slot of its split.  The slots that at
 // least two trees hold become the columns of a trees x columns bit matrix, shared(i, j) is the popcount of row i AND row j, and
-// RF(i, j) = 2 (n - 3) - 2 shared(i, j) (k_rf_columns, k_rf_rows, k_rf_shared / k_rf_pairs, k_rf_finish of splits.hip).  The matrix is
+// RF(i, j) = 2 (n - 3) - 2 shared(i, j) (k_rf_columns, k_rf_rows, k_rf_shared / k_rf_pairs, k_rf_finish of splits.hip); with trees
+// given as neighbour lists in the call, which may have fewer splits, c_i + c_j - 2 shared(i, j) from the trees' split counts.  The matrix is
 // built and multiplied in chunks of columns within kRfBudgetBytes.  The clusters of the overflow list (true key collisions) are
 // grouped by whole-set comparison on the host (splitsets::overflow_columns) and get columns of their own, so the result is exact.
 #include <string>
@@ -33,17 +34,27 @@ int bad(const std::string &what) { set_error("rf distances: " + what); return MP
 
 int Engine::rf_distances(int mode, int n_trees, const int32_t *backs, int n_trees2, const int32_t *backs2, int64_t cap, int32_t *rf)
 {
+  splitsets::TreeSet a, b;
+  a.n_records = n_trees;
+  a.backs = backs;
+  b.n_records = n_trees2;
+  b.backs = backs2;
+  return rf_distances(mode, a, b, cap, rf);
+}
+
+int Engine::rf_distances(int mode, const splitsets::TreeSet &s1, const splitsets::TreeSet &s2, int64_t cap, int32_t *rf)
+{
   using namespace splitsets;
   const int n = n_, C = n - 3, words = words_of(n);
-  const size_t len = 3 * (size_t)(2 * n - 1);
   rf_columns_ = rf_chunks_ = rf_launches_ = rf_rows_ns_ = rf_shared_ns_ = 0;
   split_overflow_ = 0;
   if (mode != RF_ALL_PAIRS && mode != RF_ADJACENT && mode != RF_TWO_SETS) return bad("unknown mode " + std::to_string(mode));
-  if (n_trees < 1 || !backs) return bad("no trees");
+  if (s1.size() < 1 || s1.n_records < 0 || s1.n_lists < 0 || !s1.pointers_ok()) return bad("no trees");
   const bool two = mode == RF_TWO_SETS;
-  if (two && (n_trees2 < 1 || !backs2)) return bad("two sets: no second set");
-  if (!two && (n_trees2 != 0 || backs2)) return bad("a second set is given, but the mode is not MPF_RF_TWO_SETS");
-  const int N1 = n_trees, N2 = two ? n_trees2 : 0;
+  if (two && (s2.size() < 1 || s2.n_records < 0 || s2.n_lists < 0 || !s2.pointers_ok())) return bad("two sets: no second set");
+  if (!two && (s2.n_records != 0 || s2.backs || s2.n_lists != 0 || s2.n_inner || s2.first || s2.nbr))
+    return bad("a second set is given, but the mode is not MPF_RF_TWO_SETS");
+  const int N1 = s1.size(), N2 = two ? s2.size() : 0;
   const int64_t entries = mode == RF_ALL_PAIRS ? (int64_t)N1 * N1 : mode == RF_ADJACENT ? (int64_t)N1 - 1 : (int64_t)N1 * N2;
   if (entries > INT32_MAX) { set_error("rf distances: the result would have more than 2^31 - 1 entries"); return MPF_E_UNSUPPORTED; }
   if (cap < entries) return bad("cap " + std::to_string(cap) + " is smaller than the " + std::to_string(entries) + " entries of the result");
@@ -52,15 +63,27 @@ int Engine::rf_distances(int mode, int n_trees, const int32_t *backs, int n_tree
     set_error("rf distances: more than " + std::to_string(kSplitMaxTaxa) + " taxa (a tree's records and its walk's stack must fit 64 KiB of LDS)");
     return MPF_E_UNSUPPORTED;
   }
-  // the checks of mpf_set_tree on every tree
-  std::vector<const int32_t *> &trees = split_trees_;
+  // the checks of mpf_set_tree (records) or of the polytomy hand-over (lists) on every tree
+  std::vector<TreeRef> &trees = split_trees_;
   std::vector<int32_t> &hw = split_hw_;
   trees.clear();
-  auto tree_name = [&](size_t i) { return i < (size_t)N1 ? "tree " + std::to_string(i) : "second set, tree " + std::to_string(i - (size_t)N1); };
-  for (int t = 0; t < N1 + N2; t++) {
-    const int32_t *b = t < N1 ? backs + (size_t)t * len : backs2 + (size_t)(t - N1) * len;
-    if (!links_ok(b, n)) return bad(tree_name((size_t)t) + ": inconsistent back links (a complete tree on n_taxa taxa is needed)");
-    trees.push_back(b);
+  auto tree_name = [&](size_t i) {
+    const TreeSet &s = i < (size_t)N1 ? s1 : s2;
+    const size_t k = i < (size_t)N1 ? i : i - (size_t)N1;
+    return std::string(i < (size_t)N1 ? "" : "second set, ") + (k < (size_t)s.n_records ? "tree " + std::to_string(k) : "list tree " + std::to_string(k - (size_t)s.n_records));
+  };
+  std::string why;
+  for (int set = 0; set < (two ? 2 : 1); set++) {
+    const size_t at = trees.size();
+    const int stop = set_refs(n, set ? s2 : s1, trees);
+    for (size_t t = at; t < trees.size(); t++) {
+      if (trees[t].is_list()) {
+        if (!lists_ok(n, trees[t].n_inner, trees[t].first, trees[t].nbr, &why)) return bad(tree_name(t) + ": " + why);
+      } else if (!links_ok(trees[t].back, n))
+        return bad(tree_name(t) + ": inconsistent back links (a complete tree on n_taxa taxa is needed)");
+    }
+    if (stop >= 0)
+      return bad(std::string(set ? "second set, " : "") + "list tree " + std::to_string(stop) + ": n_inner or first[] are not those of a tree on n_taxa taxa");
   }
   hw.assign(trees.size(), 1);
   if (C < 1) {                                     // three taxa: one tree shape, no inner branch
@@ -70,7 +93,7 @@ int Engine::rf_distances(int mode, int n_trees, const int32_t *backs, int n_tree
   SplitPass ps;
   int rc = split_pass("rf distances", trees, hw, tree_name, false, true, ps);
   if (rc) return rc;
-  rf_launches_ = 5;                                // keys, insert, count, compact, columns
+  rf_launches_ = 4 + ps.key_launches;              // keys (one launch for record-format trees alone), insert, count, compact, columns
   SplitBufs &b = split_;
   // true key collisions: the overflow clusters grouped as sets; a group of two or more is a column behind the device's
   std::vector<uint32_t> patch;
@@ -122,7 +145,8 @@ int Engine::rf_distances(int mode, int n_trees, const int32_t *backs, int n_tree
       if (hipEventElapsedTime(&ms, ev1_, ev2_) == hipSuccess) rf_shared_ns_ += (uint64_t)((double)ms * 1e6);
     }
   }
-  HIPCHK(launch_rf_finish(st_, rf_out_.p, (unsigned long long)entries, n, mode == RF_ALL_PAIRS ? (uint32_t)N1 : 0u));
+  HIPCHK(launch_rf_finish(st_, rf_out_.p, (unsigned long long)entries, n, mode == RF_ALL_PAIRS ? (uint32_t)N1 : 0u, ps.n_splits, (uint32_t)N1,
+                          (uint32_t)N2));
   rf_launches_++;
   HIPCHK(hipMemcpyAsync(rf, rf_out_.p, (size_t)entries * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
   HIPCHK(hipStreamSynchronize(st_));

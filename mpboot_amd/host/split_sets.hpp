@@ -6,6 +6,9 @@
 // as whole sets; the hash of SetIndex only picks a bucket.
 //
 //   walk_clusters     the walk of k_split_keys restated: DFS from tip 1, every inner branch an interval [lo, hi) of DFS positions
+//   lists_ok          the hand-over conditions of the mpf_polytomy_* calls on a tree given as CSR neighbour lists
+//   walk_clusters_lists  the walk of k_split_keys_lists restated: the same intervals for a tree of any inner degree >= 3
+//   TreeSet, TreeRef  a set that mixes record-format and list-form trees (the records first, then the lists), and one tree of it
 //   SetIndex          exact set -> index map (the overflow list of k_split_count is resolved through it; so is count_splits)
 //   count_splits      the whole summary on the host (the CPU yardstick of tools/splits_timing.py)
 //   order_splits      the contract order: count descending, then the words ascending as unsigned, word 0 first
@@ -23,6 +26,7 @@
 #include <cstdint>
 #include <cstring>
 #include <numeric>
+#include <string>
 #include <unordered_map>
 #include <vector>
 
@@ -51,6 +55,8 @@ struct TreeClusters {
   std::vector<int32_t> order;   // [n - 1]  the tip at each DFS position
   std::vector<int32_t> lo, hi;  // [n - 3]  cluster ci = the tips with lo <= pos < hi, ci in pre-order of the inner nodes
   std::vector<int32_t> node;    // [n - 3]  the inner node below the branch (the end away from tip 1)
+  // (a list tree with m inner nodes: m - 1 clusters)
+  int size() const { return (int)lo.size(); }
 };
 
 // The walk of k_split_keys, step for step: an explicit stack of records, a negative entry closes cluster -(x + 1).  The inner
@@ -91,6 +97,178 @@ inline bool walk_clusters(const int32_t *back, int n, TreeClusters &c)
   }
   c.pos[0] = n - 1;
   return cnt == n - 1 && inner == n - 2;
+}
+
+// ---- trees as CSR neighbour lists (the hand-over of mpf_polytomy_*): tips 1 .. n, inner node i = node n + 1 + i with the
+// neighbours nbr[first[i] .. first[i + 1])
+
+// the largest stack walk_clusters_lists / k_split_keys_lists can need: every node waits there at most once, and every inner node
+// but the first leaves one closing entry
+inline size_t list_walk_stack(int n, int n_inner) { return (size_t)n + 2 * (size_t)n_inner + 2; }
+
+// (Engine::polytomy_check of host/polytomy.cpp checks the same conditions for the mpf_polytomy_* calls, with messages of its own and
+// the rooted shape as a by-product; it needs the engine, this header must not.  Whoever changes the hand-over rule changes both.)
+// The conditions of the hand-over: 1 <= n_inner <= n - 2, first[0] = 0, every inner degree >= 3, entries in range, no loop on a
+// node, every tip exactly once, symmetric adjacency without doubles, n + n_inner - 1 edges, one connected tree.  why (may be
+// null): what is wrong
+inline bool lists_ok(int n, int n_inner, const int32_t *first, const int32_t *nbr, std::string *why = nullptr)
+{
+  auto no = [&](const char *w) { if (why) *why = w; return false; };
+  if (!first || !nbr) return no("null neighbour lists");
+  if (n < 3 || n_inner < 1 || n_inner > n - 2) return no("n_inner must be in 1 .. n_taxa - 2");
+  if (first[0] != 0) return no("first[0] must be 0");
+  const int N = n + n_inner;
+  for (int i = 0; i < n_inner; i++)
+    if ((int64_t)first[i + 1] - (int64_t)first[i] < 3) return no("an inner node has fewer than three neighbours");
+  const int64_t E = first[n_inner];
+  if (E > 3 * (int64_t)(n - 2)) return no("more neighbour entries than a tree of n_taxa leaves can have");
+  std::vector<int32_t> tip_nb((size_t)n + 1, 0);
+  std::vector<std::pair<int32_t, int32_t>> arcs;         // inner -> inner
+  for (int i = 0; i < n_inner; i++)
+    for (int k = first[i]; k < first[i + 1]; k++) {
+      const int u = nbr[k], v = n + 1 + i;
+      if (u < 1 || u > N) return no("neighbour number out of range");
+      if (u == v) return no("a node is its own neighbour");
+      if (u <= n) {
+        if (tip_nb[(size_t)u]) return no("a tip occurs more than once");
+        tip_nb[(size_t)u] = v;
+      } else arcs.emplace_back(v, u);
+    }
+  for (int u = 1; u <= n; u++)
+    if (!tip_nb[(size_t)u]) return no("a tip does not occur");
+  std::sort(arcs.begin(), arcs.end());
+  for (size_t i = 0; i < arcs.size(); i++) {
+    if (i && arcs[i] == arcs[i - 1]) return no("a neighbour is listed twice");
+    if (!std::binary_search(arcs.begin(), arcs.end(), std::make_pair(arcs[i].second, arcs[i].first))) return no("adjacency is not symmetric");
+  }
+  if ((int64_t)n + (int64_t)arcs.size() / 2 != (int64_t)N - 1) return no("not n_taxa + n_inner - 1 edges");
+  // with that many edges: one tree iff every node is reached from tip 1 (a cycle leaves a part unreached)
+  std::vector<char> seen((size_t)N + 1, 0);
+  std::vector<int32_t> st{tip_nb[1]};
+  seen[1] = seen[(size_t)tip_nb[1]] = 1;
+  int reached = 2;
+  while (!st.empty()) {
+    const int v = st.back();
+    st.pop_back();
+    for (int k = first[v - n - 1]; k < first[v - n]; k++) {
+      const int u = nbr[k];
+      if (seen[(size_t)u]) continue;
+      seen[(size_t)u] = 1;
+      reached++;
+      if (u > n) st.push_back(u);
+    }
+  }
+  if (reached != N) return no("the neighbour lists hold a cycle or the tree is not connected");
+  return true;
+}
+
+// the inner node next to tip 1 (0: tip 1 is in no list)
+inline int list_root(int n, int n_inner, const int32_t *first, const int32_t *nbr)
+{
+  const int E = first[n_inner];
+  for (int i = 0; i < n_inner; i++) {
+    if (first[i] < 0 || first[i + 1] > E) return 0;
+    for (int k = first[i]; k < first[i + 1]; k++)
+      if (nbr[k] == 1) return n + 1 + i;
+  }
+  return 0;
+}
+
+// The walk of k_split_keys_lists, step for step: an explicit stack of (node, dad) entries, children in list order, a negative
+// entry closes cluster -(x + 1).  The inner node next to tip 1 is entered first and gets no cluster, so a tree with m inner nodes
+// has m - 1 clusters; c.node[ci] is the inner node below cluster ci's branch.  Tips and inner nodes are met in the order of the
+// branch walk of mpf_polytomy_branch_substitutions from root_taxon = 1.  Every index is checked and the walk is bounded by the
+// node counts, as on the device.  false: the lists do not form ONE tree over all n tips
+inline bool walk_clusters_lists(int n, int n_inner, const int32_t *first, const int32_t *nbr, TreeClusters &c)
+{
+  const int K = std::max(n_inner - 1, 0);
+  c.pos.assign((size_t)n, 0);
+  c.order.assign((size_t)std::max(n - 1, 0), 0);
+  c.lo.assign((size_t)K, 0);
+  c.hi.assign((size_t)K, 0);
+  c.node.assign((size_t)K, 0);
+  if (n < 3 || n_inner < 1 || n_inner > n - 2) return false;
+  const int N = n + n_inner, E = first[n_inner];
+  const size_t cap = list_walk_stack(n, n_inner);
+  const int root = list_root(n, n_inner, first, nbr);
+  if (!root) return false;
+  struct F { int32_t node, dad; };
+  std::vector<F> st;
+  st.reserve(cap);
+  st.push_back(F{root, 1});
+  int cnt = 0, inner = 0;
+  while (!st.empty()) {
+    const F x = st.back();
+    st.pop_back();
+    if (x.node < 0) { c.hi[(size_t)(-x.node - 1)] = cnt; continue; }
+    const int v = x.node;
+    if (v < 1 || v > N) return false;
+    if (v <= n) {
+      if (v == 1 || cnt >= n - 1) return false;
+      c.pos[(size_t)v - 1] = cnt;
+      c.order[(size_t)cnt++] = v;
+      continue;
+    }
+    if (inner >= n_inner) return false;
+    const int f0 = first[v - n - 1], f1 = first[v - n];
+    if (f0 < 0 || f1 < f0 || f1 > E || st.size() + (size_t)(f1 - f0) + 1 > cap) return false;
+    const int ci = inner++ - 1;
+    if (ci >= 0) {
+      c.lo[(size_t)ci] = cnt;
+      c.node[(size_t)ci] = v;
+      st.push_back(F{-(ci + 1), 0});
+    }
+    for (int k = f1 - 1; k >= f0; k--)
+      if (nbr[k] != x.dad) st.push_back(F{nbr[k], v});
+  }
+  c.pos[0] = n - 1;
+  return cnt == n - 1 && inner == n_inner;
+}
+
+// A set that mixes the two forms, as the C-ABI hands it over (mpf_tree_set): the records first, then the lists.  The lists'
+// first[] lie one behind the other (n_inner[t] + 1 entries each, each starting at 0), and so do their nbr[] (first[n_inner[t]] each)
+struct TreeSet {
+  int n_records = 0; const int32_t *backs = nullptr;
+  int n_lists = 0;   const int32_t *n_inner = nullptr, *first = nullptr, *nbr = nullptr;
+  int size() const { return std::max(n_records, 0) + std::max(n_lists, 0); }
+  bool pointers_ok() const { return (n_records <= 0 || backs) && (n_lists <= 0 || (n_inner && first && nbr)); }
+};
+// one tree of a set: records (back != null) or lists
+struct TreeRef {
+  const int32_t *back = nullptr;
+  int n_inner = 0; const int32_t *first = nullptr, *nbr = nullptr;
+  bool is_list() const { return back == nullptr; }
+  int clusters(int n) const { return is_list() ? std::max(n_inner - 1, 0) : std::max(n - 3, 0); }
+};
+
+// The trees of a set, appended to refs.  A list tree's place follows from the sizes of those before it, so the walk ends at the
+// first list whose n_inner or first[n_inner] cannot be one of a tree on n taxa: its index within the lists comes back (-1: all found)
+inline int set_refs(int n, const TreeSet &s, std::vector<TreeRef> &refs)
+{
+  const size_t len = 3 * (size_t)(2 * n - 1);
+  for (int t = 0; t < s.n_records; t++) { TreeRef r; r.back = s.backs + (size_t)t * len; refs.push_back(r); }
+  size_t fo = 0, no = 0;
+  for (int t = 0; t < s.n_lists; t++) {
+    const int m = s.n_inner[t];
+    if (m < 1 || m > n - 2) return t;
+    TreeRef r;
+    r.n_inner = m;
+    r.first = s.first + fo;
+    r.nbr = s.nbr + no;
+    const int64_t E = r.first[m];
+    if (r.first[0] != 0 || E < 0 || E > 3 * (int64_t)(n - 2)) return t;
+    refs.push_back(r);
+    fo += (size_t)m + 1;
+    no += (size_t)E;
+  }
+  return -1;
+}
+
+// checks and walk of one tree of either form.  false: not a complete tree on n taxa
+inline bool tree_clusters(const TreeRef &r, int n, TreeClusters &c)
+{
+  if (r.is_list()) return lists_ok(n, r.n_inner, r.first, r.nbr) && walk_clusters_lists(n, r.n_inner, r.first, r.nbr, c);
+  return links_ok(r.back, n) && walk_clusters(r.back, n, c);
 }
 
 inline void cluster_bits(const TreeClusters &c, int ci, int words, uint32_t *out)
@@ -138,25 +316,27 @@ struct SplitTable {
 };
 
 // MTreeSet::convertSplits (reference mtreeset.cpp:288-470) without the strings: every tree's splits into one table, weighted.
-// weights may be null (all 1); a tree of weight 0 contributes nothing.  false: a tree is not a complete tree on n taxa
-inline bool count_splits(int n, int n_trees, const int32_t *backs, const int32_t *weights, SplitTable &out)
+// weights (indexed as the set: records, then lists) may be null (all 1); a tree of weight 0 contributes nothing.  false: a tree is
+// not a complete tree on n taxa (*bad_tree: which, in set order)
+inline bool count_splits(int n, const TreeSet &set, const int32_t *weights, SplitTable &out, int *bad_tree = nullptr)
 {
-  const size_t len = 3 * (size_t)(2 * n - 1);
   out.n = n;
   out.words = words_of(n);
   out.total = 0;
   out.bits.clear();
   out.count.clear();
+  std::vector<TreeRef> refs;
+  const int stop = set_refs(n, set, refs);
+  if (stop >= 0) { if (bad_tree) *bad_tree = set.n_records + stop; return false; }
   SetIndex idx(out.words);
   TreeClusters c;
   std::vector<uint32_t> w((size_t)out.words);
-  for (int t = 0; t < n_trees; t++) {
+  for (size_t t = 0; t < refs.size(); t++) {
     const int64_t wt = weights ? weights[t] : 1;
-    const int32_t *back = backs + (size_t)t * len;
-    if (!links_ok(back, n) || !walk_clusters(back, n, c)) return false;
+    if (!tree_clusters(refs[t], n, c)) { if (bad_tree) *bad_tree = (int)t; return false; }
     if (wt == 0) continue;
     out.total += wt;
-    for (int ci = 0; ci < n - 3; ci++) {
+    for (int ci = 0; ci < c.size(); ci++) {
       cluster_bits(c, ci, out.words, w.data());
       int64_t k = idx.find(out.bits, w.data());
       if (k < 0) {
@@ -169,6 +349,13 @@ inline bool count_splits(int n, int n_trees, const int32_t *backs, const int32_t
     }
   }
   return true;
+}
+inline bool count_splits(int n, int n_trees, const int32_t *backs, const int32_t *weights, SplitTable &out)
+{
+  TreeSet s;
+  s.n_records = n_trees;
+  s.backs = backs;
+  return count_splits(n, s, weights, out);
 }
 
 // the contract order: count descending, then the set's words ascending as unsigned, word 0 first
@@ -344,72 +531,87 @@ inline std::vector<RfChunk> rf_chunk_plan(int64_t columns, int64_t rows, int64_t
   return plan;
 }
 
-// every tree's splits as a sorted list of ids into one exact table.  false: a tree is not a complete tree on n taxa
-inline bool rf_id_lists(int n, int n_trees, const int32_t *backs, SetIndex &idx, std::vector<uint32_t> &table, std::vector<int64_t> &ids)
+// one tree's splits as a sorted list of ids into one exact table, appended to ids.  false: the tree is not a complete tree on n taxa
+inline bool rf_id_list(int n, const TreeRef &r, SetIndex &idx, std::vector<uint32_t> &table, std::vector<int64_t> &ids)
 {
-  const size_t len = 3 * (size_t)(2 * n - 1);
-  const int words = words_of(n), C = std::max(n - 3, 0);
+  const int words = words_of(n);
   TreeClusters c;
   std::vector<uint32_t> w((size_t)words);
-  for (int t = 0; t < n_trees; t++) {
-    const int32_t *back = backs + (size_t)t * len;
-    if (!links_ok(back, n) || !walk_clusters(back, n, c)) return false;
-    const size_t at = ids.size();
-    for (int ci = 0; ci < C; ci++) {
-      cluster_bits(c, ci, words, w.data());
-      int64_t k = idx.find(table, w.data());
-      if (k < 0) {
-        k = (int64_t)(table.size() / (size_t)words);
-        table.insert(table.end(), w.begin(), w.end());
-        idx.insert(w.data(), k);
-      }
-      ids.push_back(k);
+  if (!tree_clusters(r, n, c)) return false;
+  const size_t at = ids.size();
+  for (int ci = 0; ci < c.size(); ci++) {
+    cluster_bits(c, ci, words, w.data());
+    int64_t k = idx.find(table, w.data());
+    if (k < 0) {
+      k = (int64_t)(table.size() / (size_t)words);
+      table.insert(table.end(), w.begin(), w.end());
+      idx.insert(w.data(), k);
     }
-    std::sort(ids.begin() + (long)at, ids.end());
+    ids.push_back(k);
   }
+  std::sort(ids.begin() + (long)at, ids.end());
   return true;
 }
 
-// MTreeSet::computeRFDist without the strings and without weights: the number of splits in one tree and not in the other.
-// out: the layout of the mode (all pairs [T][T]; adjacent [T - 1]; two sets [T][T2]).  false: a tree is broken (*bad_tree: which,
-// counted through both sets) or the mode is unknown
-inline bool host_rf(int n, int mode, int n_trees, const int32_t *backs, int n_trees2, const int32_t *backs2, std::vector<int32_t> &out,
-                    int *bad_tree = nullptr)
+// MTreeSet::computeRFDist without the strings and without weights: the number of splits in one tree and not in the other,
+// size(A) + size(B) - 2 common, for trees of either form (a fully resolved tree has n - 3 splits, a list tree with m inner nodes
+// m - 1).  out: the layout of the mode (all pairs [T][T]; adjacent [T - 1]; two sets [T][T2]).  false: a tree is broken
+// (*bad_tree: which, counted through both sets, each in set order) or the mode is unknown
+inline bool host_rf(int n, int mode, const TreeSet &s1, const TreeSet &s2, std::vector<int32_t> &out, int *bad_tree = nullptr)
 {
-  const int C = std::max(n - 3, 0), words = words_of(n);
+  const int words = words_of(n);
   SetIndex idx(words);
   std::vector<uint32_t> table;
-  std::vector<int64_t> ids, ids2;
+  std::vector<int64_t> ids;
+  std::vector<size_t> at{0};                         // tree t's ids: ids[at[t] .. at[t + 1])
   if (mode != RF_ALL_PAIRS && mode != RF_ADJACENT && mode != RF_TWO_SETS) return false;
-  for (int t = 0; t < n_trees; t++)
-    if (!rf_id_lists(n, 1, backs + (size_t)t * 3 * (size_t)(2 * n - 1), idx, table, ids)) { if (bad_tree) *bad_tree = t; return false; }
-  if (mode == RF_TWO_SETS)
-    for (int t = 0; t < n_trees2; t++)
-      if (!rf_id_lists(n, 1, backs2 + (size_t)t * 3 * (size_t)(2 * n - 1), idx, table, ids2)) { if (bad_tree) *bad_tree = n_trees + t; return false; }
-  auto dist = [&](const int64_t *a, const int64_t *b) {
+  std::vector<TreeRef> refs;
+  int stop = set_refs(n, s1, refs);
+  if (stop >= 0) { if (bad_tree) *bad_tree = s1.n_records + stop; return false; }
+  const int n_trees = (int)refs.size();
+  if (mode == RF_TWO_SETS) {
+    stop = set_refs(n, s2, refs);
+    if (stop >= 0) { if (bad_tree) *bad_tree = n_trees + s2.n_records + stop; return false; }
+  }
+  const int n_trees2 = (int)refs.size() - n_trees;
+  for (size_t t = 0; t < refs.size(); t++) {
+    if (!rf_id_list(n, refs[t], idx, table, ids)) { if (bad_tree) *bad_tree = (int)t; return false; }
+    at.push_back(ids.size());
+  }
+  auto dist = [&](int i, int j) {
+    const int64_t *a = ids.data() + at[(size_t)i], *b = ids.data() + at[(size_t)j];
+    const int na = (int)(at[(size_t)i + 1] - at[(size_t)i]), nb = (int)(at[(size_t)j + 1] - at[(size_t)j]);
     int shared = 0;
-    for (int i = 0, j = 0; i < C && j < C;) {
-      if (a[i] == b[j]) { shared++; i++; j++; }
-      else if (a[i] < b[j]) i++;
-      else j++;
+    for (int p = 0, q = 0; p < na && q < nb;) {
+      if (a[p] == b[q]) { shared++; p++; q++; }
+      else if (a[p] < b[q]) p++;
+      else q++;
     }
-    return (int32_t)(2 * C - 2 * shared);
+    return (int32_t)(na + nb - 2 * shared);
   };
   out.clear();
   if (mode == RF_ALL_PAIRS) {
     out.assign((size_t)n_trees * (size_t)n_trees, 0);
     for (int i = 0; i < n_trees; i++)
-      for (int j = i + 1; j < n_trees; j++)
-        out[(size_t)i * (size_t)n_trees + (size_t)j] = out[(size_t)j * (size_t)n_trees + (size_t)i] =
-            dist(ids.data() + (size_t)i * (size_t)C, ids.data() + (size_t)j * (size_t)C);
+      for (int j = i + 1; j < n_trees; j++) out[(size_t)i * (size_t)n_trees + (size_t)j] = out[(size_t)j * (size_t)n_trees + (size_t)i] = dist(i, j);
   } else if (mode == RF_ADJACENT) {
-    for (int i = 0; i + 1 < n_trees; i++) out.push_back(dist(ids.data() + (size_t)i * (size_t)C, ids.data() + (size_t)(i + 1) * (size_t)C));
+    for (int i = 0; i + 1 < n_trees; i++) out.push_back(dist(i, i + 1));
   } else {
     out.reserve((size_t)n_trees * (size_t)n_trees2);
     for (int i = 0; i < n_trees; i++)
-      for (int j = 0; j < n_trees2; j++) out.push_back(dist(ids.data() + (size_t)i * (size_t)C, ids2.data() + (size_t)j * (size_t)C));
+      for (int j = 0; j < n_trees2; j++) out.push_back(dist(i, n_trees + j));
   }
   return true;
+}
+inline bool host_rf(int n, int mode, int n_trees, const int32_t *backs, int n_trees2, const int32_t *backs2, std::vector<int32_t> &out,
+                    int *bad_tree = nullptr)
+{
+  TreeSet a, b;
+  a.n_records = n_trees;
+  a.backs = backs;
+  b.n_records = n_trees2;
+  b.backs = backs2;
+  return host_rf(n, mode, a, b, out, bad_tree);
 }
 
 }  // namespace splitsets

@@ -5,7 +5,8 @@
 // a hash map, computeConsensusTree (phyloanalysis.cpp:2488-2600) drops the splits at or below the threshold and keeps a maximal
 // compatible set (SplitGraph::findMaxCompatibleSplits, splitgraph.cpp:615-648), and the supports go onto the best tree's branches.
 //
-// Here the trees stay in the engine's record format.  The device makes every tree's clusters and counts them exactly (splits.hip:
+// Here the trees stay in the engine's record format, or come as CSR neighbour lists where an inner node has more than three
+// neighbours (the consensus tree itself, user trees with polytomies: the hand-over of mpf_polytomy_*).  The device makes every tree's clusters and counts them exactly (splits.hip:
 // keys -> insert -> count -> compact); the host checks the trees, resolves the overflow list of true key collisions through whole-set
 // comparison, puts the distinct splits in the contract order and runs the consensus rule on the kept sets (host/split_sets.hpp,
 // which holds everything that needs no device and is tested stand-alone under a sanitizer).
@@ -32,12 +33,13 @@ int bad(const std::string &what) { set_error("split summary: " + what); return M
 }  // namespace
 
 // The front half of every call on a tree set: the trees (already checked link by link by the caller) are staged, walked
-// (k_split_keys; a tree whose records do not form one tree ends the call, named by `name`), and their clusters inserted and counted
+// (k_split_keys over every run of record-format trees, k_split_keys_lists over all list trees, into the same pos / order / cluster
+// arrays; a tree whose records or lists do not form one tree ends the call, named by `name`), and their clusters inserted and counted
 // (k_split_insert, k_split_count, k_split_compact); the counters and the overflow list of true key collisions come back.
 // hw[i]: the weight of trees[i].  gather_last: the counts of the last tree's clusters go to split_.h_tsup (a target tree).
 // rf: k_rf_columns numbers the slots that at least two trees hold (p.rf_columns).  Afterwards split_.h_entries holds the p.D used
 // slots and split_.h_ids[p.D .. p.D + p.n_ovf) the overflow clusters, sorted
-int Engine::split_pass(const char *what, const std::vector<const int32_t *> &trees, const std::vector<int32_t> &hw,
+int Engine::split_pass(const char *what, const std::vector<splitsets::TreeRef> &trees, const std::vector<int32_t> &hw,
                        const std::function<std::string(size_t)> &name, bool gather_last, bool rf, SplitPass &p)
 {
   const int n = n_, C = n - 3;
@@ -48,9 +50,37 @@ int Engine::split_pass(const char *what, const std::vector<const int32_t *> &tre
   uint32_t tsize = 64;
   while ((uint64_t)tsize < 2ull * M) tsize <<= 1;
   SplitBufs &b = split_;
-  HIPCHK(b.h_backs.reserve(T * len));
-  for (size_t i = 0; i < T; i++) std::memcpy(b.h_backs.p + i * len, trees[i], len * sizeof(int32_t));
-  HIPCHK(b.backs.reserve(T * len));
+  size_t R = 0, L = 0, list_words = 0;
+  for (const splitsets::TreeRef &t : trees) {
+    if (!t.is_list()) { R++; continue; }
+    L++;
+    list_words += (size_t)t.n_inner + 1 + (size_t)t.first[t.n_inner];
+  }
+  HIPCHK(b.h_backs.reserve(R * len));
+  HIPCHK(b.backs.reserve(R * len));
+  constexpr size_t kDescWords = sizeof(SplitListDesc) / sizeof(int32_t);
+  if (L) {
+    // the list trees: their descriptors, then every tree's first[] and nbr[]
+    HIPCHK(b.h_lists.reserve(L * kDescWords + list_words));
+    HIPCHK(b.lists.reserve(L * kDescWords + list_words));
+    HIPCHK(b.n_splits.reserve(T));
+    HIPCHK(b.h_n_splits.reserve(T));
+  }
+  {
+    SplitListDesc *desc = reinterpret_cast<SplitListDesc *>(b.h_lists.p);
+    size_t r = 0, l = 0, at = L * kDescWords;
+    for (size_t i = 0; i < T; i++) {
+      const splitsets::TreeRef &t = trees[i];
+      if (L) b.h_n_splits.p[i] = t.clusters(n);
+      if (!t.is_list()) { std::memcpy(b.h_backs.p + r++ * len, t.back, len * sizeof(int32_t)); continue; }
+      const int32_t E = t.first[t.n_inner];
+      desc[l++] = SplitListDesc{(int32_t)i, t.n_inner, (int32_t)at, (int32_t)(at + (size_t)t.n_inner + 1), E,
+                                splitsets::list_root(n, t.n_inner, t.first, t.nbr)};
+      std::memcpy(b.h_lists.p + at, t.first, ((size_t)t.n_inner + 1) * sizeof(int32_t));
+      std::memcpy(b.h_lists.p + at + (size_t)t.n_inner + 1, t.nbr, (size_t)E * sizeof(int32_t));
+      at += (size_t)t.n_inner + 1 + (size_t)E;
+    }
+  }
   HIPCHK(b.pos.reserve(T * (size_t)n));
   HIPCHK(b.order.reserve(T * (size_t)(n - 1)));
   HIPCHK(b.cl.reserve(M));
@@ -64,19 +94,41 @@ int Engine::split_pass(const char *what, const std::vector<const int32_t *> &tre
   HIPCHK(b.entries.reserve(M));
   if (rf) HIPCHK(b.col_of_slot.reserve(tsize));
   unsigned long long *tkey = b.table.p, *trep = tkey + tsize, *tcount = trep + tsize;
-  HIPCHK(hipMemcpyAsync(b.backs.p, b.h_backs.p, T * len * sizeof(int32_t), hipMemcpyHostToDevice, st_));
+  if (R) HIPCHK(hipMemcpyAsync(b.backs.p, b.h_backs.p, R * len * sizeof(int32_t), hipMemcpyHostToDevice, st_));
+  if (L) {
+    HIPCHK(hipMemcpyAsync(b.lists.p, b.h_lists.p, (L * kDescWords + list_words) * sizeof(int32_t), hipMemcpyHostToDevice, st_));
+    HIPCHK(hipMemcpyAsync(b.n_splits.p, b.h_n_splits.p, T * sizeof(int32_t), hipMemcpyHostToDevice, st_));
+  }
   HIPCHK(hipMemcpyAsync(b.w.p, hw.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(tkey, 0xFF, 2 * (size_t)tsize * sizeof(unsigned long long), st_));      // keys and representatives: empty
   HIPCHK(hipMemsetAsync(tcount, 0, (size_t)tsize * sizeof(unsigned long long), st_));
   HIPCHK(hipMemsetAsync(b.counters.p, 0, 4 * sizeof(uint32_t), st_));
   if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
-  HIPCHK(launch_split_keys(st_, b.backs.p, (int)T, n, split_key_bits_, b.pos.p, b.order.p, b.cl.p, b.flags.p));
+  uint32_t key_launches = 0;
+  for (size_t i = 0, r = 0; i < T;) {                // the record walk over every run of record-format trees
+    if (trees[i].is_list()) { i++; continue; }
+    size_t j = i;
+    while (j < T && !trees[j].is_list()) j++;
+    HIPCHK(launch_split_keys(st_, b.backs.p + r * len, (int)(j - i), n, split_key_bits_, b.pos.p + i * (size_t)n, b.order.p + i * (size_t)(n - 1),
+                             b.cl.p + i * (size_t)C, b.flags.p + i));
+    key_launches++;
+    r += j - i;
+    i = j;
+  }
+  if (L) {                                           // the list walk over all list trees, into the same arrays
+    HIPCHK(launch_split_keys_lists(st_, reinterpret_cast<const SplitListDesc *>(b.lists.p), (int)L, b.lists.p, n, split_key_bits_, b.pos.p,
+                                   b.order.p, b.cl.p, b.flags.p));
+    key_launches++;
+  }
   if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
   HIPCHK(hipMemcpyAsync(b.h_flags.p, b.flags.p, T * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
   // the later kernels index through what the walk wrote: they start only behind a walk that ended well on every tree
   HIPCHK(hipStreamSynchronize(st_));
   for (size_t i = 0; i < T; i++)
-    if (b.h_flags.p[i]) { set_error(std::string(what) + ": " + name(i) + ": the records do not form one tree"); return MPF_E_INVALID; }
+    if (b.h_flags.p[i]) {
+      set_error(std::string(what) + ": " + name(i) + (trees[i].is_list() ? ": the lists do not form one tree" : ": the records do not form one tree"));
+      return MPF_E_INVALID;
+    }
   if (timing_) HIPCHK(hipEventRecord(ev2_, st_));
   HIPCHK(launch_split_insert(st_, b.cl.p, M, tkey, trep, tsize, b.slot_of.p));
   HIPCHK(launch_split_count(st_, b.cl.p, M, n, b.pos.p, b.order.p, trep, b.slot_of.p, b.w.p, tcount, b.ovf.p, b.counters.p));
@@ -107,7 +159,7 @@ int Engine::split_pass(const char *what, const std::vector<const int32_t *> &tre
   std::sort(b.h_ids.p + D, b.h_ids.p + D + n_ovf);
   for (uint32_t k = 0; k < n_ovf; k++)
     if (b.h_ids.p[D + k] >= M) { set_error(std::string(what) + ": overflow entry out of range"); return MPF_E_STATE; }
-  p = SplitPass{T, M, tsize, n_ovf, D, cols, trep, tcount};
+  p = SplitPass{T, M, tsize, n_ovf, D, cols, trep, tcount, key_launches, L ? b.n_splits.p : nullptr};
   return MPF_OK;
 }
 
@@ -132,11 +184,11 @@ int Engine::split_fetch_sets(size_t first, size_t m)
 
 // One pass over the trees.  r.table: the distinct splits with count > max(0, threshold * total) and, if want_sets, their sets -- in
 // no particular order.  target (may be null): one more tree of weight 0 whose clusters' counts come back in r.target_support,
-// indexed as splitsets::walk_clusters numbers them (r.target)
-int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, bool want_sets, double threshold, SplitRun &r)
+// indexed as splitsets::walk_clusters / walk_clusters_lists number them (r.target)
+int Engine::split_run(const splitsets::TreeSet &set, const int32_t *weights, const splitsets::TreeRef *target, bool want_sets, double threshold,
+                      SplitRun &r)
 {
   const int n = n_, C = n - 3, words = splitsets::words_of(n);
-  const size_t len = 3 * (size_t)(2 * n - 1);
   splitsets::SplitTable &tab = r.table;
   tab.n = n;
   tab.words = words;
@@ -145,39 +197,55 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
   tab.count.clear();
   r.target_support.clear();
   split_overflow_ = 0;
-  if (n_trees < 1 || !backs) return bad("no trees");
+  if (set.size() < 1 || set.n_records < 0 || set.n_lists < 0 || !set.pointers_ok()) return bad("no trees");
   if (n > kSplitMaxTaxa) {
     set_error("split summary: more than " + std::to_string(kSplitMaxTaxa) + " taxa (a tree's records and its walk's stack must fit 64 KiB of LDS)");
     return MPF_E_UNSUPPORTED;
   }
-  // the checks of mpf_set_tree on every tree; trees of weight 0 are left out here
+  // the checks of mpf_set_tree (records) or of the polytomy hand-over (lists) on every tree; trees of weight 0 are left out here
   std::vector<int32_t> &hw = split_hw_;
   std::vector<int32_t> &pick = split_pick_;
-  std::vector<const int32_t *> &trees = split_trees_;
+  std::vector<splitsets::TreeRef> &trees = split_trees_;
+  std::vector<splitsets::TreeRef> &all = split_all_;
   hw.clear();
   pick.clear();
   trees.clear();
-  for (int t = 0; t < n_trees; t++) {
+  all.clear();
+  const int stop = splitsets::set_refs(n, set, all);
+  auto tree_name = [&](size_t t) {
+    return t < (size_t)set.n_records ? "tree " + std::to_string(t) : "list tree " + std::to_string(t - (size_t)set.n_records);
+  };
+  std::string why;
+  for (size_t t = 0; t < all.size(); t++) {
     const int32_t w = weights ? weights[t] : 1;
-    if (w < 0) return bad("tree " + std::to_string(t) + " has a negative weight");
-    if (!splitsets::links_ok(backs + (size_t)t * len, n)) return bad("tree " + std::to_string(t) + ": inconsistent back links (a complete tree on n_taxa taxa is needed)");
+    if (w < 0) return bad(tree_name(t) + " has a negative weight");
+    if (all[t].is_list()) {
+      if (!splitsets::lists_ok(n, all[t].n_inner, all[t].first, all[t].nbr, &why)) return bad(tree_name(t) + ": " + why);
+    } else if (!splitsets::links_ok(all[t].back, n))
+      return bad(tree_name(t) + ": inconsistent back links (a complete tree on n_taxa taxa is needed)");
     if (!w) continue;
     tab.total += w;
     hw.push_back(w);
-    pick.push_back(t);
-    trees.push_back(backs + (size_t)t * len);
+    pick.push_back((int32_t)t);
+    trees.push_back(all[t]);
   }
+  if (stop >= 0) return bad("list tree " + std::to_string(stop) + ": n_inner or first[] are not those of a tree on n_taxa taxa");
   if (target) {
-    if (!splitsets::links_ok(target, n)) return bad("target tree: inconsistent back links (a complete tree on n_taxa taxa is needed)");
-    if (!splitsets::walk_clusters(target, n, r.target)) return bad("target tree: the records do not form one tree");
-    r.target_support.assign((size_t)std::max(C, 0), 0);
+    if (target->is_list()) {
+      if (!splitsets::lists_ok(n, target->n_inner, target->first, target->nbr, &why)) return bad("target tree: " + why);
+      if (!splitsets::walk_clusters_lists(n, target->n_inner, target->first, target->nbr, r.target)) return bad("target tree: the lists do not form one tree");
+    } else {
+      if (!splitsets::links_ok(target->back, n)) return bad("target tree: inconsistent back links (a complete tree on n_taxa taxa is needed)");
+      if (!splitsets::walk_clusters(target->back, n, r.target)) return bad("target tree: the records do not form one tree");
+    }
+    r.target_support.assign((size_t)r.target.size(), 0);
     hw.push_back(0);
-    trees.push_back(target);
+    trees.push_back(*target);
   }
   if (C < 1 || hw.empty()) return MPF_OK;
   SplitPass ps;
   int rc = split_pass("split summary", trees, hw,
-                      [&](size_t i) { return i < pick.size() ? "tree " + std::to_string(pick[i]) : std::string("target tree"); }, target != nullptr,
+                      [&](size_t i) { return i < pick.size() ? tree_name((size_t)pick[i]) : std::string("target tree"); }, target != nullptr,
                       false, ps);
   if (rc) return rc;
   SplitBufs &b = split_;
@@ -188,7 +256,7 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
   if (!n_ovf) {
     // no collision: every slot is one split and its count is final
     if (target)
-      for (int ci = 0; ci < C; ci++) r.target_support[(size_t)ci] = b.h_tsup.p[ci];
+      for (int ci = 0; ci < r.target.size(); ci++) r.target_support[(size_t)ci] = b.h_tsup.p[ci];
     size_t m = 0;
     for (uint32_t i = 0; i < D; i++)
       if (passes((int64_t)ent[i].count)) { b.h_ids.p[m++] = ent[i].rep; tab.count.push_back((int64_t)ent[i].count); }
@@ -226,7 +294,7 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
     if (g >= target_first) target_row[g - target_first] = row;
   }
   if (target)
-    for (int ci = 0; ci < C; ci++)
+    for (int ci = 0; ci < r.target.size(); ci++)
       r.target_support[(size_t)ci] = target_row[(size_t)ci] >= 0 ? cnt[(size_t)target_row[(size_t)ci]] : (int64_t)b.h_tsup.p[ci];
   for (size_t i = 0; i < cnt.size(); i++)
     if (passes(cnt[i])) {
@@ -237,35 +305,45 @@ int Engine::split_run(int n_trees, const int32_t *backs, const int32_t *weights,
 }
 
 // MTreeSet::convertSplits: the distinct splits of the trees with their summed weights, in the contract order
-int Engine::split_counts(int n_trees, const int32_t *backs, const int32_t *weights, splitsets::SplitTable &out)
+int Engine::split_counts(const splitsets::TreeSet &set, const int32_t *weights, splitsets::SplitTable &out)
 {
   SplitRun &r = split_run_;
-  int rc = split_run(n_trees, backs, weights, nullptr, true, -1.0, r);
+  int rc = split_run(set, weights, nullptr, true, -1.0, r);
   if (rc) return rc;
   splitsets::apply_order(r.table, splitsets::order_splits(r.table));
   out = r.table;
   return MPF_OK;
 }
 
-// the supports of the branches of `target`, in the walk order of branch_substitutions from tip 1 (fixNegativeBranch's walk)
-int Engine::split_support(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, std::vector<NniBranch> &br,
+// the supports of the branches of `target`: a record-format target in the walk order of branch_substitutions from tip 1
+// (fixNegativeBranch's walk), a list target in that of polytomy_branch_substitutions from tip 1 (the same walk, neighbours in list
+// order).  -1 on a leaf branch and -- a list target -- on the branch at tip 1
+int Engine::split_support(const splitsets::TreeSet &set, const int32_t *weights, const splitsets::TreeRef &target, std::vector<NniBranch> &br,
                           std::vector<int64_t> &support, int64_t *total)
 {
-  if (!target) return bad("null target tree");
+  if (target.is_list() && (!target.first || !target.nbr)) return bad("null target tree");
   SplitRun &r = split_run_;
-  int rc = split_run(n_trees, backs, weights, target, false, -1.0, r);
+  int rc = split_run(set, weights, &target, false, -1.0, r);
   if (rc) return rc;
-  std::vector<int32_t> cluster_of((size_t)2 * n_, -1);
+  const int N = target.is_list() ? n_ + target.n_inner : 2 * n_ - 2;
+  std::vector<int32_t> cluster_of((size_t)N + 1, -1);
   for (size_t ci = 0; ci < r.target.node.size(); ci++) cluster_of[(size_t)r.target.node[ci]] = (int32_t)ci;
   br.clear();
   struct F { int node, dad; };
   std::vector<F> st{F{1, 0}};
-  while (!st.empty()) {                            // Engine::branch_order on the target's records
+  if (target.is_list()) st[0] = F{splitsets::list_root(n_, target.n_inner, target.first, target.nbr), 1};
+  while (!st.empty()) {                            // Engine::branch_order on the target's records, or its like on the lists
     const F f = st.back();
     st.pop_back();
     if (f.dad) br.push_back(NniBranch{f.dad, f.node});
+    if (target.is_list()) {
+      if (f.node <= n_) continue;
+      for (int k = target.first[f.node - n_] - 1; k >= target.first[f.node - n_ - 1]; k--)
+        if (target.nbr[k] != f.dad) st.push_back(F{target.nbr[k], f.node});
+      continue;
+    }
     for (int s = (f.node > n_ ? 2 : 0); s >= 0; s--) {
-      const int nb = target[3 * f.node + s] / 3;
+      const int nb = target.back[3 * f.node + s] / 3;
       if (nb != f.dad) st.push_back(F{nb, f.node});
     }
   }
@@ -279,16 +357,43 @@ int Engine::split_support(int n_trees, const int32_t *backs, const int32_t *weig
 }
 
 // computeConsensusTree: threshold filter, contract order, greedy maximal compatible set, neighbour lists
-int Engine::consensus_tree(int n_trees, const int32_t *backs, const int32_t *weights, double threshold, splitsets::ListTree &out, int64_t *total)
+int Engine::consensus_tree(const splitsets::TreeSet &set, const int32_t *weights, double threshold, splitsets::ListTree &out, int64_t *total)
 {
   if (!(threshold >= 0.0 && threshold <= 1.0)) return bad("threshold must be in 0 .. 1");
   SplitRun &r = split_run_;
-  int rc = split_run(n_trees, backs, weights, nullptr, true, threshold, r);
+  int rc = split_run(set, weights, nullptr, true, threshold, r);
   if (rc) return rc;
   splitsets::apply_order(r.table, splitsets::order_splits(r.table));
   splitsets::build_lists(r.table, splitsets::greedy_compatible(r.table, threshold), out);
   if (total) *total = r.table.total;
   return MPF_OK;
+}
+
+// the same calls on record-format trees alone
+namespace {
+splitsets::TreeSet record_set(int n_trees, const int32_t *backs)
+{
+  splitsets::TreeSet s;
+  s.n_records = n_trees;
+  s.backs = backs;
+  return s;
+}
+}  // namespace
+int Engine::split_counts(int n_trees, const int32_t *backs, const int32_t *weights, splitsets::SplitTable &out)
+{
+  return split_counts(record_set(n_trees, backs), weights, out);
+}
+int Engine::split_support(int n_trees, const int32_t *backs, const int32_t *weights, const int32_t *target, std::vector<NniBranch> &br,
+                          std::vector<int64_t> &support, int64_t *total)
+{
+  if (!target) return bad("null target tree");
+  splitsets::TreeRef t;
+  t.back = target;
+  return split_support(record_set(n_trees, backs), weights, t, br, support, total);
+}
+int Engine::consensus_tree(int n_trees, const int32_t *backs, const int32_t *weights, double threshold, splitsets::ListTree &out, int64_t *total)
+{
+  return consensus_tree(record_set(n_trees, backs), weights, threshold, out, total);
 }
 
 // The weighted tree set of IQTree::summarizeBootstrap from the attached tracker.  rule 0: tree_weights[boot_trees[b]]++

@@ -297,6 +297,14 @@ def lists_to_back(first, nbr, n: int) -> np.ndarray:
     return back
 
 
+def back_to_lists(back, n: int):
+    """(first, nbr) of the binary tree `back`: inner node n + 1 + i lists the nodes behind its three records in slot order -- the
+    inverse of lists_to_back"""
+    back = np.asarray(back)
+    nbr = np.array([int(back[3 * v + s]) // 3 for v in range(n + 1, 2 * n - 1) for s in range(3)], dtype=np.int32)
+    return np.arange(0, 3 * (n - 2) + 1, 3, dtype=np.int32), nbr
+
+
 def lists_to_newick(first, nbr, names: list[str], support=None) -> str:
     """Newick string of a tree given as neighbour lists (tips 1 .. n, inner node i = node n + 1 + i), written from tip 1 with the
     neighbours in list order.  support[i] (optional, per inner node): written as the label of inner node i where it is >= 0 --
