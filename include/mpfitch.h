@@ -224,7 +224,15 @@ int mpf_optimize_spr(mpf_engine *e, int32_t mintrav, int32_t maxtrav, uint32_t *
 int mpf_optimize_spr_many(mpf_engine **engines, int32_t n_engines, int32_t mintrav, int32_t maxtrav, uint32_t *final_scores);
 /* ... one LAUNCH of it (every active climb to its optimum, or to a full move list), for callers with more climbs than engines:
    state[k] in: 0 = engine k takes no part, 1 = a climb STARTS on it now, 2 = its climb goes on; out: 2 = goes on, 0 = done
-   (final_scores[k] valid).  A finished engine gets its next tree (and weights, stream) and state 1 before the next round. */
+   (final_scores[k] valid).  A finished engine gets its next tree (and weights, stream) and state 1 before the next round.
+   The shape of a round's launch (mpboot_amd/host/many_shape.hpp): one launch has one tile width, number of states, word-major flag
+   and device, and a climb keeps the shape it STARTED on until it is done -- its tiles and per-tile scores are laid out for it, and
+   the width follows from the row pitch, i.e. from the weights.  The climbs that go on give the shape; a starting climb whose own
+   shape is another one (re-weighted across a pitch boundary, option "climb_tile", another alphabet or device) runs alone inside the
+   call, as every engine the batch cannot take; where no climb goes on, the first starting engine that fits the batch gives the shape.
+   MPF_E_STATE, before anything is touched: two climbs that go on in different shapes; a climb that goes on while its engine was
+   packed again (mpf_set_weights between two rounds) or no longer fits the shape it started on (an option changed); state 2 on an
+   engine that never started.  MPF_E_INVALID: an engine listed twice (as mpf_optimize_spr_many). */
 int mpf_optimize_spr_many_round(mpf_engine **engines, int32_t n_engines, int32_t mintrav, int32_t maxtrav, uint8_t *state, uint32_t *final_scores);
 
 /* _pllComputeRandomizedStepwiseAdditionParsimonyTree(tr, pr, sprDist, iqtree)

@@ -257,6 +257,8 @@ int mpf_optimize_spr_many_round(mpf_engine **engines, int32_t n_engines, int32_t
   std::vector<mpf::Engine *> es((size_t)n_engines);
   for (int k = 0; k < n_engines; k++) {
     if (!engines[k]) { set_error("mpf_optimize_spr_many_round: null engine"); return MPF_E_INVALID; }
+    // (two workgroups of one launch on one vector store)
+    for (int j = 0; j < k; j++) if (engines[j] == engines[k]) { set_error("mpf_optimize_spr_many_round: an engine is listed twice"); return MPF_E_INVALID; }
     es[(size_t)k] = &engines[k]->eng;
   }
   return mpf::Engine::climb_many_round(es.data(), n_engines, mintrav, maxtrav, state, final_scores);

@@ -28,6 +28,7 @@
 #include "../host/ufb_books.hpp"
 #include "../host/split_sets.hpp"
 #include "../host/refresh_plan.hpp"
+#include "../host/many_shape.hpp"
 #include "climb.hpp"
 #include "kernels.hpp"
 #include "ufboot.hpp"
@@ -683,8 +684,10 @@ public:
   static int climb_many(Engine **engs, int n, int mintrav, int maxtrav, uint32_t *scores);
   static int climb_many_round(Engine **engs, int n, int mintrav, int maxtrav, uint8_t *state, uint32_t *scores);
 private:
-  struct ManyState { uint32_t startMP = 0, randomMP = 0; unsigned iter_hits = 1; int i = 1; bool in_sweep = false; int tiles = 0; } many_;   // this engine's climb inside a batch
-  struct ManyBufs { DevBuf<ClimbParams> d_params; PinBuf<ClimbParams> h_params; } many_bufs_;   // a batch's parameter blocks (held by the batch's first engine)
+  ManyShape many_shape();                        // the shape k_climb_many would run this engine's climb on now (vw 0: none)
+  // (shape, gen: the launch shape the climb started on and pack_gen_ at that moment -- host/many_shape.hpp holds every later round to them)
+  struct ManyState { uint32_t startMP = 0, randomMP = 0; unsigned iter_hits = 1; int i = 1; bool in_sweep = false; int tiles = 0; ManyShape shape; uint64_t gen = 0; } many_;   // this engine's climb inside a batch
+  struct ManyBufs { DevBuf<ClimbParams> d_params; PinBuf<ClimbParams> h_params; } many_bufs_;   // a batch's parameter blocks (held by the batch's first member)
 
   // ---- device-resident stepwise addition (grow.hip; host/climb_host.cpp): one k_grow launch adds every taxon behind the start
   // tree, the insertions it reports are replayed onto the host's topology mirror

@@ -1225,7 +1225,9 @@ __global__ void k_pattern_sum(const uint32_t *__restrict__ planes, int n_chunks,
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_patterns) return;
   const int site = first_site[p];
-  if (site < 0) { ptn[p] = 0; return; }
+  // (a kept pattern of weight 0 has no site of its own: first_site names the NEXT pattern's -- and, behind the last pattern, the site
+  //  after the last one, which is a padding site (length 0) unless the sites fill the row to its last bit: then there is no such word)
+  if (site < 0 || site >= 32 * Wp) { ptn[p] = 0; return; }
   const int w = site >> 5, bit = site & 31;
   uint32_t total = 0;
   for (int ch = 0; ch < n_chunks; ch++)

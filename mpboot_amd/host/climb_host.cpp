@@ -80,9 +80,23 @@ int Engine::climb_fit_vw(bool one_workgroup)
     const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1));
     const int tiles = climb_tiles(g_, vw);
     const int wgs = climb_groups_ > 0 ? std::min(climb_groups_, tiles) : tiles;        // (fewer workgroups than tiles: each works through several)
-    if ((wgs + per_cu - 1) / per_cu <= cap) return vw;
+    if ((wgs + per_cu - 1) / per_cu > cap) continue;
+    // (a climb as ONE workgroup at a width the option "climb_tile" or the alphabet gave: k_climb_many's own footprint at that width,
+    //  in the shape its launch takes -- what does not fit there runs alone)
+    if (one_workgroup && climb_lds_bytes(g_, n_, vw, many_batch_max(), true, g_.S == 4 && vw == 4 && many_word_major_) > 160 * 1024) return 0;
+    return vw;
   }
   return 0;
+}
+
+ManyShape Engine::many_shape()
+{
+  ManyShape s;
+  s.vw = climb_fit_vw(true);
+  s.S = g_.S;
+  s.dev = dev_;
+  s.wm = g_.S == 4 && s.vw == 4 && many_word_major_;
+  return s;
 }
 
 // One launch of the climb kernel in three parts: climb_prepare lays the segment out (staging, parameters) and enqueues its uploads,
@@ -374,28 +388,39 @@ int Engine::climb_many_round(Engine **engs, int n, int mintrav, int maxtrav, uin
 {
   if (n <= 0) return MPF_OK;
   if (!engs || !scores || !state) { set_error("mpf_optimize_spr_many: null argument"); return MPF_E_INVALID; }
-  int first = -1;
-  for (int k = 0; k < n; k++) if (state[k]) { first = k; break; }
-  if (first < 0) return MPF_OK;
-  Engine &e0 = *engs[first];
-  const int vw0 = e0.climb_fit_vw(true);
-  // a starting climb's preamble (the full evaluate of :3277) on its own engine; what does not fit the batch runs alone, here
-  std::vector<int> starting;
+  // which climbs share the launch, on what shape, and which run alone: decided before anything is touched (host/many_shape.hpp)
+  std::vector<ManyEntry> tab((size_t)n);
   for (int k = 0; k < n; k++) {
-    if (state[k] != 1) continue;
+    ManyEntry &t = tab[(size_t)k];
+    t.state = state[k];
+    if (!state[k]) continue;
     Engine &e = *engs[k];
-    if (!e.have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
-    const int mt_eff = std::min(maxtrav, e.n_ - 3);
-    const bool fits = vw0 > 0 && e.dev_ == e0.dev_ && e.g_.S == e0.g_.S && !e.sankoff_ && !e.rand_fn_ && !(e.ufb_ && !e.ufb_->suspended) && mintrav == 1 &&
-                      e.max_visits_ == 0 && e.scan_mode_ == 1 && e.climb_device_ > 0 && climb_supported(e.g_, e.n_, mt_eff, e.many_batch_max()) && e.climb_fit_vw(true) == vw0;
-    if (!fits) {
-      const int rc = e.optimize_spr(mintrav, maxtrav, &scores[k]);
-      if (rc) return rc;
-      state[k] = 0;
-      continue;
+    t.now = e.many_shape();
+    t.pack_gen = e.pack_gen_;
+    if (state[k] == 1) {
+      if (!e.have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
+      const int mt_eff = std::min(maxtrav, e.n_ - 3);
+      t.fits = t.now.vw > 0 && !e.sankoff_ && !e.rand_fn_ && !(e.ufb_ && !e.ufb_->suspended) && mintrav == 1 && e.max_visits_ == 0 && e.scan_mode_ == 1 &&
+               e.climb_device_ > 0 && climb_supported(e.g_, e.n_, mt_eff, e.many_batch_max());
+    } else {
+      t.started = e.many_.shape;
+      t.started_gen = e.many_.gen;
     }
-    starting.push_back(k);
   }
+  const ManyPlan plan = many_shape_decide(tab.data(), n);
+  if (plan.rc) { set_error(plan.error); return plan.rc; }
+  // a starting climb's preamble (the full evaluate of :3277) on its own engine; what does not fit the batch runs alone, here
+  for (int k : plan.alone) {
+    const int rc = engs[k]->optimize_spr(mintrav, maxtrav, &scores[k]);
+    if (rc) return rc;
+    state[k] = 0;
+  }
+  if (plan.batch.empty()) return MPF_OK;
+  // (the first member lends the launch its stream and its parameter blocks; width, word-major flag and LDS come from the shape)
+  Engine &e0 = *engs[plan.batch[0]];
+  const ManyShape shape = plan.shape;
+  std::vector<int> starting;
+  for (int k : plan.batch) if (state[k] == 1) starting.push_back(k);
   {
     auto preamble = [&](int k) -> int {
       Engine &e = *engs[k];
@@ -411,6 +436,8 @@ int Engine::climb_many_round(Engine **engs, int n, int mintrav, int maxtrav, uin
       e.visits_done_ = 0;
       e.many_ = ManyState{};
       e.many_.randomMP = len;
+      e.many_.shape = shape;
+      e.many_.gen = e.pack_gen_;
       return MPF_OK;
     };
     // (an evaluate per engine, each with its own stream and its own wait: a quarter of a millisecond one after the other --
@@ -451,26 +478,27 @@ int Engine::climb_many_round(Engine **engs, int n, int mintrav, int maxtrav, uin
     if (!s.in_sweep) { s.startMP = s.randomMP; e.node_rectifier(); s.i = 1; s.in_sweep = true; }
     int vw = 0;
     const int rc = e.climb_prepare(std::min(maxtrav, e.n_ - 3), total, s.i, s.randomMP, s.iter_hits, false, 1, e0.st_, mb.h_params.p[batch.size()], &vw, &s.tiles,
-                                   e0.many_sweeps_inside_, s.startMP);
+                                   e.many_sweeps_inside_, s.startMP);
     if (rc) return rc;
+    if (vw != shape.vw) { set_error("mpf_optimize_spr_many: a climb was laid out for another tile width than its launch's"); return MPF_E_STATE; }
     max_ns = std::max(max_ns, (uint32_t)e.nslots_);
     batch.push_back(k);
   }
   if (batch.empty()) return MPF_OK;
   const auto t_prep = std::chrono::steady_clock::now();
   HIPCHK(hipMemcpyAsync(mb.d_params.p, mb.h_params.p, batch.size() * sizeof(ClimbParams), hipMemcpyHostToDevice, e0.st_));
-  const bool wm = e0.g_.S == 4 && vw0 == 4 && e0.many_word_major_;
+  const bool wm = shape.wm;
   size_t lds = 0;
   for (size_t b = 0; b < batch.size(); b++) {
     Engine &e = *engs[batch[b]];
-    lds = std::max(lds, climb_lds_bytes(e.g_, e.n_, vw0, (int)mb.h_params.p[b].batch_max, true, wm));
+    lds = std::max(lds, climb_lds_bytes(e.g_, e.n_, shape.vw, (int)mb.h_params.p[b].batch_max, true, wm));
   }
-  HIPCHK(launch_climb_many(e0.st_, e0.g_, vw0, mb.d_params.p, (int)batch.size(), lds, wm));
+  HIPCHK(launch_climb_many(e0.st_, e0.g_, shape.vw, mb.d_params.p, (int)batch.size(), lds, wm));
   for (int k : batch) {
     Engine &e = *engs[k];
     const size_t out_words = hdr_words + 3 * (size_t)e.cd_.max_moves;
     HIPCHK(hipMemcpyAsync(e.cd_.h_out.p, e.cd_.out.p, out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, e0.st_));
-    if (e0.many_sweeps_inside_) HIPCHK(hipMemcpyAsync(e.cd_.h_order.p, e.cd_.order.p, (size_t)(2 * e.n_ - 2) * sizeof(uint16_t), hipMemcpyDeviceToHost, e0.st_));
+    if (e.many_sweeps_inside_) HIPCHK(hipMemcpyAsync(e.cd_.h_order.p, e.cd_.order.p, (size_t)(2 * e.n_ - 2) * sizeof(uint16_t), hipMemcpyDeviceToHost, e0.st_));
   }
   {
     // (bounded like every wait on this kernel: climb_segment)

@@ -287,7 +287,7 @@ int Engine::nni_pattern_terms(int root_taxon, std::vector<NniBranch> &br, std::v
   for (size_t r = 0; r < 3 * nb; r++)
     for (int p = 0; p < P_; p++) {
       const int site = first_site_[(size_t)p];
-      if (site < 0) continue;
+      if (site < 0 || (size_t)site >= 32 * Wp) continue;      // (weight 0 behind the last site of a full row: k_pattern_sum)
       const size_t w = r * Wp + (size_t)(site >> 5);
       terms[r * (size_t)P_ + (size_t)p] = (uint8_t)(((h[w] >> (site & 31)) & 1u) + 2u * ((h[rows_p * Wp + w] >> (site & 31)) & 1u));
     }
