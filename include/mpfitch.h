@@ -381,6 +381,54 @@ int mpf_polytomy_branch_substitutions(mpf_engine *e, int32_t n_inner, const int3
                                       int32_t *node1, int32_t *node2, uint32_t *subst, int32_t *n);
 int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_sites,
                                 int32_t unit_cost_parstree, int32_t cap, int32_t *node1, int32_t *node2, double *length /* [cap] */, int32_t *n);
+/* Taxon insertion: what it costs to attach taxon t to branch b of a tree that does not hold t yet.  The reference asks this in
+   PhyloTree::addTaxonMPFast (phylotree.cpp:1322-1378), which tries the taxon on every branch in a pre-order walk from the root
+   leaf -- first (root leaf, its neighbour), then FOR_NEIGHBOR_IT(node, dad, it) in neighbors[] order, the walk of
+   fixNegativeBranch -- calls computeParsimonyBranch at each and keeps the FIRST strictly smallest score (no random draw).  On top
+   of it sit PhyloTree::computeParsimonyTree (phylotree.cpp:1243-1320: the start tree of -starttree PARS, tools.cpp:1476-1489, and
+   the fall-back when PLL cannot take the data, phyloanalysis.cpp:1671-1681) and IQTree::reinsertLeavesByParsimony
+   (iqtree.cpp:981-1016).
+
+   The backbone is handed over as the lists of mpf_polytomy_* with ONE relaxation: tips may be absent.  MPF_E_INVALID unless every
+   tip occurs at most once, at least three occur, adjacency is symmetric, there are tips + n_inner - 1 edges, the tree is connected
+   and root_taxon is one of the tips present.  Every inner node must have degree exactly 3, else MPF_E_UNSUPPORTED (the k-ary Fitch
+   rule depends on the root; an insertion cost on such a tree is not what any reference function computes).  Query taxa are rows of
+   the engine's alignment, absent from the backbone and pairwise distinct (else MPF_E_INVALID); n_query = 0 is legal.
+   MPF_E_UNSUPPORTED with a message on a weighted engine: there the cost is a min-plus product rooted as parstree.cpp:439-541 roots
+   it, another kernel family, not served yet.
+
+   Fitch length does not depend on the root, so with A, B the two directed views of a branch and T the query tip the length is
+   len(backbone) + #sites where X and T share no state, X = A & B where that is non-empty, else A | B: all views come from one
+   k_poly_views launch, the Q x B x sites popcount product from k_place_costs (place.hip), which joins A and B on its way into LDS.
+   Patterns follow the contract of mpf_branch_substitutions: an engine made with keep_all_sites = 1 counts what IQ-TREE counts, one
+   that drops uninformative patterns counts the kept ones (on data without ambiguity-only variation the difference is a constant
+   per query and the chosen branch is the same).  Stateless towards the engine's own tree exactly as the polytomy calls are.
+   Options: "place_tile" (0 = from the number of outputs | 1 = narrow, 4 queries x 16 branches per workgroup | 2 = wide, 64 x 64 for 4
+   state rows, 32 x 32 for 20 and 32), read-only "place_launches" and, under "timing", "place_kernel_ns".
+
+   mpf_insertion_costs: every insertion test of addTaxonMPFast for each query taxon: cost[q * cap + i] = length of the backbone with
+   query_taxa[q] attached to branch i; branches in the order of mpf_polytomy_branch_substitutions for the same lists (*n = 2 m - 3
+   for m tips); sizing protocol of mpf_nni_scores (arrays filled when cap >= *n); *tree_length = length of the backbone. */
+int mpf_insertion_costs(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon,
+                        int32_t n_query, const int32_t *query_taxa, int32_t cap, int32_t *node1, int32_t *node2,
+                        uint32_t *cost, int32_t *n, uint32_t *tree_length);
+/* addTaxonMPFast's answer per query: the first minimum in walk order (best_branch = its index in that order, best_node1 / 2 its
+   ends, best_length the length of the tree with the taxon there); the minimum is taken on the device (k_place_best: the lowest
+   branch index among the minima), the Q x B matrix is not copied back.  Outputs may be NULL. */
+int mpf_place_taxa(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon,
+                   int32_t n_query, const int32_t *query_taxa, int32_t *best_branch, int32_t *best_node1,
+                   int32_t *best_node2, uint32_t *best_length, uint32_t *tree_length);
+/* PhyloTree::computeParsimonyTree.  tie_state != NULL: order[] is filled by my_random_shuffle (tools.h:2107-2113: identity, then for
+   i = n - 1 .. 1 swap(order[i], order[random_int(i + 1)])) from that stream (n - 1 draws, state advanced, as mpf_iq_random_nnis
+   hands a stream over); NULL: order[] (1-based, a permutation) is taken as given.  The start is the star of order[0 .. 2] rooted at
+   the leaf order[0]; every later taxon is tried on every branch (all views made again, one Q = 1 placement) and put at the first
+   minimum: the new inner node takes target_dad's place in target_node's list and the other way round, in place, and lists
+   [new taxon, target_node, target_dad].  Out: the tree as lists in the reference's neighbors[] order (first[n - 1], nbr[3 (n - 2)];
+   inner node 0 = the centre of the first three, inner node k = the node made for order[k + 2]), length_per_step[j] = length of
+   the tree of the first j + 3 taxa (j = 0 .. n - 3), *score = the last.  The engine's own tree is not replaced: convert the lists
+   (record slot = list position) and call mpf_set_tree to climb from it. */
+int mpf_iq_parsimony_tree(mpf_engine *e, uint64_t *tie_state, int32_t *order, int32_t *first, int32_t *nbr,
+                          uint32_t *length_per_step, uint32_t *score);
 /* The summary of a -bb run: split supports and the bootstrap consensus tree.  The reference weights the booked trees by the samples
    that point to them (IQTree::summarizeBootstrap, iqtree.cpp:4020-4165), turns every tree into Split objects through its Newick
    string and counts them in a hash map (MTreeSet::convertSplits, mtreeset.cpp:288-470), and builds the consensus from the counted

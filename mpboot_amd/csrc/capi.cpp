@@ -3,6 +3,7 @@
 #include <new>
 
 #include "engine.hpp"
+#include "place.hpp"
 
 namespace mpf { const std::string &last_error(); }
 
@@ -424,6 +425,70 @@ int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *f
     node2[i] = br[i].node2;
     length[i] = parsimony_branch_length((int)s[i], n_sites, e->eng.S());
   }
+  return MPF_OK;
+}
+
+// ---- taxon insertion (host/place.cpp): addTaxonMPFast's tests on a backbone given as neighbour lists, computeParsimonyTree
+int mpf_insertion_costs(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_query,
+                        const int32_t *query_taxa, int32_t cap, int32_t *node1, int32_t *node2, uint32_t *cost, int32_t *n, uint32_t *tree_length)
+{
+  NEED(e);
+  if (!n) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<uint32_t> d;
+  uint32_t len = 0;
+  const bool fill = (int64_t)cap >= 2 * (int64_t)n_inner + 1;       // (a binary backbone of m = n_inner + 2 tips has 2 m - 3 branches)
+  const int rc = e->eng.place_costs(n_inner, first, nbr, root_taxon, n_query, query_taxa, br, fill ? &d : nullptr, nullptr, &len);
+  if (rc) return rc;
+  *n = (int32_t)br.size();
+  if (tree_length) *tree_length = len;
+  if (cap < *n) return MPF_OK;
+  if (!node1 || !node2 || (n_query > 0 && !cost)) { set_error("null output"); return MPF_E_INVALID; }
+  for (size_t i = 0; i < br.size(); i++) {
+    node1[i] = br[i].node1;
+    node2[i] = br[i].node2;
+  }
+  for (int q = 0; q < n_query; q++)
+    for (size_t i = 0; i < br.size(); i++) cost[(size_t)q * (size_t)cap + i] = len + d[(size_t)q * br.size() + i];
+  return MPF_OK;
+}
+
+int mpf_place_taxa(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_query,
+                   const int32_t *query_taxa, int32_t *best_branch, int32_t *best_node1, int32_t *best_node2, uint32_t *best_length,
+                   uint32_t *tree_length)
+{
+  NEED(e);
+  std::vector<mpf::Engine::NniBranch> br;
+  std::vector<mpf::Engine::PlaceBest> best;
+  uint32_t len = 0;
+  const int rc = e->eng.place_costs(n_inner, first, nbr, root_taxon, n_query, query_taxa, br, nullptr, &best, &len);
+  if (rc) return rc;
+  if (tree_length) *tree_length = len;
+  for (int q = 0; q < n_query; q++) {
+    const mpf::Engine::NniBranch at = br[(size_t)best[(size_t)q].branch];
+    if (best_branch) best_branch[q] = (int32_t)best[(size_t)q].branch;
+    if (best_node1) best_node1[q] = at.node1;
+    if (best_node2) best_node2[q] = at.node2;
+    if (best_length) best_length[q] = len + best[(size_t)q].delta;
+  }
+  return MPF_OK;
+}
+
+int mpf_iq_parsimony_tree(mpf_engine *e, uint64_t *tie_state, int32_t *order, int32_t *first, int32_t *nbr, uint32_t *length_per_step,
+                          uint32_t *score)
+{
+  NEED(e);
+  if (!order || !first || !nbr) { set_error("mpf_iq_parsimony_tree: null argument"); return MPF_E_INVALID; }
+  const int n = e->eng.n();
+  if (tie_state) mpf::place_shuffle_order(n, tie_state, order);
+  std::vector<int32_t> f, nb;
+  std::vector<uint32_t> len((size_t)std::max(n - 2, 1), 0u);
+  const int rc = e->eng.parsimony_tree(order, f, nb, len.data());
+  if (rc) return rc;
+  std::copy(f.begin(), f.end(), first);
+  std::copy(nb.begin(), nb.end(), nbr);
+  if (length_per_step) std::copy(len.begin(), len.end(), length_per_step);
+  if (score) *score = len.back();
   return MPF_OK;
 }
 

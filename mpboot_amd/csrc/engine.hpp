@@ -358,6 +358,17 @@ class Engine {
   int polytomy_branch_substitutions(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, std::vector<NniBranch> &br,
                                     std::vector<uint32_t> &subst, uint32_t *fitch_len = nullptr);
 
+  // ---- taxon insertion (host/place.cpp, place.hip; reference PhyloTree::addTaxonMPFast, phylotree.cpp:1322-1378): the backbone is a
+  // BINARY tree over a subset of the tips, given as the polytomy calls take their lists with tips allowed to be absent.  br = its
+  // branches in the order of polytomy_branch_substitutions; delta (null: not wanted) [n_query][br.size()] = substitutions the
+  // attachment of query q in the middle of branch b adds to the backbone's length; best (null: not wanted) [n_query] = (lowest
+  // delta, first branch of the walk that has it), made on the device.  Fitch engine only.  Stateless as the polytomy calls are
+  struct PlaceBest { uint32_t delta, branch; };
+  int place_costs(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, int n_query, const int32_t *query_taxa,
+                  std::vector<NniBranch> &br, std::vector<uint32_t> *delta, std::vector<PlaceBest> *best, uint32_t *tree_length);
+  // PhyloTree::computeParsimonyTree (phylotree.cpp:1243-1320) over order[0 .. n) (1-based taxa): n - 3 exhaustive Q = 1 placements
+  int parsimony_tree(const int32_t *order, std::vector<int32_t> &first, std::vector<int32_t> &nbr, uint32_t *length_per_step);
+
   // ---- the summary of a -bb run (host/splits.cpp, splits.hip; reference IQTree::summarizeBootstrap, MTreeSet::convertSplits,
   // computeConsensusTree): the splits of a weighted set of complete trees counted exactly on the device, the supports of a target
   // tree's branches, the consensus tree as neighbour lists.  Stateless towards the engine's own tree and its vectors
@@ -625,8 +636,9 @@ class Engine {
     std::vector<PolyOut> outs;
     int n_rows = 0;                              // step-mask rows (Fitch): one per up view + the root edge
   } poly_tree_;
-  int polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, PolyTree &t) const;
-  int polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, bool all_views, PolyTree &t);
+  // absent_tips (taxon insertion only): tips may be missing from the lists; parent / tip_nb of such a tip stay -1 / 0
+  int polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, PolyTree &t, bool absent_tips = false) const;
+  int polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, bool all_views, PolyTree &t, bool absent_tips = false);
   void polytomy_view_time();
   int poly_tile_ = 0;
   bool poly_view_timed_ = false;
@@ -639,6 +651,12 @@ class Engine {
   PinBuf<uint16_t> h_poly_ptn_;
   DevBuf<int32_t> d_poly_first_;                 // first_site_ on the device, as of packing poly_first_gen_
   uint64_t poly_first_gen_ = ~0ull;
+  // taxon insertion: option "place_tile" (0 = from the number of outputs, queries x branches, 1 = the narrow shape, 2 = the wide shape; place.hpp), read-only
+  // place_launches (k_place_costs launches) and, under "timing", place_kernel_ns (HIP-event time of k_place_costs + k_place_best)
+  int place_tile_ = 0;
+  uint64_t place_launches_ = 0, place_kernel_ns_ = 0;
+  DevBuf<uint32_t> d_place_q_, d_place_out_;
+  PinBuf<uint32_t> h_place_q_, h_place_out_;
 
   int addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *insert_per_step);
   void apply_move(int remove_rec, int insert_rec);

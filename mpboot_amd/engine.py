@@ -37,6 +37,7 @@ EXPORTS = [
     "mpf_optimize_nni", "mpf_nni_scores", "mpf_get_nni_moves", "mpf_ufboot_optimize_nni", "mpf_nni_pattern_terms", "mpf_nni_pattern_lengths",
     "mpf_branch_substitutions", "mpf_branch_lengths",
     "mpf_polytomy_parsimony", "mpf_polytomy_branch_substitutions", "mpf_polytomy_branch_lengths",
+    "mpf_insertion_costs", "mpf_place_taxa", "mpf_iq_parsimony_tree",
     "mpf_split_counts", "mpf_split_support", "mpf_consensus_tree", "mpf_ufboot_summarize", "mpf_ufboot_summary_trees",
     "mpf_rf_distances",
     "mpf_split_counts_set", "mpf_split_support_set", "mpf_consensus_tree_set", "mpf_rf_distances_set",
@@ -200,6 +201,9 @@ def load_library():
         L.mpf_polytomy_parsimony.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
         L.mpf_polytomy_branch_substitutions.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.mpf_polytomy_branch_lengths.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.mpf_insertion_costs.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.mpf_place_taxa.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+        L.mpf_iq_parsimony_tree.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.mpf_split_counts.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]
         L.mpf_split_support.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_consensus_tree.argtypes = [vp, C.c_int32, vp, vp, C.c_double, vp, vp, vp, vp, vp]
@@ -697,6 +701,71 @@ class FitchEngine:
                                                         _p(a), _p(b), _p(ln), C.byref(n)))
         assert n.value == m
         return a[:m], b[:m], ln[:m]
+
+    # ---- taxon insertion (host/place.cpp, place.hip): a binary backbone over a subset of the tips, as neighbour lists
+    def insertion_costs(self, first, nbr, queries, root_taxon: int = 1, cap=None):
+        """every insertion test of addTaxonMPFast: (node1[m], node2[m], cost[Q][m], tree_length) -- cost[q][i] = the length of the
+        backbone (first, nbr: the lists of polytomy_branch_substitutions with tips allowed to be absent, every inner degree 3) with
+        taxon queries[q] attached to branch i = (node1[i], node2[i]), branches in the walk order from root_taxon, m = 2 tips - 3.
+        cap (tests): the room handed to the C call; below m nothing is filled and only (m, tree_length) comes back."""
+        f, nb, k = self._lists(first, nbr)
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        m = 2 * k + 1 if cap is None else int(cap)
+        n = C.c_int32()
+        ln = C.c_uint32()
+        a = np.zeros(max(m, 1), dtype=np.int32)
+        b = np.zeros(max(m, 1), dtype=np.int32)
+        c = np.zeros((max(len(q), 1), max(m, 1)), dtype=np.uint32)
+        _chk(load_library().mpf_insertion_costs(self.h, k, _p(f), _p(nb), root_taxon, len(q), _p(q) if len(q) else None, m, _p(a), _p(b),
+                                                _p(c), C.byref(n), C.byref(ln)))
+        if n.value > m:
+            return int(n.value), int(ln.value)
+        return a[:n.value], b[:n.value], c[:len(q), :n.value], int(ln.value)
+
+    def place_taxa(self, first, nbr, queries, root_taxon: int = 1):
+        """addTaxonMPFast's answer for every query taxon: (branch[Q], node1[Q], node2[Q], length[Q], tree_length) -- the first branch
+        of the walk from root_taxon with the smallest length (found on the device: the Q x m matrix is not copied back).
+
+        IQTree::reinsertLeavesByParsimony, leaves deleted from the record tree `back` put back one by one at their best branch:
+
+            first, nbr = trees.drop_tips(back, n, leaves)
+            for t in leaves:
+                _, a, b, _, _ = eng.place_taxa(first, nbr, [t])
+                first, nbr = trees.insert_tip(first, nbr, n, t, int(a[0]), int(b[0]))
+            back = trees.lists_to_back(first, nbr, n)
+        """
+        f, nb, k = self._lists(first, nbr)
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        Q = len(q)
+        br = np.zeros(max(Q, 1), dtype=np.int32)
+        a = np.zeros(max(Q, 1), dtype=np.int32)
+        b = np.zeros(max(Q, 1), dtype=np.int32)
+        ln = np.zeros(max(Q, 1), dtype=np.uint32)
+        tl = C.c_uint32()
+        _chk(load_library().mpf_place_taxa(self.h, k, _p(f), _p(nb), root_taxon, Q, _p(q) if Q else None, _p(br), _p(a), _p(b), _p(ln),
+                                           C.byref(tl)))
+        return br[:Q], a[:Q], b[:Q], ln[:Q], int(tl.value)
+
+    def iq_parsimony_tree(self, order=None, tie_state=None):
+        """PhyloTree::computeParsimonyTree (-starttree PARS): stepwise addition with every branch tried at every step and the first
+        minimum taken -> (first, nbr, lengths[n - 2], order[n], tie_state).  order (1-based permutation) is taken as given; with
+        tie_state instead it is drawn by my_random_shuffle from that state of the host's random_double() stream (n - 1 draws), and the
+        state behind them comes back.  lengths[j] = the length of the tree of the first j + 3 taxa.  The engine's own tree stays:
+        set_tree(trees.lists_to_back(first, nbr, n)) to climb from the result."""
+        n = self.n
+        if (order is None) == (tie_state is None):
+            raise ValueError("iq_parsimony_tree: give either order or tie_state")
+        o = np.zeros(n, dtype=np.int32) if order is None else np.ascontiguousarray(order, dtype=np.int32).copy()
+        if len(o) != n:
+            raise ValueError("iq_parsimony_tree: order must list all taxa")
+        st = None if tie_state is None else C.c_uint64(int(tie_state) & ((1 << 64) - 1))
+        f = np.zeros(n - 1, dtype=np.int32)
+        nb = np.zeros(3 * (n - 2), dtype=np.int32)
+        ln = np.zeros(max(n - 2, 1), dtype=np.uint32)
+        sc = C.c_uint32()
+        _chk(load_library().mpf_iq_parsimony_tree(self.h, None if st is None else C.byref(st), _p(o), _p(f), _p(nb), _p(ln), C.byref(sc)))
+        assert int(sc.value) == int(ln[-1])
+        return f, nb, ln, o, (None if st is None else int(st.value))
 
     # ---- the summary of a -bb run: split counts, supports on a tree, consensus tree (host/splits.cpp, splits.hip)
     def _tree_set(self, backs, weights):

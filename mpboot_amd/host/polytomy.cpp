@@ -35,7 +35,7 @@ int bad(const std::string &what) { set_error("polytomy tree: " + what); return M
 // (splitsets::lists_ok of host/split_sets.hpp restates these conditions device-free for the mpf_*_set calls: change both together.)
 // The checks of the hand-over (include/mpfitch.h) and the rooted shape: parent and pre-order of every node from the root leaf,
 // neighbours in list order (fixNegativeBranch's walk: FOR_NEIGHBOR_IT(node, dad, it))
-int Engine::polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, PolyTree &t) const
+int Engine::polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, PolyTree &t, bool absent_tips) const
 {
   const int n = n_;
   if (!first || !nbr) return bad("null neighbour lists");
@@ -59,14 +59,18 @@ int Engine::polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr
         t.tip_nb[(size_t)u] = v;
       } else arcs.emplace_back(v, u);
     }
-  for (int u = 1; u <= n; u++)
-    if (!t.tip_nb[(size_t)u]) return bad("tip " + std::to_string(u) + " does not occur");
+  int m = 0;                                             // tips that occur
+  for (int u = 1; u <= n; u++) {
+    if (t.tip_nb[(size_t)u]) m++;
+    else if (!absent_tips) return bad("tip " + std::to_string(u) + " does not occur");
+  }
+  if (!t.tip_nb[(size_t)root_taxon]) return bad("root_taxon does not occur");
   std::sort(arcs.begin(), arcs.end());
   for (size_t i = 0; i < arcs.size(); i++) {
     if (i && arcs[i] == arcs[i - 1]) return bad("a neighbour is listed twice");
     if (!std::binary_search(arcs.begin(), arcs.end(), std::make_pair(arcs[i].second, arcs[i].first))) return bad("adjacency is not symmetric");
   }
-  if ((int64_t)n + (int64_t)arcs.size() / 2 != (int64_t)N - 1) return bad("not n_taxa + n_inner - 1 edges");
+  if ((int64_t)m + (int64_t)arcs.size() / 2 != (int64_t)(m + n_inner) - 1) return bad("not n_taxa + n_inner - 1 edges");
   // pre-order from the root leaf
   t.parent.assign((size_t)N + 1, -1);
   t.order.clear();
@@ -93,14 +97,14 @@ int Engine::polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr
       st.push_back(u);
     }
   }
-  if ((int)t.order.size() != N) return bad("the tree is not connected");
+  if ((int)t.order.size() != m + n_inner) return bad("the tree is not connected");
   return MPF_OK;
 }
 
 // items of the view launch: up views by height, the root edge (Fitch), down views by depth
-int Engine::polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, bool all_views, PolyTree &t)
+int Engine::polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, bool all_views, PolyTree &t, bool absent_tips)
 {
-  int rc = polytomy_check(n_inner, first, nbr, root_taxon, t);
+  int rc = polytomy_check(n_inner, first, nbr, root_taxon, t, absent_tips);
   if (rc) return rc;
   const int n = n_, N = n + n_inner;
   // whatever the engine's own tree has under way is finished first; its vectors are about to be overwritten

@@ -305,6 +305,53 @@ def back_to_lists(back, n: int):
     return np.arange(0, 3 * (n - 2) + 1, 3, dtype=np.int32), nbr
 
 
+def insert_tip(first, nbr, n: int, tip: int, node1: int, node2: int):
+    """(first, nbr) with `tip` attached in the middle of branch (node1, node2) the way PhyloTree::computeParsimonyTree rewires
+    neighbors[] (phylotree.cpp:1243-1320): the new inner node -- number n + 1 + old n_inner, its list appended -- takes node1's
+    place in node2's list and node2's place in node1's list, in place, and lists [tip, node2, node1] (node2 = target_node, the end
+    away from the root leaf; node1 = target_dad)."""
+    first = [int(x) for x in first]
+    nbr = [int(x) for x in nbr]
+    v = n + len(first)
+    for at, what in ((node2, node1), (node1, node2)):
+        if at > n:
+            i = at - n - 1
+            k = nbr.index(what, first[i], first[i + 1])
+            nbr[k] = v
+    nbr += [int(tip), int(node2), int(node1)]
+    first.append(len(nbr))
+    return np.array(first, dtype=np.int32), np.array(nbr, dtype=np.int32)
+
+
+def drop_tips(tree, n: int, tips):
+    """(first, nbr) of `tree` -- a record tree (back array) or a (first, nbr) pair -- with the leaves `tips` removed and every node
+    left with two neighbours suppressed: the backbone of a reinsertion (FitchEngine.place_taxa).  Surviving inner nodes keep their
+    relative order and are renumbered n + 1 ..; a neighbour that went away is replaced in place by what lay behind it."""
+    if isinstance(tree, (tuple, list)):
+        first, nbr = tree
+    else:
+        first, nbr = back_to_lists(tree, n)
+    first = [int(x) for x in first]
+    adj = {n + 1 + i: [int(u) for u in nbr[first[i]:first[i + 1]]] for i in range(len(first) - 1)}
+    for t in tips:
+        t = int(t)
+        v = next(v for v, l in adj.items() if t in l)
+        adj[v].remove(t)
+        if len(adj[v]) == 2:                    # (its two neighbours keep their degree: nothing else to suppress)
+            a, b = adj.pop(v)
+            for x, y in ((a, b), (b, a)):
+                if x > n:
+                    adj[x][adj[x].index(v)] = y
+    keep = sorted(adj)
+    assert len(keep) >= 1 and all(len(adj[v]) >= 3 for v in keep), "fewer than three tips left"
+    number = {v: n + 1 + i for i, v in enumerate(keep)}
+    out_first, out_nbr = [0], []
+    for v in keep:
+        out_nbr += [u if u <= n else number[u] for u in adj[v]]
+        out_first.append(len(out_nbr))
+    return np.array(out_first, dtype=np.int32), np.array(out_nbr, dtype=np.int32)
+
+
 def lists_to_newick(first, nbr, names: list[str], support=None) -> str:
     """Newick string of a tree given as neighbour lists (tips 1 .. n, inner node i = node n + 1 + i), written from tip 1 with the
     neighbours in list order.  support[i] (optional, per inner node): written as the label of inner node i where it is >= 0 --
