@@ -32,16 +32,6 @@ static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
 const std::string &last_error() { return g_err; }
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
-                std::to_string(__LINE__) + ")");                                                  \
-      return MPF_E_HIP;                                                                           \
-    }                                                                                             \
-  } while (0)
-
 Engine::~Engine()
 {
   if (std::getenv("MPF_VIEWS_PROFILE"))

@@ -26,6 +26,7 @@
 #include "../../include/mpfitch.h"
 #include "../host/rng.hpp"
 #include "../host/ufb_books.hpp"
+#include "../host/list_tree.hpp"
 #include "../host/split_sets.hpp"
 #include "../host/refresh_plan.hpp"
 #include "../host/many_shape.hpp"
@@ -38,6 +39,17 @@ namespace mpf {
 
 void set_error(const std::string &msg);
 const std::string &last_error();
+
+// a failed HIP call ends the calling function with MPF_E_HIP and says where
+#define HIPCHK(expr)                                                                              \
+  do {                                                                                            \
+    hipError_t e__ = (expr);                                                                      \
+    if (e__ != hipSuccess) {                                                                      \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
+                std::to_string(__LINE__) + ")");                                                  \
+      return MPF_E_HIP;                                                                           \
+    }                                                                                             \
+  } while (0)
 
 template <typename T>
 struct DevBuf {
@@ -591,7 +603,7 @@ class Engine {
   // list carries the result; default 64), read-only options split_overflow (length of the last call's overflow list),
   // split_launches and, under "timing", split_keys_ns / split_count_ns / split_bits_ns (HIP-event time of k_split_keys, of
   // insert + count + compact + gather, of k_split_bits)
-  struct SplitRun { splitsets::SplitTable table; splitsets::TreeClusters target; std::vector<int64_t> target_support; } split_run_;
+  struct SplitRun { splitsets::SplitTable table; splitsets::TreeClusters target; listtree::Shape target_shape; std::vector<int64_t> target_support; } split_run_;
   int split_run(const splitsets::TreeSet &set, const int32_t *weights, const splitsets::TreeRef *target, bool want_sets, double threshold,
                 SplitRun &r);
   // what the front half of a call leaves (split_pass): T trees, M cluster slots, a table of tsize slots of which D are used, n_ovf
@@ -629,16 +641,11 @@ class Engine {
   // multifurcating trees: the rooted shape of the tree handed over and the items of its view launch; option "poly_tile" (0 = from
   // the row length, 4 | 8 | 16 | 32 words per workgroup), read-only options poly_launches / poly_views (directed views written) and,
   // under "timing", poly_view_ns / poly_branch_ns (HIP-event time of the view launch / of the branch launch)
-  struct PolyTree {
-    std::vector<int32_t> tip_nb, parent, order, lev_off;
-    std::vector<uint32_t> up_slot, inputs;      // up_slot[v]: the view of v towards its parent (a tip: its own vector)
-    std::vector<PolyItem> items;
-    std::vector<PolyOut> outs;
-    int n_rows = 0;                              // step-mask rows (Fitch): one per up view + the root edge
-  } poly_tree_;
-  // absent_tips (taxon insertion only): tips may be missing from the lists; parent / tip_nb of such a tip stay -1 / 0
-  int polytomy_check(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, PolyTree &t, bool absent_tips = false) const;
-  int polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, bool all_views, PolyTree &t, bool absent_tips = false);
+  // (check, walk and plan: host/list_tree.hpp)
+  struct PolyTree { listtree::Shape shape; listtree::ViewPlan plan; } poly_tree_;
+  // checked: t.shape is that of these lists already (taxon insertion has its own rules on top of the check); else the lists are
+  // checked here, every tip required
+  int polytomy_views(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, bool all_views, PolyTree &t, bool checked = false);
   void polytomy_view_time();
   int poly_tile_ = 0;
   bool poly_view_timed_ = false;

@@ -11,6 +11,8 @@
 #include <atomic>
 #include <type_traits>
 
+#include "../host/list_tree.hpp"
+
 namespace mpf {
 
 // recompute dst = fitch(a, b); cnt[dst] += #sites with empty intersection   (K1, newview)
@@ -234,7 +236,7 @@ hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t
 // Parsimony branch lengths: every branch of the tree in one launch (cids of the two directional vectors of the branch; a tip's own
 // vector at a pendant branch).  out[i] (zeroed by the caller) = number of sites whose two state sets have nothing in common
 // (k_branch_subst; vw / word_major as launch_nni_eval)
-struct BranchDesc { uint32_t a, b; };
+// (BranchDesc: host/list_tree.hpp)
 hipError_t launch_branch_subst(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                                uint32_t *out, int vw, bool word_major);
 // ... on the weighted engine (k_snk_branch_eval): out[i] = the FULL weighted length of the tree rooted at branch i, a = the side
@@ -285,8 +287,7 @@ hipError_t launch_pattern_sum(hipStream_t st, const Geometry &g, const uint32_t 
 // of them), stored at slot dst (0xFFFFFFFF: not stored) and, Fitch engine, its step mask ~OR_rows(AND) at masks[mask_row][Wp]
 // (0xFFFFFFFF: none).  Items are laid out by level, lev_off[0 .. n_lev]; one launch, a workgroup barrier between levels.
 // tile: words (elements) of a row per workgroup, 4 | 8 | 16 | 32; 0 = chosen from the row length (poly_tile)
-struct PolyItem { uint32_t in_begin, n_in, out_begin, n_out; };
-struct PolyOut { uint32_t dst, excl, mask_row, pad; };
+// PolyItem and PolyOut are defined in host/list_tree.hpp, where the plan is made (listtree::plan_views)
 int poly_tile(int W, int want);
 hipError_t launch_poly_views(hipStream_t st, const Geometry &g, uint32_t *vec, const PolyItem *items, const PolyOut *outs,
                              const uint32_t *inputs, const int32_t *lev_off, int n_lev, uint32_t *masks, int tile);

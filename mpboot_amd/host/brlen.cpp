@@ -12,16 +12,6 @@
 
 namespace mpf {
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
-                std::to_string(__LINE__) + ")");                                                  \
-      return MPF_E_HIP;                                                                           \
-    }                                                                                             \
-  } while (0)
-
 // fixNegativeBranch(force, node = root, dad = NULL): FOR_NEIGHBOR_IT(node, dad, it) { the branch node--(*it)->node; recurse }, i.e. a
 // pre-order walk from the root leaf, neighbours in slot order, every branch met once from its root side -- the order of evalNNIs
 // (nni_full_order) with the pendant branches included.  node1 = the end nearer the root leaf

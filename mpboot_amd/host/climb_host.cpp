@@ -17,16 +17,6 @@
 
 namespace mpf {
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
-                std::to_string(__LINE__) + ")");                                                  \
-      return MPF_E_HIP;                                                                           \
-    }                                                                                             \
-  } while (0)
-
 // k_climb's workgroups wait for each other, so all of them must be resident at once.  Engines on several host threads of one
 // process share a device: launches are admitted only while their workgroups fit the chip together (a launch that still fails
 // to become resident -- other processes -- gives up inside the kernel after 30 ms and the caller falls back to host batches).

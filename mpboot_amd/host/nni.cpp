@@ -14,16 +14,6 @@
 
 namespace mpf {
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
-                std::to_string(__LINE__) + ")");                                                  \
-      return MPF_E_HIP;                                                                           \
-    }                                                                                             \
-  } while (0)
-
 int Engine::nni_check(int root_taxon) const
 {
   // the weighted climb (ParsTree scoring, no rollback: iqtree.cpp:2258) is served under the option "nni_weighted" only; an attached

@@ -2,8 +2,9 @@
 //
 // Reference: PhyloTree::addTaxonMPFast (phylotree.cpp:1322-1378) under PhyloTree::computeParsimonyTree (phylotree.cpp:1243-1320, the
 // start tree of -starttree PARS) and IQTree::reinsertLeavesByParsimony (iqtree.cpp:981-1016).  The backbone is a binary tree over a
-// subset of the tips, handed over as the polytomy calls take their lists (host/place_tree.hpp holds the check, the walk, the
-// first-minimum rule and the growth of the lists, device-free).  All its directed views come from ONE k_poly_views launch
+// subset of the tips, handed over as the polytomy calls take their lists (device-free: host/list_tree.hpp holds the check, the walk,
+// the view plan and the sides of a branch, host/place_tree.hpp the rule of insertion alone, the first-minimum rule and the growth of
+// the lists).  All its directed views come from ONE k_poly_views launch
 // (Engine::polytomy_views, all views); k_place_costs (place.hip) then joins the two views of every branch on the way into LDS and
 // counts, per query, the sites that share no state with the query tip's own vector.
 //
@@ -18,16 +19,6 @@
 
 namespace mpf {
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
-                std::to_string(__LINE__) + ")");                                                  \
-      return MPF_E_HIP;                                                                           \
-    }                                                                                             \
-  } while (0)
-
 int Engine::place_costs(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, int n_query, const int32_t *query_taxa,
                         std::vector<NniBranch> &br, std::vector<uint32_t> *delta, std::vector<PlaceBest> *best, uint32_t *tree_length)
 {
@@ -36,7 +27,8 @@ int Engine::place_costs(int n_inner, const int32_t *first, const int32_t *nbr, i
     set_error("taxon insertion: not served on the weighted (-cost) engine (its cost is a min-plus product rooted at the branch)");
     return MPF_E_UNSUPPORTED;
   }
-  placetree::Walk w;
+  PolyTree &t = poly_tree_;
+  listtree::Shape &w = t.shape;                        // checked once, here: polytomy_views takes it as it is
   std::string err;
   const int verdict = placetree::check(n, n_inner, first, nbr, root_taxon, w, err);
   if (verdict) { set_error(err); return verdict == placetree::PT_UNSUPPORTED ? MPF_E_UNSUPPORTED : MPF_E_INVALID; }
@@ -44,34 +36,22 @@ int Engine::place_costs(int n_inner, const int32_t *first, const int32_t *nbr, i
   {
     std::vector<char> seen((size_t)n + 1, 0);
     for (int q = 0; q < n_query; q++) {
-      const int t = query_taxa[q];
-      if (t < 1 || t > n) { set_error("taxon insertion: query taxon out of range"); return MPF_E_INVALID; }
-      if (w.tip_nb[(size_t)t]) { set_error("taxon insertion: query taxon " + std::to_string(t) + " is in the backbone"); return MPF_E_INVALID; }
-      if (seen[(size_t)t]) { set_error("taxon insertion: query taxon " + std::to_string(t) + " is listed twice"); return MPF_E_INVALID; }
-      seen[(size_t)t] = 1;
+      const int u = query_taxa[q];
+      if (u < 1 || u > n) { set_error("taxon insertion: query taxon out of range"); return MPF_E_INVALID; }
+      if (w.tip_nb[(size_t)u]) { set_error("taxon insertion: query taxon " + std::to_string(u) + " is in the backbone"); return MPF_E_INVALID; }
+      if (seen[(size_t)u]) { set_error("taxon insertion: query taxon " + std::to_string(u) + " is listed twice"); return MPF_E_INVALID; }
+      seen[(size_t)u] = 1;
     }
   }
-  PolyTree &t = poly_tree_;
   int rc = polytomy_views(n_inner, first, nbr, root_taxon, true, t, true);
   if (rc) return rc;
-  br.clear();
-  for (size_t i = 0; i < w.node2.size(); i++) br.push_back(NniBranch{w.node1[i], w.node2[i]});
-  const size_t nb = br.size(), Q = (delta || best) ? (size_t)n_query : 0, rows = (size_t)t.n_rows;      // (nothing wanted: the checks, the branches, the length)
+  listtree::branches(t.shape, br);
+  const size_t nb = br.size(), Q = (delta || best) ? (size_t)n_query : 0, rows = (size_t)t.plan.n_rows;      // (nothing wanted: the checks, the branches, the length)
   if (delta) delta->assign(Q * nb, 0u);
   if (best) best->assign(Q, PlaceBest{0u, 0u});
-  // the two sides of every branch, as polytomy_branch_substitutions finds them
-  std::vector<uint32_t> down((size_t)n + (size_t)n_inner + 1, 0xFFFFFFFFu);
-  for (int i = 0; i < n_inner; i++)
-    for (int k = first[i]; k < first[i + 1]; k++)
-      if (t.parent[(size_t)nbr[k]] == n + 1 + i) down[(size_t)nbr[k]] = (uint32_t)(n + k);
   HIPCHK(h_br_desc_.reserve(nb));
   HIPCHK(d_br_desc_.reserve(nb));
-  for (size_t i = 0; i < nb; i++) {
-    const int v1 = br[i].node1, v2 = br[i].node2;
-    const uint32_t rest = v1 <= n ? (uint32_t)(v1 - 1) : down[(size_t)v2], sub = t.up_slot[(size_t)v2];
-    if (rest == 0xFFFFFFFFu || sub == 0xFFFFFFFFu) { set_error("taxon insertion: inconsistent walk"); return MPF_E_STATE; }
-    h_br_desc_.p[i] = BranchDesc{sub, rest};
-  }
+  if (!listtree::branch_sides(n, n_inner, first, nbr, t.shape, t.plan, h_br_desc_.p)) { set_error("taxon insertion: inconsistent walk"); return MPF_E_STATE; }
   HIPCHK(hipMemcpyAsync(d_br_desc_.p, h_br_desc_.p, nb * sizeof(BranchDesc), hipMemcpyHostToDevice, st_));
   HIPCHK(d_poly_cnt_.reserve(rows));
   HIPCHK(h_poly_cnt_.reserve(rows));

@@ -103,7 +103,9 @@ int main(int argc, char **argv)
   if (verdict) { std::printf("%s: %s\n", verdict == PT_UNSUPPORTED ? "unsupported" : "invalid", err.c_str()); return 0; }
   if (cmd == "check") {
     std::printf("ok\nbranches");
-    for (size_t i = 0; i < w.node2.size(); i++) std::printf(" %d %d", w.node1[i], w.node2[i]);
+    std::vector<mpf::listtree::Branch> br;
+    mpf::listtree::branches(w, br);
+    for (const auto &b : br) std::printf(" %d %d", b.node1, b.node2);
     std::printf("\n");
     return 0;
   }
@@ -115,7 +117,7 @@ int main(int argc, char **argv)
   const auto t0 = std::chrono::steady_clock::now();
   host_costs(in.n, in.S, in.W, in.tips.data(), in.n_inner, in.first.data(), in.nbr.data(), w, in.Q, in.query.data(), delta, &len);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  const size_t nb = w.node2.size();
+  const size_t nb = w.order.size() - 1;
   std::printf("length %u\n", len);
   for (int q = 0; q < in.Q; q++) {
     std::printf("row %d", q);

@@ -6,7 +6,8 @@
 // my_random_shuffle order (tools.h:2107-2113), and the way it rewires neighbors[] decides the next step's walk.
 //
 // A backbone comes as the CSR neighbour lists of the polytomy calls (tips 1 .. n, inner node i = node n + 1 + i with neighbours
-// nbr[first[i] .. first[i + 1]) in the host's neighbors[] order) with one relaxation: tips may be absent.
+// nbr[first[i] .. first[i + 1]) in the host's neighbors[] order) with one relaxation: tips may be absent.  Check and walk are those of
+// list_tree.hpp.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -14,79 +15,23 @@
 #include <utility>
 #include <vector>
 
+#include "list_tree.hpp"
+
 namespace mpf {
 namespace placetree {
 
 enum { PT_OK = 0, PT_INVALID = 1, PT_UNSUPPORTED = 2 };
 
-struct Walk {
-  int m = 0;                                   // tips that occur
-  std::vector<int32_t> tip_nb, parent, order;  // tip_nb[u]: the inner neighbour of tip u (0: absent); parent / pre-order from the root leaf
-  std::vector<int32_t> node1, node2;           // the 2 m - 3 branches in walk order, node1 the root side
-};
+using Walk = listtree::Shape;                   // the rooted shape; its 2 m - 3 branches in walk order: listtree::branches
 
-// The relaxed check of the hand-over.  PT_INVALID: not a tree over a subset of the tips with root_taxon among them;
-// PT_UNSUPPORTED: a tree, but some inner node has a degree other than 3 (the k-ary Fitch rule depends on the root, and an
-// insertion cost on such a tree is not what any reference function computes)
+// The hand-over check (listtree::check, tips may be absent) and the rule of insertion alone.  PT_INVALID: not a tree over a subset
+// of the tips with root_taxon among them (three or more occur: every inner node of a tree that passes has three or more
+// neighbours); PT_UNSUPPORTED: a tree, but some inner node has a degree other than 3 (the k-ary Fitch rule depends on the root, and
+// an insertion cost on such a tree is not what any reference function computes)
 inline int check(int n, int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, Walk &w, std::string &err)
 {
-  auto bad = [&](const char *what) { err = std::string("backbone tree: ") + what; return (int)PT_INVALID; };
-  if (!first || !nbr) return bad("null neighbour lists");
-  if (n < 3) return bad("fewer than three taxa");
-  if (n_inner < 1 || n_inner > n - 2) return bad("n_inner must be in 1 .. n_taxa - 2");
-  if (root_taxon < 1 || root_taxon > n) return bad("root_taxon must be in 1 .. n_taxa");
-  if (first[0] != 0) return bad("first[0] must be 0");
-  const int N = n + n_inner;
-  for (int i = 0; i < n_inner; i++)
-    if (first[i + 1] - first[i] < 3) return bad("an inner node has fewer than three neighbours");
-  if ((int64_t)first[n_inner] > 3 * (int64_t)(n - 2)) return bad("more neighbour entries than a tree of n_taxa leaves can have");
-  w.tip_nb.assign((size_t)n + 1, 0);
-  std::vector<std::pair<int32_t, int32_t>> arcs;
-  for (int i = 0; i < n_inner; i++)
-    for (int k = first[i]; k < first[i + 1]; k++) {
-      const int u = nbr[k], v = n + 1 + i;
-      if (u < 1 || u > N) return bad("neighbour number out of range");
-      if (u == v) return bad("a node is its own neighbour");
-      if (u <= n) {
-        if (w.tip_nb[(size_t)u]) return bad("a tip occurs more than once");
-        w.tip_nb[(size_t)u] = v;
-      } else arcs.emplace_back(v, u);
-    }
-  w.m = 0;
-  for (int u = 1; u <= n; u++) w.m += w.tip_nb[(size_t)u] != 0;
-  if (w.m < 3) return bad("fewer than three tips occur");
-  if (!w.tip_nb[(size_t)root_taxon]) return bad("root_taxon does not occur");
-  std::sort(arcs.begin(), arcs.end());
-  for (size_t i = 0; i < arcs.size(); i++) {
-    if (i && arcs[i] == arcs[i - 1]) return bad("a neighbour is listed twice");
-    if (!std::binary_search(arcs.begin(), arcs.end(), std::make_pair(arcs[i].second, arcs[i].first))) return bad("adjacency is not symmetric");
-  }
-  if ((int64_t)w.m + (int64_t)arcs.size() / 2 != (int64_t)w.m + n_inner - 1) return bad("not tips + n_inner - 1 edges");
-  w.parent.assign((size_t)N + 1, -1);
-  w.order.clear();
-  w.node1.clear();
-  w.node2.clear();
-  w.parent[(size_t)root_taxon] = 0;
-  w.order.push_back(root_taxon);
-  std::vector<int32_t> st{w.tip_nb[(size_t)root_taxon]};
-  w.parent[(size_t)st[0]] = root_taxon;
-  while (!st.empty()) {
-    const int v = st.back();
-    st.pop_back();
-    w.order.push_back(v);
-    w.node1.push_back(w.parent[(size_t)v]);
-    w.node2.push_back(v);
-    if (v <= n) continue;
-    const int i = v - n - 1;
-    for (int k = first[i + 1] - 1; k >= first[i]; k--) {
-      const int u = nbr[k];
-      if (u == w.parent[(size_t)v]) continue;
-      if (w.parent[(size_t)u] >= 0) return bad("the neighbour lists hold a cycle");
-      w.parent[(size_t)u] = v;
-      st.push_back(u);
-    }
-  }
-  if ((int)w.order.size() != w.m + n_inner) return bad("the tree is not connected");
+  std::string why;
+  if (!listtree::check(n, n_inner, first, nbr, root_taxon, true, w, &why)) { err = "backbone tree: " + why; return PT_INVALID; }
   for (int i = 0; i < n_inner; i++)
     if (first[i + 1] - first[i] != 3) {
       err = "backbone tree: an inner node of degree " + std::to_string(first[i + 1] - first[i]) + " (insertion costs are defined on binary trees)";
@@ -195,11 +140,11 @@ inline void host_costs(int n, int S, int W, const uint32_t *tips, int n_inner, c
     join(&down[(size_t)v * V], &up[(size_t)c[0] * V], &down[(size_t)c[1] * V], false);
   }
   if (tree_length) *tree_length = len;
-  const size_t nb = w.node2.size();
+  const size_t nb = w.order.size() - 1;
   delta.assign((size_t)n_query * nb, 0u);
   std::vector<uint32_t> x(V);
   for (size_t b = 0; b < nb; b++) {
-    const int v = w.node2[b];
+    const int v = w.order[b + 1];                // branch b ends at the b-th node behind the root leaf
     join(&down[(size_t)v * V], &up[(size_t)v * V], x.data(), false);
     for (int q = 0; q < n_query; q++) {
       const uint32_t *t = tips + (size_t)(queries[q] - 1) * V;

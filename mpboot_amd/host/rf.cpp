@@ -18,16 +18,6 @@
 
 namespace mpf {
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
-                std::to_string(__LINE__) + ")");                                                  \
-      return MPF_E_HIP;                                                                           \
-    }                                                                                             \
-  } while (0)
-
 namespace {
 int bad(const std::string &what) { set_error("rf distances: " + what); return MPF_E_INVALID; }
 }  // namespace

@@ -6,7 +6,7 @@
 // as whole sets; the hash of SetIndex only picks a bucket.
 //
 //   walk_clusters     the walk of k_split_keys restated: DFS from tip 1, every inner branch an interval [lo, hi) of DFS positions
-//   lists_ok          the hand-over conditions of the mpf_polytomy_* calls on a tree given as CSR neighbour lists
+//   lists_ok          the hand-over conditions on a tree given as CSR neighbour lists (listtree::check of list_tree.hpp: root leaf 1, every tip)
 //   walk_clusters_lists  the walk of k_split_keys_lists restated: the same intervals for a tree of any inner degree >= 3
 //   TreeSet, TreeRef  a set that mixes record-format and list-form trees (the records first, then the lists), and one tree of it
 //   SetIndex          exact set -> index map (the overflow list of k_split_count is resolved through it; so is count_splits)
@@ -29,6 +29,8 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
+
+#include "list_tree.hpp"
 
 namespace mpf {
 namespace splitsets {
@@ -106,73 +108,15 @@ inline bool walk_clusters(const int32_t *back, int n, TreeClusters &c)
 // but the first leaves one closing entry
 inline size_t list_walk_stack(int n, int n_inner) { return (size_t)n + 2 * (size_t)n_inner + 2; }
 
-// (Engine::polytomy_check of host/polytomy.cpp checks the same conditions for the mpf_polytomy_* calls, with messages of its own and
-// the rooted shape as a by-product; it needs the engine, this header must not.  Whoever changes the hand-over rule changes both.)
-// The conditions of the hand-over: 1 <= n_inner <= n - 2, first[0] = 0, every inner degree >= 3, entries in range, no loop on a
-// node, every tip exactly once, symmetric adjacency without doubles, n + n_inner - 1 edges, one connected tree.  why (may be
-// null): what is wrong
+// The conditions of the hand-over (listtree::check states them) for a tree of a set: every tip occurs, the root leaf is tip 1.
+// why (may be null): what is wrong
 inline bool lists_ok(int n, int n_inner, const int32_t *first, const int32_t *nbr, std::string *why = nullptr)
 {
-  auto no = [&](const char *w) { if (why) *why = w; return false; };
-  if (!first || !nbr) return no("null neighbour lists");
-  if (n < 3 || n_inner < 1 || n_inner > n - 2) return no("n_inner must be in 1 .. n_taxa - 2");
-  if (first[0] != 0) return no("first[0] must be 0");
-  const int N = n + n_inner;
-  for (int i = 0; i < n_inner; i++)
-    if ((int64_t)first[i + 1] - (int64_t)first[i] < 3) return no("an inner node has fewer than three neighbours");
-  const int64_t E = first[n_inner];
-  if (E > 3 * (int64_t)(n - 2)) return no("more neighbour entries than a tree of n_taxa leaves can have");
-  std::vector<int32_t> tip_nb((size_t)n + 1, 0);
-  std::vector<std::pair<int32_t, int32_t>> arcs;         // inner -> inner
-  for (int i = 0; i < n_inner; i++)
-    for (int k = first[i]; k < first[i + 1]; k++) {
-      const int u = nbr[k], v = n + 1 + i;
-      if (u < 1 || u > N) return no("neighbour number out of range");
-      if (u == v) return no("a node is its own neighbour");
-      if (u <= n) {
-        if (tip_nb[(size_t)u]) return no("a tip occurs more than once");
-        tip_nb[(size_t)u] = v;
-      } else arcs.emplace_back(v, u);
-    }
-  for (int u = 1; u <= n; u++)
-    if (!tip_nb[(size_t)u]) return no("a tip does not occur");
-  std::sort(arcs.begin(), arcs.end());
-  for (size_t i = 0; i < arcs.size(); i++) {
-    if (i && arcs[i] == arcs[i - 1]) return no("a neighbour is listed twice");
-    if (!std::binary_search(arcs.begin(), arcs.end(), std::make_pair(arcs[i].second, arcs[i].first))) return no("adjacency is not symmetric");
-  }
-  if ((int64_t)n + (int64_t)arcs.size() / 2 != (int64_t)N - 1) return no("not n_taxa + n_inner - 1 edges");
-  // with that many edges: one tree iff every node is reached from tip 1 (a cycle leaves a part unreached)
-  std::vector<char> seen((size_t)N + 1, 0);
-  std::vector<int32_t> st{tip_nb[1]};
-  seen[1] = seen[(size_t)tip_nb[1]] = 1;
-  int reached = 2;
-  while (!st.empty()) {
-    const int v = st.back();
-    st.pop_back();
-    for (int k = first[v - n - 1]; k < first[v - n]; k++) {
-      const int u = nbr[k];
-      if (seen[(size_t)u]) continue;
-      seen[(size_t)u] = 1;
-      reached++;
-      if (u > n) st.push_back(u);
-    }
-  }
-  if (reached != N) return no("the neighbour lists hold a cycle or the tree is not connected");
-  return true;
+  listtree::Shape shape;
+  return listtree::check(n, n_inner, first, nbr, 1, false, shape, why);
 }
 
-// the inner node next to tip 1 (0: tip 1 is in no list)
-inline int list_root(int n, int n_inner, const int32_t *first, const int32_t *nbr)
-{
-  const int E = first[n_inner];
-  for (int i = 0; i < n_inner; i++) {
-    if (first[i] < 0 || first[i + 1] > E) return 0;
-    for (int k = first[i]; k < first[i + 1]; k++)
-      if (nbr[k] == 1) return n + 1 + i;
-  }
-  return 0;
-}
+using listtree::list_root;
 
 // The walk of k_split_keys_lists, step for step: an explicit stack of (node, dad) entries, children in list order, a negative
 // entry closes cluster -(x + 1).  The inner node next to tip 1 is entered first and gets no cluster, so a tree with m inner nodes

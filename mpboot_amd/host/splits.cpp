@@ -18,16 +18,6 @@
 
 namespace mpf {
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e__) + " (" + __FILE__ + ":" +      \
-                std::to_string(__LINE__) + ")");                                                  \
-      return MPF_E_HIP;                                                                           \
-    }                                                                                             \
-  } while (0)
-
 namespace {
 int bad(const std::string &what) { set_error("split summary: " + what); return MPF_E_INVALID; }
 }  // namespace
@@ -232,7 +222,7 @@ int Engine::split_run(const splitsets::TreeSet &set, const int32_t *weights, con
   if (stop >= 0) return bad("list tree " + std::to_string(stop) + ": n_inner or first[] are not those of a tree on n_taxa taxa");
   if (target) {
     if (target->is_list()) {
-      if (!splitsets::lists_ok(n, target->n_inner, target->first, target->nbr, &why)) return bad("target tree: " + why);
+      if (!listtree::check(n, target->n_inner, target->first, target->nbr, 1, false, r.target_shape, &why)) return bad("target tree: " + why);
       if (!splitsets::walk_clusters_lists(n, target->n_inner, target->first, target->nbr, r.target)) return bad("target tree: the lists do not form one tree");
     } else {
       if (!splitsets::links_ok(target->back, n)) return bad("target tree: inconsistent back links (a complete tree on n_taxa taxa is needed)");
@@ -330,18 +320,13 @@ int Engine::split_support(const splitsets::TreeSet &set, const int32_t *weights,
   for (size_t ci = 0; ci < r.target.node.size(); ci++) cluster_of[(size_t)r.target.node[ci]] = (int32_t)ci;
   br.clear();
   struct F { int node, dad; };
-  std::vector<F> st{F{1, 0}};
-  if (target.is_list()) st[0] = F{splitsets::list_root(n_, target.n_inner, target.first, target.nbr), 1};
-  while (!st.empty()) {                            // Engine::branch_order on the target's records, or its like on the lists
+  std::vector<F> st;
+  if (target.is_list()) listtree::branches(r.target_shape, br);       // the walk from tip 1 that split_run's check of the target left
+  else st.push_back(F{1, 0});
+  while (!st.empty()) {                            // Engine::branch_order on the target's records
     const F f = st.back();
     st.pop_back();
     if (f.dad) br.push_back(NniBranch{f.dad, f.node});
-    if (target.is_list()) {
-      if (f.node <= n_) continue;
-      for (int k = target.first[f.node - n_] - 1; k >= target.first[f.node - n_ - 1]; k--)
-        if (target.nbr[k] != f.dad) st.push_back(F{target.nbr[k], f.node});
-      continue;
-    }
     for (int s = (f.node > n_ ? 2 : 0); s >= 0; s--) {
       const int nb = target.back[3 * f.node + s] / 3;
       if (nb != f.dad) st.push_back(F{nb, f.node});

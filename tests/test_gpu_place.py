@@ -302,6 +302,40 @@ def test_refusals():
     _check(eng, wit, *plw.GOOD, [6, 7, 8, 9], 5)                                             # ... and served afterwards
 
 
+def test_one_set_of_lists_three_consumers():
+    """the same lists handed to insertion, to the polytomy calls and to a tree set, on one engine that holds a tree: each applies the
+    one hand-over check in its own mode"""
+    import polytomy_witness as pw
+    import split_lists_witness as lw
+    from mpboot_amd import engine, trees
+    n, P = 9, 65
+    codes, weights = _alignment(n, P, "dna", 3)
+    eng = _engine(codes, weights, "dna")
+    rng = np.random.default_rng(3)
+    back = trees.random_topology(n, rng)
+    score = eng.score_tree(back)
+
+    def code_of(call):
+        with pytest.raises(engine.MpfError) as ei:
+            call()
+        return ei.value.code
+
+    # a binary backbone with two tips absent: legal for insertion, no tree for the calls that need every tip
+    first, nbr = plw.backbone(n, [1, 2, 3, 4, 5, 6, 7], rng)
+    _check(eng, plw.PlaceWitness(codes, weights, 0), first, nbr, [8, 9], 1)
+    assert code_of(lambda: eng.polytomy_parsimony(first, nbr)) == -2
+    assert code_of(lambda: eng.split_counts([back], lists=[(first, nbr)])) == -2
+    assert (eng.get_tree() == back).all() and eng.score_tree() == score
+    # a backbone with a node of degree 4: a tree for the polytomy calls, unsupported for insertion
+    first, nbr = lw.collapse(back, n, 1, rng)
+    assert max(np.diff(first)) == 4
+    assert code_of(lambda: eng.place_taxa(first, nbr, [9])) == -6
+    a, b, subst = eng.polytomy_branch_substitutions(first, nbr)
+    br, want = pw.PolyWitness(codes, weights, 0).substitutions(first, nbr)
+    assert list(zip(a.tolist(), b.tolist())) == br and (subst.astype(np.int64) == want).all()
+    assert (eng.get_tree() == back).all() and eng.score_tree() == score
+
+
 # ---------------------------------------------------------------- computeParsimonyTree
 @pytest.mark.parametrize("alphabet", ALPHABETS)
 def test_iq_parsimony_tree(alphabet):

@@ -17,6 +17,14 @@ every one that opens the GPU under `timeout`, one GPU process at a time; a step 
   host   3. mpboot_amd/host/place_host_main.cpp built with -O2 and without a sanitizer, fed the engine's own tip vectors and the
             same backbone: its host_costs on one core, median of 3.
 The costs of 1, 2 and 3 must be equal, and 1 must be faster than 2; the run fails otherwise.
+
+    python tools/place_timing.py --compare-lib OTHER/libmpfitch.so --out profiles/place/timing_list_tree.json
+
+Two builds of the library next to each other -- this tree's and another commit's -- on the host-bound calls: the one-query call
+of step 1 and mpf_iq_parsimony_tree (n - 3 such steps with the host's check, plan and list growth between them), both shapes.  Each
+build runs in child processes of its own (MPF_LIB_PATH), `--rounds` of them per shape, the two builds taking turns; a round's
+figure is its median, a build's figure the median of its rounds and its spread their maximum minus their minimum.  Accepted: the same
+costs and the same tree from both, and this build's figure not above the other's by more than the larger of the two spreads.
 """
 import argparse
 import json
@@ -128,6 +136,65 @@ def step_gpu(shape, reps, workdir):
     print(json.dumps(out))
 
 
+def step_ab(shape, reps):
+    """one round of one build: wall clock of the one-query call and of mpf_iq_parsimony_tree, and what they returned"""
+    import hashlib
+
+    from mpboot_amd import engine, synth, trees
+    letters, _ = synth.workload(shape)
+    codes = synth.letters_to_codes(letters, "DNA")
+    n = codes.shape[0]
+    eng = engine.FitchEngine(codes)
+    first, nbr = trees.drop_tips(trees.random_topology(n, np.random.default_rng(1)), n, [n])
+    order = np.arange(1, n + 1)
+    cost = eng.insertion_costs(first, nbr, [n])[2]
+    tree = eng.iq_parsimony_tree(order=order)
+    one, grow = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        eng.insertion_costs(first, nbr, [n])
+        one.append((time.perf_counter() - t0) * 1e3)
+    for _ in range(3):
+        t0 = time.perf_counter()
+        eng.iq_parsimony_tree(order=order)
+        grow.append((time.perf_counter() - t0) * 1e3)
+    h = hashlib.sha256()
+    for a in (cost, tree[0], tree[1], tree[2]):
+        h.update(np.ascontiguousarray(a).tobytes())
+    print(json.dumps({"taxa": n, "library": engine.LIB_PATH, "one_query_ms": statistics.median(one), "iq_parsimony_tree_ms": statistics.median(grow),
+                      "results_sha256": h.hexdigest()}))
+
+
+def compare(other_lib, shapes, reps, rounds):
+    res = {"reps": reps, "rounds": rounds, "shapes": {}}
+    ok = True
+    for name in shapes:
+        got = {"other": [], "this": []}
+        for _ in range(rounds):
+            for side in ("other", "this"):
+                env = dict(os.environ)
+                if side == "other":
+                    env["MPF_LIB_PATH"] = os.path.abspath(other_lib)
+                else:
+                    env.pop("MPF_LIB_PATH", None)
+                got[side].append(child(["--step", "ab", "--shape", name, "--reps", str(reps)], limit=300, env=env))
+        one = {"taxa": got["this"][0]["taxa"]}
+        one["same_results"] = len({r["results_sha256"] for side in got.values() for r in side}) == 1
+        ok = ok and one["same_results"]
+        for what in ("one_query_ms", "iq_parsimony_tree_ms"):
+            fig = {}
+            for side in got:
+                xs = [r[what] for r in got[side]]
+                fig[side] = {"median_ms": statistics.median(xs), "spread_ms": max(xs) - min(xs), "rounds_ms": xs}
+            fig["accepted"] = fig["this"]["median_ms"] <= fig["other"]["median_ms"] + max(fig["this"]["spread_ms"], fig["other"]["spread_ms"])
+            ok = ok and fig["accepted"]
+            one[what] = fig
+        res["shapes"][name] = one
+        print(json.dumps({name: one}), flush=True)
+    res["accepted"] = ok
+    return res
+
+
 def step_host(shape, workdir):
     cxx = shutil.which("g++") or shutil.which("c++")
     exe = os.path.join(workdir, "place_host")
@@ -144,11 +211,11 @@ def step_host(shape, workdir):
     print(json.dumps({"host_costs": spread(ms), "same_costs_as_the_engine": same, "note": "one core, -O2, views and costs"}))
 
 
-def child(args, limit=None):
+def child(args, limit=None, env=None):
     cmd = [sys.executable, os.path.abspath(__file__)] + args
     if limit:
         cmd = ["timeout", "-k", "10", str(limit)] + cmd
-    r = subprocess.run(cmd, capture_output=True, text=True)
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env)
     if r.returncode != 0:
         sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
         raise SystemExit("step %s ended with status %d: stopping here" % (args[1], r.returncode))
@@ -160,13 +227,26 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--shape", default=None, choices=SHAPES, help="one shape only")
-    ap.add_argument("--step", default=None, choices=("gpu", "host"))
+    ap.add_argument("--step", default=None, choices=("gpu", "host", "ab"))
+    ap.add_argument("--compare-lib", default=None, help="another commit's libmpfitch.so: time the host-bound calls of both builds in turn")
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--workdir", default=None)
     a = ap.parse_args()
     if a.step == "gpu":
         step_gpu(a.shape, a.reps, a.workdir)
     elif a.step == "host":
         step_host(a.shape, a.workdir)
+    elif a.step == "ab":
+        step_ab(a.shape, a.reps)
+    elif a.compare_lib:
+        res = compare(a.compare_lib, [a.shape] if a.shape else SHAPES, a.reps, a.rounds)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
+        if not res["accepted"]:
+            raise SystemExit("the two builds differ in their results, or this one is slower than the other by more than the spread")
     else:
         res = {"reps": a.reps, "shapes": {}}
         ok = True
