@@ -578,6 +578,10 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
   RefreshShape s;
   s.nops = 3 * (size_t)(n_ - 2);
   s.maxlev = -1;                                   // (the level count stays on the device)
+  // no k_sched at all: the refresh workgroups find the levels themselves, the descriptor workgroup runs beside them
+  s.self = refresh_self_sched_ && newview_self_supported(g_, (uint32_t)n_, (uint32_t)s.nops);
+  s.fold_inside = s.self && s.nops <= 512;        // (few ops: the refresh kernel's last workgroup folds the counts, as on the host's route)
+  self_active_ = s.self;
   const size_t n_prune = sweep_maxtrav > 0 ? 2 * (size_t)n_ - 2 : 0;
   if (kids_host_.size() != nslots_) kids_host_.assign(nslots_, make_uint2(0u, 0u));
   for (int v = n_ + 1; v <= 2 * n_ - 2; v++) {
@@ -628,8 +632,12 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
   kids_dirty_ = false;
   kids_upload_ = false;
   kids_dev_ready_ = true;
-  HIPCHK(launch_sched(st_, reinterpret_cast<const uint2 *>(h_kstage_.p), (uint32_t)n_, (uint32_t)s.nops, reinterpret_cast<NvOp *>(src + sg.ops_off),
-                      reinterpret_cast<int32_t *>(src + sg.lev_off), reinterpret_cast<int32_t *>(src + sg.nlev_off), sw, reinterpret_cast<uint2 *>(src)));
+  if (s.self)
+    // all that stands in front of the refresh: the topology array, pinned memory to device, one thread per record
+    HIPCHK(launch_kids_copy(st_, reinterpret_cast<const uint2 *>(h_kstage_.p), reinterpret_cast<uint2 *>(src), (uint32_t)n_, (uint32_t)s.nops));
+  else
+    HIPCHK(launch_sched(st_, reinterpret_cast<const uint2 *>(h_kstage_.p), (uint32_t)n_, (uint32_t)s.nops, reinterpret_cast<NvOp *>(src + sg.ops_off),
+                        reinterpret_cast<int32_t *>(src + sg.lev_off), reinterpret_cast<int32_t *>(src + sg.nlev_off), sw, reinterpret_cast<uint2 *>(src)));
   int rc = launch_refresh(src, sg, s);            // (view kernel time = the refresh proper; k_sched reports its own: option sched_ticks)
   if (rc) return rc;
   // what the host still needs is a dependency order for the subtree scores (finish_views): the views looking away from
@@ -641,7 +649,7 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
   if (all.size() != s.nops) { set_error("refresh schedule: the tree is not complete"); return MPF_E_STATE; }
   for (size_t i = all.size(); i >= 3; i -= 3) upd_order_[at++] = all[i - 3];
   for (size_t i = 0; i < all.size(); i += 3) { upd_order_[at++] = all[i + 1]; upd_order_[at++] = all[i + 2]; }
-  rc = commit_refresh(sg, s, true, 2, true);
+  rc = commit_refresh(sg, s, true, 2, true);       // (self-scheduled with the plan cache on: a workgroup of the refresh left the schedule)
   if (n_prune) dsw_sched_gen_ = sched_gen_;       // the sweep descriptors belong to this schedule's topology
   return rc;
 }
@@ -669,7 +677,9 @@ int Engine::launch_refresh(const uint8_t *src, const RefreshStage &sg, const Ref
   const bool zero = s.ride && zero_req_ptr_;      // the outputs of the scan that follows, cleared by the refresh launch
   x.zero_ptr = zeroed_ptr_ = zero ? zero_req_ptr_ : nullptr;
   x.zero_words = (uint32_t)(zeroed_words_ = zero ? zero_req_words_ : 0);
-  if (s.sw && plan_ride_) {
+  // (a self-scheduled refresh makes the descriptors itself: the plan rides on the count fold behind it, where there is one)
+  plan_rode_ = s.sw && plan_ride_ && !(s.self && s.fold_inside);
+  if (plan_rode_) {
     // the walk plan of the sweep rides on the refresh launch (extra workgroups on the CUs the refresh leaves idle): no dispatch
     // of its own between refresh and scan.  (The fold of the refresh's mutation counts does NOT ride on the scan launch: its
     // 588 000 strided 4-byte reads beside the scan's first waves made the scan 60 us longer -- measured, dropped.)
@@ -690,6 +700,17 @@ int Engine::launch_refresh(const uint8_t *src, const RefreshStage &sg, const Ref
       x.kids = reinterpret_cast<uint2 *>(d_vstage_.p);
     }
     HIPCHK(launch_newview_chains(st_, g_, vec, dops, dlo, plan_.ch_levels, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), done, x));
+    stats.view_launches++;
+  } else if (s.self) {
+    // no schedule: of src the kernel reads the topology array alone (always d_vstage_; its descriptor workgroup reads the pinned
+    // array, which the host leaves alone until the flag is up)
+    HIPCHK(launch_newview_self(st_, g_, vec, reinterpret_cast<const uint2 *>(src), (uint32_t)n_, (uint32_t)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), done,
+                               reinterpret_cast<int32_t *>(d_vstage_.p + sg.nlev_off), reinterpret_cast<const uint2 *>(h_kstage_.p),
+                               s.sw ? *s.sw : SweepDescArgs(), x,
+                               // (the plan cache would replay this refresh: one more workgroup leaves the schedule it finds, for k_newview_wgq)
+                               (plan_cache_ & 2) ? reinterpret_cast<NvOp *>(d_vstage_.p + sg.ops_off) : nullptr,
+                               (plan_cache_ & 2) ? reinterpret_cast<int32_t *>(d_vstage_.p + sg.lev_off) : nullptr));
+    if (x.wm_only) rows_ok_ = false;              // (as k_newview_wgq's word-major shape)
     stats.view_launches++;
   } else if (views_mode_ >= 1) {                  // (always so for a device-made or stored schedule)
     // narrow levels (the partial trees of the addition phase, small refreshes): fewer waves per workgroup -- a wave of the
@@ -713,7 +734,11 @@ int Engine::launch_refresh(const uint8_t *src, const RefreshStage &sg, const Ref
   }
   // the per-tile mutation counts are folded by the refresh kernel's last workgroup when there are few ops (s.fold_inside), by a
   // separate chip-wide launch when there are many (one workgroup would need longer than the launch costs)
-  if (!s.fold_inside)
+  if (s.self) {
+    // (no ops array: the inner slots themselves; the walk plan and the cleared outputs of a sweep ride on this launch -- the
+    //  descriptors they need were written by the refresh launch in front of it)
+    if (!s.fold_inside) HIPCHK(launch_cntsum_slots(st_, (uint32_t)n_, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), tiles_for_levels(g_), x));
+  } else if (!s.fold_inside)
     // (no host mirror here: hundreds of scattered 4-byte writes over PCIe cost more than the one copy-back they would save)
     HIPCHK(launch_cntsum(st_, g_, dops, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(),
                          (views_mode_ >= 1 && !s.chains) ? tiles_for_levels(g_) : 0));   // rows of cntp the refresh kernel wrote
@@ -770,6 +795,7 @@ int Engine::schedule_views(const std::vector<int> *roots)
   if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
   ScopedMs timer(stats.host_views_ms_total);
   RefreshShape s;
+  if (all_invalid_) self_active_ = false;          // (a from-scratch refresh: the self-scheduled routes below say so themselves)
   if (!roots && all_invalid_ && sched_cache_valid_ && !kids_dirty_ && !sankoff_) {
     // the same topology as when the last from-scratch schedule was built (the tree was handed over again, re-weighted or
     // re-evaluated): its ops, level offsets and the topology array are still on the device -- launch, nothing else
@@ -1657,8 +1683,9 @@ int Engine::sweep_scan_dev(int mt, uint64_t *n_tests, uint32_t *min_mp)
     if (warm) HIPCHK(hipMemsetAsync(d_out(), 0, clear_words(nout) * sizeof(uint32_t), st_));
     if (timing_) HIPCHK(hipEventRecord(ev0_, st_));
     if (!warm) {
-      // (the program was planned and the outputs were cleared by the refresh launch's extra workgroups)
-      if (!plan_ride_) HIPCHK(launch_walk_plan(st_, d_kids(), n_, d_walk_.p, (int)nd, d_prog_.p, d_out(), (uint32_t)clear_words(nout)));
+      // (the program was planned and the outputs were cleared by extra workgroups of the refresh launch or, self-scheduled, of the
+      //  count fold behind it)
+      if (!plan_rode_) HIPCHK(launch_walk_plan(st_, d_kids(), n_, d_walk_.p, (int)nd, d_prog_.p, d_out(), (uint32_t)clear_words(nout)));
       prog_gen_ = walk_gen_;
       parts_gen_ = walk_gen_;
       n_parts_dev_ = nd;
@@ -1847,6 +1874,8 @@ int Engine::set_option(const std::string &key, int64_t v)
   }
   if (key == "dev_sched") { dev_sched_ = v != 0; sched_cache_valid_ = false; dsw_valid_ = false; return MPF_OK; }
   if (key == "dev_plan") { dev_plan_ = v != 0; plan_ride_ = !(v & 2); dsw_valid_ = false; return MPF_OK; }   // (bit 1: the walk plan as a launch of its own)               // scan descriptors of mpf_sweep_scan laid out on the device   // refresh schedule of a new topology made on the device (k_sched)
+  // a from-scratch refresh of a complete tree schedules itself (k_newview_self) where the device could make its schedule (A/B switch)
+  if (key == "refresh_self_sched") { refresh_self_sched_ = v != 0; sched_cache_valid_ = false; dsw_valid_ = false; return MPF_OK; }
   if (key == "refresh_wm") { refresh_wm_ = v != 0; return MPF_OK; }          // refreshes on the word-major copy alone where they can (A/B switch; no effect without that copy)
   if (key == "scan_shadow") { scan_shadow_ = v != 0; return MPF_OK; }        // planned scan reads the word-major copy when it is current (A/B switch)
   if (key == "reduce") { g_.reduce = v ? 1 : 0; return MPF_OK; }
@@ -1958,6 +1987,8 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   // ... and whether this engine can follow it at all (DNA with a word-major copy; the weighted engine, wider alphabets and stores of
   // 2 GiB and more ignore the option)
   else if (key == "refresh_wm_active") *v = (refresh_wm_ && !sankoff_ && g_.S == 4 && g_.shoff != 0) ? 1 : 0;
+  else if (key == "refresh_self_sched") *v = refresh_self_sched_ ? 1 : 0;
+  else if (key == "refresh_self_sched_active") *v = self_active_ ? 1 : 0;      // the route of the last from-scratch refresh
   else if (key == "rows_ok") *v = rows_ok_ ? 1 : 0;
   else if (key == "ensure_rows_launches") *v = (int64_t)ensure_rows_launches_;
   else if (key == "scan_batch") *v = scan_batch_;
@@ -1971,7 +2002,8 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "views_tile") *v = g_.nv_tile;
   else if (key == "plan_cache") *v = plan_cache_;
   else if (key == "sched_levels" || key == "sched_ticks" || key == "sched_desc_ticks") {
-    // diagnostics of the last device-made schedule: dependency levels, duration of k_sched's two workgroups (10 ns ticks)
+    // diagnostics of the last device-made schedule: dependency levels, duration of k_sched's two workgroups (10 ns ticks);
+    // self-scheduled: the levels the refresh found, what listing them cost its workgroup 0, the descriptor workgroup's duration
     int32_t w[16] = {0};
     if (sched_on_dev_ && d_vstage_.p) { (void)hipStreamSynchronize(st_); (void)hipMemcpy(w, d_vstage_.p + sc_stage_.nlev_off, 64, hipMemcpyDeviceToHost); }
     *v = w[key == "sched_levels" ? 0 : key == "sched_ticks" ? 1 : 2];

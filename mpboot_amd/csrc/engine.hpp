@@ -300,7 +300,9 @@ class Engine {
   bool dev_sched_usable() const;
   int schedule_views_dev(int sweep_maxtrav);
   // one refresh as its route describes it to the shared tail (launch_refresh, commit_refresh); maxlev < 0: the level count is on the device
-  struct RefreshShape { size_t nops = 0; int maxlev = 0; bool chains = false, direct = false, fold_inside = false, generic = false, ride = false;
+  // self: no schedule at all -- the refresh kernel finds the levels of the complete tree itself (launch_newview_self)
+  struct RefreshShape { size_t nops = 0; int maxlev = 0; bool chains = false, direct = false, fold_inside = false, generic = false, ride = false,
+                             self = false;
                         const SweepDescArgs *sw = nullptr; };
   int launch_refresh(const uint8_t *src, const RefreshStage &sg, const RefreshShape &s);
   int commit_refresh(const RefreshStage &sg, const RefreshShape &s, bool full, int made, bool cacheable);
@@ -887,6 +889,12 @@ private:
   bool refresh_wm_ = true;                      // option refresh_wm: refreshes read and write the word-major copy alone where they can
   uint64_t ensure_rows_launches_ = 0;           // option ensure_rows_launches (read only)
   bool plan_ride_ = true;                       // the walk plan of a device-planned sweep rides on the refresh launch
+  bool plan_rode_ = false;                      // ... and did so on the last one (launch_refresh; else sweep_scan_dev launches it)
+  // option refresh_self_sched: a from-scratch refresh of a complete tree runs without a schedule in front (k_newview_self) where
+  // dev_sched_usable() holds.  With the plan cache on, one workgroup of that launch leaves the schedule for the replay, which is
+  // the stored schedule's as before (sched_cache_valid_, k_newview_wgq)
+  bool refresh_self_sched_ = true;
+  bool self_active_ = false;                    // option refresh_self_sched_active (read only): the route of the last from-scratch refresh
   std::vector<int> sc_order_;
   bool sweep_cache_valid_ = false, walk_dev_reuse_ = false;
   uint64_t walk_gen_ = 0, sweep_cache_gen_ = 0;

@@ -317,14 +317,16 @@ __global__ __launch_bounds__(256) void k_newview(uint32_t *__restrict__ vec, con
 
 // cnt[dst] = sum over tiles of cntp[tile][dst] for the ops of a refresh: 32 lanes per op (one tile each, strided), two ops
 // per group in flight.  The partial counts were written by other workgroups (other XCDs): the caller has acquired them.
-__device__ __forceinline__ void fold_counts(const NvOp *__restrict__ ops, int n_ops, const uint32_t *__restrict__ cntp,
-                                            uint32_t nslots, int tiles, uint32_t *__restrict__ cnt, int tid, int nthreads,
-                                            uint32_t *__restrict__ cnt_host = nullptr)
+// dst_of(i) = the slot op i wrote: from the ops array, or -- a refresh of every inner vector, which has no ops array -- first + i
+template <class DstOf>
+__device__ __forceinline__ void fold_counts_of(DstOf dst_of, int n_ops, const uint32_t *__restrict__ cntp,
+                                               uint32_t nslots, int tiles, uint32_t *__restrict__ cnt, int tid, int nthreads,
+                                               uint32_t *__restrict__ cnt_host)
 {
   const int l32 = tid & 31, grp = tid >> 5, ngrp = nthreads >> 5;
   for (int i = grp; i < n_ops; i += 2 * ngrp) {
     const int j = i + ngrp < n_ops ? i + ngrp : i;
-    const uint32_t d0 = ops[i].dst, d1 = ops[j].dst;
+    const uint32_t d0 = dst_of(i), d1 = dst_of(j);
     uint32_t s0 = 0, s1 = 0;
     for (int t = l32; t < tiles; t += 32) {
       s0 += __builtin_nontemporal_load(cntp + (size_t)t * nslots + d0);
@@ -344,6 +346,12 @@ __device__ __forceinline__ void fold_counts(const NvOp *__restrict__ ops, int n_
       }
     }
   }
+}
+__device__ __forceinline__ void fold_counts(const NvOp *__restrict__ ops, int n_ops, const uint32_t *__restrict__ cntp,
+                                            uint32_t nslots, int tiles, uint32_t *__restrict__ cnt, int tid, int nthreads,
+                                            uint32_t *__restrict__ cnt_host = nullptr)
+{
+  fold_counts_of([ops](int i) { return ops[i].dst; }, n_ops, cntp, nslots, tiles, cnt, tid, nthreads, cnt_host);
 }
 
 // ALL levels in one launch: one 16-wave workgroup per tile walks the levels, the waves share a level's
@@ -938,6 +946,327 @@ __global__ __launch_bounds__(256) void k_cntsum(const NvOp *__restrict__ ops, in
     cnt[dst] = s;
     if (cnt_host) cnt_host[dst] = s;
   }
+}
+
+// ---------------------------------------------------------------- the from-scratch refresh that schedules itself
+//
+// A from-scratch refresh of a complete tree recomputes every inner vector, and the level of a vector follows from the topology
+// array alone (k_sched above).  A tile of sites never needs another tile's vectors, so nothing has to be agreed between workgroups:
+// every refresh workgroup keeps the topology (16 + 16 bits per record) and one level entry per slot in LDS and finds the levels
+// ITSELF, one per barrier, while the operands of the level before are on their way.  No k_sched launch in front; the refresh reads no
+// ops array and no level offsets: the op of a listed record c is (c, kids[c].x, kids[c].y), read from LDS.
+//   round l (inside level l's data loop, between its first operand requests and their use) lists level l + 1: the records whose two
+//   inputs stand at a level <= l.  A record listed in this round gets the entry l + 1 at once; whoever reads that entry in the same
+//   round finds "not settled" or l + 1 -- neither passes "<= l" --, so the level's one barrier is all the ordering there is.
+//   The size of level l + 1 is summed in s_c[(l + 1) % 3]: read by everybody behind the barrier that ends level l, cleared for
+//   level l + 3 by thread 0 behind the barrier after that (every reader is past it then, and nobody adds before the next one).
+// The kernel ends with the first empty level: every record settled (a tree), or nothing left that can settle (not a tree: those
+// vectors stay unwritten, as with k_sched; the host's link check makes this unreachable).  Every round but the last lists at least
+// one record, so there are at most n_ops + 1 of them.
+// The first records of a thread (tid, tid + 1024, ...: four for DNA) stay in registers, packed, 0 once listed (slot 0 is a tip: no
+// record has it twice); further ones -- DNA: trees above 1 367 taxa -- are read back from LDS every round.
+// Tried and dropped: a round that looks only at the vectors of the level at hand and lists the records that take them (2 n_ops
+// look-ups in all instead of two per open record and level).  Its four dependent LDS look-ups per vector made the refresh slower,
+// 62 us against 58 at C3; and reading the 100 MHz clock around every round instead of once changed nothing.
+// LDS: 4 n_ops + 2 (n + n_ops) + 2 n_ops bytes, 106 KB at kSchedMaxSlots (the descriptor workgroup below needs as much): every
+// tree k_sched takes fits.
+static size_t self_sched_lds_bytes(uint32_t n, uint32_t n_ops, bool desc)
+{
+  const size_t ns = (size_t)n + n_ops;
+  const size_t a = (size_t)n_ops * 4 + ((ns * 2 + 15) & ~(size_t)15) + (((size_t)n_ops * 2 + 15) & ~(size_t)15);
+  return desc ? std::max(a, sched_lds_bytes(n, (uint32_t)ns, true)) : a;
+}
+
+// the device copy of the topology array, from the pinned one the host filled in: one thread per inner record (a copy dispatch in its
+// place takes 15 us)
+__global__ __launch_bounds__(256) void k_kids_copy(const uint2 *__restrict__ src, uint2 *__restrict__ dst, uint32_t first, uint32_t count)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) dst[first + i] = src[first + i];
+}
+
+// Workgroups [0, Wp / TW): the refresh, tiles and data loop as k_newview_wgq.  One more where sw.nodep is set: the scan descriptors of
+// the sweep that follows (sweep_desc_block, from the pinned topology array kids_host) -- beside the refresh, not in front of it.
+// One more where ops_out is set: it writes the schedule out for a replay on k_newview_wgq, which is 11 us faster at C3 than this
+// kernel when the schedule is there for the taking (the replay of a self-scheduled refresh by this kernel made the step on a
+// planned topology 10 us longer).
+// diag: {levels, 10 ns ticks of workgroup 0 up to its first list (what no load overlaps), ticks of the descriptor workgroup}
+template <int S, int TW, bool WM = false>
+__global__ __launch_bounds__(1024) void k_newview_self(uint32_t *__restrict__ vec, const uint2 *__restrict__ kids, uint32_t n, uint32_t n_ops,
+                                                       uint32_t *__restrict__ cntp, uint32_t nslots, int Wp, uint32_t *__restrict__ cnt,
+                                                       uint32_t *__restrict__ done, int32_t *__restrict__ diag,
+                                                       const uint2 *__restrict__ kids_host, SweepDescArgs sw, RefreshExtra x,
+                                                       NvOp *__restrict__ ops_out, int32_t *__restrict__ lev_off_out)
+{
+  static_assert(!WM || S == 4, "word-major copy: DNA");
+  constexpr int OPI = 64 / TW;                     // ops per wave and round
+  // Wide state sets (20, 32 rows) hold 2 S registers per operand pair: with the first pair in flight across the listing and four
+  // records in registers they spilled (132-412 bytes per lane).  They list a level first and request its operands afterwards, with
+  // one record per thread in registers (20 rows) or none (32 rows: every register counts there); DNA has the room for both.
+  constexpr int kRegRecs = S == 4 ? 4 : S <= 20 ? 1 : 0;
+  constexpr int kRegArr = kRegRecs ? kRegRecs : 1;   // (no zero-length arrays)
+  constexpr bool EARLY = S == 4;
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
+  __shared__ uint32_t s_c[3], s_wsum[32];
+  __shared__ int s_last;
+  const int nt = Wp / TW;
+  // ops_out: the LAST workgroup only lists -- no tile, no data -- and leaves the schedule it found where launch_newview_levels reads
+  // one (ops by level, level offsets; the level count is diag[0]), for a replay of this refresh on k_newview_wgq
+  const bool lister = ops_out != nullptr && blockIdx.x == gridDim.x - 1u;
+  if ((int)blockIdx.x >= nt && !lister) {
+    const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
+    sweep_desc_block(kids_host, n, n_ops, sw, s_mem, s_wsum);
+    if (threadIdx.x == 0u) diag[2] = (int32_t)(__builtin_amdgcn_s_memrealtime() - t_begin);
+    return;
+  }
+  const uint32_t tid = threadIdx.x, ns = n + n_ops;
+  const int lane = (int)(tid & 63u);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
+  constexpr int nw = 16;
+  const bool timed = blockIdx.x == 0u;
+  const unsigned long long t_begin = timed ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  uint32_t *s_k = reinterpret_cast<uint32_t *>(s_mem);                                     // [n_ops] the two inputs of record n + k
+  uint16_t *s_lev = reinterpret_cast<uint16_t *>(s_mem + (size_t)n_ops * 4);               // [ns] level of every slot, 0xFFFF: not settled
+  uint16_t *s_list = reinterpret_cast<uint16_t *>(s_mem + (size_t)n_ops * 4 + (((size_t)ns * 2 + 15) & ~(size_t)15));   // [n_ops] records by level
+  // (an index beyond the array would reach past the vector store: clamped, whatever the host's link check promises)
+  auto packed = [&](uint32_t k) { const uint2 v = kids[n + k]; return min(v.x, ns - 1u) | (min(v.y, ns - 1u) << 16); };
+  uint32_t kk[kRegArr];
+#pragma unroll
+  for (int j = 0; j < kRegRecs; j++) {
+    const uint32_t k = tid + 1024u * (uint32_t)j;
+    kk[j] = k < n_ops ? packed(k) : 0u;
+    if (k < n_ops) s_k[k] = kk[j];
+  }
+  for (uint32_t k = tid + 1024u * (uint32_t)kRegRecs; k < n_ops; k += 1024u) s_k[k] = packed(k);
+  for (uint32_t c = tid; c < ns; c += 1024u) s_lev[c] = c < n ? (uint16_t)0 : (uint16_t)0xFFFFu;
+  if (tid < 3u) s_c[tid] = 0u;
+  __syncthreads();
+  // lists level l + 1 behind the `e` records of the levels up to l
+  auto list_next = [&](uint32_t l, uint32_t e) {
+    uint32_t *const ctr = &s_c[(l + 1u) % 3u];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    bool rdy[kRegArr];
+    uint32_t pre[kRegArr], tot = 0;
+#pragma unroll
+    for (int j = 0; j < kRegRecs; j++) {
+      rdy[j] = false;
+      if (__ballot(kk[j] != 0u) != 0ull) {         // (wave-uniform; listed lanes read slot 0: a broadcast)
+        const uint32_t la = s_lev[kk[j] & 0xFFFFu], lb = s_lev[kk[j] >> 16];
+        rdy[j] = kk[j] != 0u && la <= l && lb <= l;
+        // an input seen settled is not looked up again (most records wait for ONE deep input): its field becomes slot 0
+        if (la <= l) kk[j] &= 0xFFFF0000u;
+        if (lb <= l) kk[j] &= 0x0000FFFFu;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kRegRecs; j++) {
+      const unsigned long long m = __ballot(rdy[j]);
+      pre[j] = tot + (uint32_t)__builtin_popcountll(m & below);
+      tot += (uint32_t)__builtin_popcountll(m);
+    }
+    if (tot) {                                     // one LDS atomic per wave and round: its records' places in the list
+      uint32_t at = 0;
+      if (lane == 0) at = atomicAdd(ctr, tot);
+      at = e + (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+#pragma unroll
+      for (int j = 0; j < kRegRecs; j++)
+        if (rdy[j]) {
+          const uint32_t c = n + tid + 1024u * (uint32_t)j;
+          s_list[at + pre[j]] = (uint16_t)c;
+          s_lev[c] = (uint16_t)(l + 1u);
+          kk[j] = 0u;
+        }
+    }
+    for (uint32_t k0 = 1024u * (uint32_t)kRegRecs + (tid & ~63u); k0 < n_ops; k0 += 1024u) {   // (wave-uniform bounds)
+      const uint32_t k = k0 + (uint32_t)lane;
+      bool r = false;
+      if (k < n_ops && s_lev[n + k] == 0xFFFFu) {
+        const uint32_t v = s_k[k];
+        r = s_lev[v & 0xFFFFu] <= l && s_lev[v >> 16] <= l;
+      }
+      const unsigned long long m = __ballot(r);
+      if (m != 0ull) {
+        uint32_t at = 0;
+        if (lane == 0) at = atomicAdd(ctr, (uint32_t)__builtin_popcountll(m));
+        at = e + (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+        if (r) {
+          s_list[at + (uint32_t)__builtin_popcountll(m & below)] = (uint16_t)(n + k);
+          s_lev[n + k] = (uint16_t)(l + 1u);
+        }
+      }
+    }
+  };
+  list_next(0u, 0u);                               // level 1: the records between two tips
+  __syncthreads();
+  // what nothing overlaps -- the topology into LDS and the first list -- is what workgroup 0 reports as its listing time
+  const uint32_t ticks = timed ? (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_begin) : 0u;
+  // workgroups go round the 8 XCDs, as in k_newview_wgq
+  const int xcd = (int)(blockIdx.x & 7u), q8 = nt >> 3, r8 = nt & 7;
+  const int tile = xcd * q8 + min(xcd, r8) + (int)(blockIdx.x >> 3);
+  const int sub = lane / TW;
+  const int w0 = tile * TW + (lane % TW);          // Wp is a multiple of 32: always inside the row
+  const int step = OPI * nw;
+  auto op_at = [&](int i) {
+    const uint32_t c = s_list[i], v = s_k[c - n];
+    return NvOp{c, v & 0xFFFFu, v >> 16, 0u};
+  };
+  auto ld = [&](Tile<S, 1> &t, uint32_t slot) {
+    if constexpr (WM) load_tile_wm(t, x.shadow, slot, Wp, w0);
+    else load_tile<S, 1>(t, vec, slot, Wp, w0);
+  };
+  uint32_t l = 1, b = 0;
+  for (;; l++) {
+    const uint32_t in_level = s_c[l % 3u];
+    if (tid == 0u) s_c[(l + 2u) % 3u] = 0u;
+    if (in_level == 0u) break;
+    const int e = (int)(b + in_level);
+    int ib = (int)b + OPI * wave;
+    const bool mine = !lister && ib < e;           // (wave-uniform)
+    if (lister && tid == 0u) lev_off_out[l - 1u] = (int32_t)b;
+    NvOp o = {0u, 0u, 0u, 0u}, o1 = o;
+    Tile<S, 1> ta, tb;
+    // as k_newview_wgq: indices clamped into the level, operands a round ahead -- and (EARLY) the first ones on their way while
+    // level l + 1 is listed
+    auto first = [&]() {
+      o = op_at(min(ib + sub, e - 1));
+      o1 = op_at(min(ib + step + sub, e - 1));
+      ld(ta, o.a);
+      ld(tb, o.b);
+    };
+    if constexpr (EARLY)
+      if (mine) first();
+    list_next(l, (uint32_t)e);
+    if (mine) {
+      if constexpr (!EARLY) first();
+      for (; ib < e; ib += step) {
+        const NvOp o2 = op_at(min(ib + 2 * step + sub, e - 1));
+        Tile<S, 1> na, nb, tc;
+        ld(na, o1.a);
+        ld(nb, o1.b);
+        const uint32_t k = fitch<S, 1>(tc, ta, tb);
+        if constexpr (WM) store_tile_wm(tc, x.shadow, o.dst, Wp, w0);
+        else store_tile<S, 1>(tc, vec, o.dst, Wp, w0);
+        if constexpr (S == 4 && !WM)
+          if (x.shadow) *reinterpret_cast<uint4 *>(x.shadow + ((size_t)o.dst * (size_t)Wp + (size_t)w0) * 4) = make_uint4(tc.v[0][0], tc.v[1][0], tc.v[2][0], tc.v[3][0]);
+        cntp[(size_t)tile * nslots + o.dst] = group_sum<TW>(k);
+        ta = na; tb = nb; o = o1; o1 = o2;
+      }
+    }
+    __syncthreads();
+    b = (uint32_t)e;
+  }
+  if (timed && tid == 0u) { diag[0] = (int32_t)(l - 1u); diag[1] = (int32_t)ticks; }
+  if (lister) {
+    for (uint32_t i = tid; i < b; i += 1024u) {
+      const NvOp o = op_at((int)i);
+      const uint32_t k = o.dst - n;
+      ops_out[i] = NvOp{o.dst, o.a, o.b, 3u * (n + 1u + k / 3u) + k % 3u};      // (pad: the record, as k_sched leaves it)
+    }
+    if (tid == 0u) lev_off_out[l - 1u] = (int32_t)b;
+    return;
+  }
+  if (!done) return;
+  if (tid == 0u) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    const uint32_t ticket = __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = ticket == (uint32_t)nt - 1u;
+  }
+  __syncthreads();
+  if (s_last) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    fold_counts_of([n](int i) { return n + (uint32_t)i; }, (int)n_ops, cntp, nslots, nt, cnt, (int)tid, 1024, x.cnt_host);
+    if (tid == 0u) __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+bool newview_self_supported(const Geometry &g, uint32_t n_taxa, uint32_t n_ops)
+{
+  // (32 rows on 32-word tiles -- rows above 4 096 words, or views_tile 32 -- kept 24 bytes per lane in scratch: not built, k_sched's route)
+  if (g.S > 20 && newview_tile(g) == 32) return false;
+  return !g.sankoff && g.vw == 1 && g.nv_pipe && n_taxa >= 3u && n_ops >= 1u && n_taxa + n_ops <= kSchedMaxSlots;
+}
+
+hipError_t launch_kids_copy(hipStream_t st, const uint2 *src, uint2 *dst, uint32_t first, uint32_t count)
+{
+  if (!count) return hipSuccess;
+  hipLaunchKernelGGL(k_kids_copy, dim3((count + 255u) / 256u), dim3(256), 0, st, src, dst, first, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_newview_self(hipStream_t st, const Geometry &g, uint32_t *vec, const uint2 *kids, uint32_t n_taxa, uint32_t n_ops,
+                               uint32_t *cntp, uint32_t nslots, uint32_t *cnt, uint32_t *done, int32_t *diag, const uint2 *kids_host,
+                               const SweepDescArgs &sw, const RefreshExtra &x, NvOp *ops_out, int32_t *lev_off_out)
+{
+  if (!newview_self_supported(g, n_taxa, n_ops)) return hipErrorInvalidValue;
+  if ((ops_out != nullptr) != (lev_off_out != nullptr)) return hipErrorInvalidValue;
+  if (sw.nodep && (!kids_host || sw.maxtrav < 1u || sw.maxtrav > 6u)) return hipErrorInvalidValue;
+  if (x.wm_only && !(g.S == 4 && g.shoff)) return hipErrorInvalidValue;
+  RefreshExtra xs = x;
+  if (g.shoff && g.S == 4) xs.shadow = vec + g.shoff;
+  const int tw = newview_tile(g);
+  const size_t lds = self_sched_lds_bytes(n_taxa, n_ops, sw.nodep != nullptr);
+  dim3 grid((unsigned)(g.Wp / tw) + (sw.nodep ? 1u : 0u) + (ops_out ? 1u : 0u)), block(1024);
+  hipError_t err = hipSuccess;
+  dispatch_states(g.S, [&](auto S) {
+    auto launch = [&](auto TW, auto WM) {
+      err = lds_opt_in<k_newview_self<S, TW, WM>>(160 * 1024);
+      if (err != hipSuccess) return;
+      hipLaunchKernelGGL((k_newview_self<S, TW, WM>), grid, block, lds, st, vec, kids, n_taxa, n_ops, cntp, nslots, g.Wp, cnt, done, diag,
+                         kids_host, sw, xs, ops_out, lev_off_out);
+    };
+    auto by_tile = [&](auto WM) {
+      if (tw == 32) {
+        if constexpr (S <= 20) launch(int_c<32>(), WM);     // (newview_self_supported: the 32-row one is not built)
+      } else if (tw == 16) launch(int_c<16>(), WM); else if (tw == 8) launch(int_c<8>(), WM); else launch(int_c<4>(), WM);
+    };
+    if constexpr (S == 4) {
+      if (xs.wm_only) { by_tile(bool_c<true>()); return; }
+    }
+    by_tile(bool_c<false>());
+  });
+  return err != hipSuccess ? err : hipGetLastError();
+}
+
+// k_cntsum for a refresh of every inner vector (the slots first .. first + n_ops: there is no ops array).  The first plan_blocks
+// workgroups do what rode on k_newview_wgq's extra workgroups: the walk plan of the sweep that follows and the clearing of its
+// outputs -- both need the descriptors, which the refresh launch in front of this one wrote.
+__global__ __launch_bounds__(256) void k_cntsum_slots(uint32_t first, int n_ops, const uint32_t *__restrict__ cntp, uint32_t nslots, int tiles,
+                                                      uint32_t *__restrict__ cnt, uint32_t *__restrict__ cnt_host, uint32_t plan_blocks,
+                                                      RefreshExtra x)
+{
+  if (blockIdx.x < plan_blocks) {
+    const uint32_t n_parts = x.wp_hdr[0], n_out = x.wp_hdr[1];
+    const uint32_t nw = blockDim.x >> 6, wave = threadIdx.x >> 6;
+    const uint32_t zw = ((n_out ? n_out : 1u) + 1u + 63u) & ~63u;      // (Engine::clear_words)
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < zw; i += plan_blocks * blockDim.x) x.wp_out[i] = 0u;
+    for (uint32_t item = blockIdx.x * nw + wave; item < 2u * n_parts; item += plan_blocks * nw)
+      walk_plan_item(x.wp_kids, x.wp_n, x.wp_desc, (int)n_parts, static_cast<ProgEnt *>(x.wp_prog), 0xFFFFFFFFu, (int)item, (int)(threadIdx.x & 63u));
+    return;
+  }
+  const int l32 = threadIdx.x & 31;
+  const int i = (int)((blockIdx.x - plan_blocks) * (blockDim.x >> 5) + (threadIdx.x >> 5));      // 32 lanes per op
+  if (i >= n_ops) return;
+  const uint32_t dst = first + (uint32_t)i;
+  uint32_t s = 0;
+  for (int t = l32; t < tiles; t += 32) s += cntp[(size_t)t * nslots + dst];
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) s += (uint32_t)__shfl_xor((int)s, m, 32);
+  if (l32 == 0) {
+    cnt[dst] = s;
+    if (cnt_host) cnt_host[dst] = s;
+  }
+}
+
+hipError_t launch_cntsum_slots(hipStream_t st, uint32_t first, int n_ops, const uint32_t *cntp, uint32_t nslots, uint32_t *cnt, int tiles,
+                               const RefreshExtra &x)
+{
+  // (a device-planned sweep: one 4-wave workgroup per 16 possible walk-plan items, as many waves as rode on the refresh launch)
+  const unsigned plan_blocks = x.wp_desc ? std::min(2048u, (2u * x.wp_max_parts + 15u) / 16u) : 0u;
+  const unsigned fold_blocks = n_ops > 0 ? (unsigned)((n_ops + 7) / 8) : 0u;
+  if (plan_blocks + fold_blocks == 0u) return hipSuccess;
+  hipLaunchKernelGGL(k_cntsum_slots, dim3(plan_blocks + fold_blocks), dim3(256), 0, st, first, n_ops, cntp, nslots, tiles, cnt, x.cnt_host,
+                     plan_blocks, x);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------- K2: batched evaluate

@@ -188,6 +188,26 @@ struct SweepDescArgs {
 // that follow
 hipError_t launch_sched(hipStream_t st, const uint2 *kids, uint32_t n_taxa, uint32_t n_ops, NvOp *ops, int32_t *lev_off, int32_t *n_lev,
                         const SweepDescArgs &sw = SweepDescArgs(), uint2 *kids_copy = nullptr);
+// The same refresh WITHOUT a schedule (k_newview_self): every refresh workgroup finds the levels of the complete tree itself, in LDS,
+// from the device copy `kids` of the topology array, while its operands are on their way -- no launch_sched in front, no ops, no
+// level offsets.  Tiles, data loop, counts (cntp[tile][slot], slots n_taxa .. n_taxa + n_ops) and the fold behind `done` as
+// launch_newview_levels' one-word-per-lane kernel; x.wm_only as there.  sw.nodep != nullptr: one more workgroup lays out the
+// sweep's scan descriptors beside the refresh, from the pinned array kids_host.  diag (device): {levels, 10 ns ticks workgroup 0
+// needed for the topology and its first list -- the listing that no load overlaps --, ticks of the descriptor workgroup}.  Trees of
+// up to kSchedMaxSlots vectors -- all that launch_sched takes.
+bool newview_self_supported(const Geometry &g, uint32_t n_taxa, uint32_t n_ops);
+hipError_t launch_newview_self(hipStream_t st, const Geometry &g, uint32_t *vec, const uint2 *kids, uint32_t n_taxa, uint32_t n_ops,
+                               uint32_t *cntp, uint32_t nslots, uint32_t *cnt, uint32_t *done, int32_t *diag, const uint2 *kids_host,
+                               const SweepDescArgs &sw, const RefreshExtra &x,
+                               // both or neither: a further workgroup that only lists leaves the schedule as launch_sched would (ops
+                               // by level, lev_off[0 .. levels]; the level count is diag[0]), for a replay by launch_newview_levels
+                               NvOp *ops_out = nullptr, int32_t *lev_off_out = nullptr);
+// dst[first .. first + count) = src[first .. first + count), one thread per record (src: pinned host memory)
+hipError_t launch_kids_copy(hipStream_t st, const uint2 *src, uint2 *dst, uint32_t first, uint32_t count);
+// launch_cntsum for the slots first .. first + n_ops; x.wp_desc != nullptr: further workgroups of the same launch plan the scan
+// that follows and clear its outputs (x.wp_*, as they rode on launch_newview_levels)
+hipError_t launch_cntsum_slots(hipStream_t st, uint32_t first, int n_ops, const uint32_t *cntp, uint32_t nslots, uint32_t *cnt, int tiles,
+                               const RefreshExtra &x);
 // every level in ONE launch (one 16-wave workgroup per tile, workgroup barrier between levels)
 // Fitch mode also folds the per-tile counts into cnt[dst] (last workgroup; `done` = a zeroed device word, left zeroed);
 // weighted mode leaves that to launch_cntsum
