@@ -394,8 +394,24 @@ int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *f
    and root_taxon is one of the tips present.  Every inner node must have degree exactly 3, else MPF_E_UNSUPPORTED (the k-ary Fitch
    rule depends on the root; an insertion cost on such a tree is not what any reference function computes).  Query taxa are rows of
    the engine's alignment, absent from the backbone and pairwise distinct (else MPF_E_INVALID); n_query = 0 is legal.
-   MPF_E_UNSUPPORTED with a message on a weighted engine: there the cost is a min-plus product rooted as parstree.cpp:439-541 roots
-   it, another kernel family, not served yet.
+
+   The weighted engine (mpf_engine_create_sankoff; -cost m with -starttree PARS or a leaf re-insertion).  Option "place_weighted"
+   (mpf_set_option, default 0): with 0 the three calls answer MPF_E_UNSUPPORTED with a message, as they always did; with 1 they are
+   served (a Fitch engine accepts and ignores the option).  The rule: addTaxonMPFast lends added_node the two directed views of the
+   branch and calls computeParsimonyBranch(added_node->neighbors[0], added_node), neighbors[0] being the new taxon; on a ParsTree
+   the leaf swap (parstree.cpp:449-457) makes the taxon the transformed side and the rest of the tree the parent side (the rows of
+   the matrix).  With A, B the two directed views of branch b, T the query tip's cost row (0 for a state in its set, highest_cost
+   otherwise) and m(v)[z] = min_x(v[x] + cost[z][x]) the stored min-plus transform,
+       cost(q, b) = sum over patterns of w * min_i( m(T_q)[i] + m(A_b)[i] + m(B_b)[i] ).
+   This is the FULL length of the completed tree, rooted at the NEW TAXON'S edge: it equals mpf_compute_parsimony_at(completed tree,
+   root_taxon = the query).  There is no additive backbone length; with a matrix that is not symmetric the evaluation edge matters,
+   and the backbone's root_taxon only fixes the walk order and *tree_length (the backbone's own weighted length at root_taxon, as
+   mpf_polytomy_parsimony gives it).  mpf_iq_parsimony_tree: length_per_step[0] = the star's length at the leaf order[0];
+   length_per_step[k - 2] = the score addTaxonMPFast returned for order[k], i.e. the length of the tree of the first k + 1 taxa
+   evaluated at order[k]'s edge (not a sum of a length and a difference); *score = the last.  All views come from one k_poly_snk_views
+   launch, the Q x B x patterns min-plus product from k_snk_place_costs (place.hip), which adds m(A) and m(B) on its way into LDS
+   and transforms nothing.  The 16-bit store ("sankoff_packed") needs no further condition: the sum of three transforms over
+   disjoint sides is what its guard 3 n_taxa (max cost + 1) < 2^16 covers.
 
    Fitch length does not depend on the root, so with A, B the two directed views of a branch and T the query tip the length is
    len(backbone) + #sites where X and T share no state, X = A & B where that is non-empty, else A | B: all views come from one
@@ -404,7 +420,8 @@ int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *f
    that drops uninformative patterns counts the kept ones (on data without ambiguity-only variation the difference is a constant
    per query and the chosen branch is the same).  Stateless towards the engine's own tree exactly as the polytomy calls are.
    Options: "place_tile" (0 = from the number of outputs | 1 = narrow, 4 queries x 16 branches per workgroup | 2 = wide, 64 x 64 for 4
-   state rows, 32 x 32 for 20 and 32), read-only "place_launches" and, under "timing", "place_kernel_ns".
+   state rows, 32 x 32 for 20 and 32; on the weighted engine 64 x 64 for 4 and 20 state rows, 32 x 32 for 32), "place_weighted" (above),
+   read-only "place_shape" (the shape the last product launch ran: 1 narrow | 2 wide; 0 before the first), read-only "place_launches" and, under "timing", "place_kernel_ns".
 
    mpf_insertion_costs: every insertion test of addTaxonMPFast for each query taxon: cost[q * cap + i] = length of the backbone with
    query_taxa[q] attached to branch i; branches in the order of mpf_polytomy_branch_substitutions for the same lists (*n = 2 m - 3

@@ -448,8 +448,9 @@ int mpf_insertion_costs(mpf_engine *e, int32_t n_inner, const int32_t *first, co
     node1[i] = br[i].node1;
     node2[i] = br[i].node2;
   }
+  const uint32_t base = e->eng.weighted() ? 0u : len;       // (the weighted kernel writes full lengths: there is no additive backbone length)
   for (int q = 0; q < n_query; q++)
-    for (size_t i = 0; i < br.size(); i++) cost[(size_t)q * (size_t)cap + i] = len + d[(size_t)q * br.size() + i];
+    for (size_t i = 0; i < br.size(); i++) cost[(size_t)q * (size_t)cap + i] = base + d[(size_t)q * br.size() + i];
   return MPF_OK;
 }
 
@@ -469,7 +470,7 @@ int mpf_place_taxa(mpf_engine *e, int32_t n_inner, const int32_t *first, const i
     if (best_branch) best_branch[q] = (int32_t)best[(size_t)q].branch;
     if (best_node1) best_node1[q] = at.node1;
     if (best_node2) best_node2[q] = at.node2;
-    if (best_length) best_length[q] = len + best[(size_t)q].delta;
+    if (best_length) best_length[q] = (e->eng.weighted() ? 0u : len) + best[(size_t)q].delta;
   }
   return MPF_OK;
 }

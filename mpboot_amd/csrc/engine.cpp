@@ -1904,6 +1904,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "nni_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("nni_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } nni_vw_ = (int)v; return MPF_OK; }
   if (key == "brlen_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("brlen_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } brlen_vw_ = (int)v; return MPF_OK; }
   if (key == "place_tile") { if (v < 0 || v > 2) { set_error("place_tile: 0 (from the number of outputs), 1 (narrow: 4 queries x 16 branches) or 2 (wide)"); return MPF_E_INVALID; } place_tile_ = (int)v; return MPF_OK; }
+  if (key == "place_weighted") { place_weighted_ = v ? 1 : 0; return MPF_OK; }   // taxon insertion under -cost (host/place.cpp); no effect on a Fitch engine
   if (key == "poly_tile") { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32) { set_error("poly_tile: 0 (from the row length), 4, 8, 16 or 32 words per workgroup"); return MPF_E_INVALID; } poly_tile_ = (int)v; return MPF_OK; }
   if (key == "split_key_bits") { if (v < 1 || v > 64) { set_error("split_key_bits: 1 .. 64"); return MPF_E_INVALID; } split_key_bits_ = (int)v; return MPF_OK; }
   if (key == "rf_chunk_columns") { if (v < 0 || v > (1ll << 31)) { set_error("rf_chunk_columns: 0 (sized by the memory budget) or a number of columns"); return MPF_E_INVALID; } rf_chunk_columns_ = v; return MPF_OK; }
@@ -2031,6 +2032,8 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "brlen_kernel_ns") *v = (int64_t)brlen_kernel_ns_;
   else if (key == "poly_tile") *v = poly_tile_;
   else if (key == "place_tile") *v = place_tile_;
+  else if (key == "place_weighted") *v = place_weighted_;
+  else if (key == "place_shape") *v = place_shape_;
   else if (key == "place_launches") *v = (int64_t)place_launches_;
   else if (key == "place_kernel_ns") *v = (int64_t)place_kernel_ns_;
   else if (key == "poly_launches") *v = (int64_t)poly_launches_;

@@ -376,7 +376,9 @@ class Engine {
   // BINARY tree over a subset of the tips, given as the polytomy calls take their lists with tips allowed to be absent.  br = its
   // branches in the order of polytomy_branch_substitutions; delta (null: not wanted) [n_query][br.size()] = substitutions the
   // attachment of query q in the middle of branch b adds to the backbone's length; best (null: not wanted) [n_query] = (lowest
-  // delta, first branch of the walk that has it), made on the device.  Fitch engine only.  Stateless as the polytomy calls are
+  // delta, first branch of the walk that has it), made on the device.  Stateless as the polytomy calls are.  On a weighted engine
+  // (served under the option "place_weighted" only) delta holds the FULL length of the completed tree evaluated at the query's edge
+  // and nothing is to be added to it; *tree_length is the backbone's own length at root_taxon either way
   struct PlaceBest { uint32_t delta, branch; };
   int place_costs(int n_inner, const int32_t *first, const int32_t *nbr, int root_taxon, int n_query, const int32_t *query_taxa,
                   std::vector<NniBranch> &br, std::vector<uint32_t> *delta, std::vector<PlaceBest> *best, uint32_t *tree_length);
@@ -663,6 +665,10 @@ class Engine {
   // taxon insertion: option "place_tile" (0 = from the number of outputs, queries x branches, 1 = the narrow shape, 2 = the wide shape; place.hpp), read-only
   // place_launches (k_place_costs launches) and, under "timing", place_kernel_ns (HIP-event time of k_place_costs + k_place_best)
   int place_tile_ = 0;
+  // option "place_weighted": the weighted engine serves taxon insertion (k_snk_place_costs, place.hip; the full length of the
+  // completed tree evaluated at the new taxon's edge); 0: refused as before.  No effect on a Fitch engine
+  int place_weighted_ = 0;
+  int place_shape_ = 0;                          // read-only option "place_shape": the shape of the last product launch (1 narrow | 2 wide; 0: none yet)
   uint64_t place_launches_ = 0, place_kernel_ns_ = 0;
   DevBuf<uint32_t> d_place_q_, d_place_out_;
   PinBuf<uint32_t> h_place_q_, h_place_out_;

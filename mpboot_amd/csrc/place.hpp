@@ -22,6 +22,22 @@ int place_pick(int n_query, int n_br, int tile);    // PLACE_AUTO -> the shape f
 // tip's own vector at a pendant branch) joined as above shares no state with the vector in slot qslot[q].  Row-major store only.
 hipError_t launch_place_costs(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                               const uint32_t *qslot, int n_query, uint32_t *delta, int ld, int tile);
+// The weighted (-cost) engine: k_snk_place_costs.  out[q * ld + b] = the FULL weighted length of the tree with the tip in slot
+// qslot[q] in the middle of branch b, evaluated at the new tip's edge (parstree.cpp:439-541, the tip the transformed side):
+//   sum_ptn w * min_i( m(T_q)[i] + m(A_b)[i] + m(B_b)[i] ),   m(v) the stored transform `g.moff` words behind v, A, B = desc[b].a, .b
+// Same scheme as k_place_costs, rows of We = Wp (32-bit store) or Wp / 2 (16-bit store, two patterns per operation) elements:
+//   wide:   4 and 20 rows: 64 x 64, 4 x 4 per lane, KS 16 (4 rows) | 4 (20 rows);   32 rows: 32 x 32, 2 x 2 per lane, KS 4
+//   narrow: 4 queries x 16 branches, 4 x 1 per lane, KT = KS = 16
+// wide_addr: 64-bit element offsets (always taken when a half of the store is 4 GiB or more)
+PlaceShape place_snk_shape(int S, int tile);
+// PLACE_AUTO -> narrow below this many outputs (queries x branches).  Both shapes' times grow with the row length alike, so the
+// line is a number of outputs; measured on C3 (profiles/place/timing_weighted.json): the 16-bit store crosses near 3.5e5,
+// the 32-bit store near 2.45e5; 20 rows on a 1200 x 1000 protein input with 768 taxa held out: near 3.4e5 and 2.75e5.  32 rows were
+// not measured and take the 20-row lines
+long long place_snk_narrow_below(int S, bool packed);
+int place_snk_pick(int S, bool packed, int n_query, int n_br, int tile);
+hipError_t launch_snk_place_costs(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
+                                  const uint32_t *qslot, int n_query, uint32_t *out, int ld, int tile, bool wide_addr);
 // best[2 q] = min_b delta[q * ld + b], best[2 q + 1] = the lowest b that has it (one wave per query)
 hipError_t launch_place_best(hipStream_t st, const uint32_t *delta, int n_br, int n_query, int ld, uint32_t *best);
 

@@ -707,7 +707,12 @@ class FitchEngine:
         """every insertion test of addTaxonMPFast: (node1[m], node2[m], cost[Q][m], tree_length) -- cost[q][i] = the length of the
         backbone (first, nbr: the lists of polytomy_branch_substitutions with tips allowed to be absent, every inner degree 3) with
         taxon queries[q] attached to branch i = (node1[i], node2[i]), branches in the walk order from root_taxon, m = 2 tips - 3.
-        cap (tests): the room handed to the C call; below m nothing is filled and only (m, tree_length) comes back."""
+        cap (tests): the room handed to the C call; below m nothing is filled and only (m, tree_length) comes back.
+
+        A weighted engine (cost=...) serves this, place_taxa and iq_parsimony_tree after set_option("place_weighted", 1) only
+        (default 0: MpfError -6, as before): cost[q][i] is then the FULL weighted length of the completed tree evaluated at the new
+        taxon's edge (what mpf_compute_parsimony_at gives for that tree at root_taxon = queries[q]); tree_length is the backbone's
+        own length at root_taxon, and iq_parsimony_tree's lengths[j] for j >= 1 are the scores at the edge of the taxon just added."""
         f, nb, k = self._lists(first, nbr)
         q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
         m = 2 * k + 1 if cap is None else int(cap)

@@ -9,8 +9,13 @@
 // counts, per query, the sites that share no state with the query tip's own vector.
 //
 // Stateless towards the engine's own tree exactly as the polytomy calls are: its topology stays, its vectors are marked stale, a
-// tracker books nothing.  Fitch engine only: on the weighted engine the cost is a min-plus product rooted as parstree.cpp:439-541
-// roots it -- another kernel family.
+// tracker books nothing.
+//
+// The weighted (-cost) engine, under the option "place_weighted" (default 0: refused as before): the same lists, the same check,
+// the same one view launch (k_poly_snk_views writes every view with its min-plus transform), then k_snk_place_costs: the FULL
+// length of the completed tree evaluated at the new taxon's edge, the taxon the transformed side (parstree.cpp:439-541 with the
+// leaf swap at :449-457).  There is no additive backbone length: *tree_length (the backbone at root_taxon, k_snk_evaluate as
+// mpf_polytomy_parsimony forms it) is reported next to the costs, not added to them.
 #include <string>
 
 #include "../csrc/place.hpp"
@@ -23,7 +28,7 @@ int Engine::place_costs(int n_inner, const int32_t *first, const int32_t *nbr, i
                         std::vector<NniBranch> &br, std::vector<uint32_t> *delta, std::vector<PlaceBest> *best, uint32_t *tree_length)
 {
   const int n = n_;
-  if (sankoff_) {
+  if (sankoff_ && !place_weighted_) {
     set_error("taxon insertion: not served on the weighted (-cost) engine (its cost is a min-plus product rooted at the branch)");
     return MPF_E_UNSUPPORTED;
   }
@@ -53,21 +58,39 @@ int Engine::place_costs(int n_inner, const int32_t *first, const int32_t *nbr, i
   HIPCHK(d_br_desc_.reserve(nb));
   if (!listtree::branch_sides(n, n_inner, first, nbr, t.shape, t.plan, h_br_desc_.p)) { set_error("taxon insertion: inconsistent walk"); return MPF_E_STATE; }
   HIPCHK(hipMemcpyAsync(d_br_desc_.p, h_br_desc_.p, nb * sizeof(BranchDesc), hipMemcpyHostToDevice, st_));
-  HIPCHK(d_poly_cnt_.reserve(rows));
-  HIPCHK(h_poly_cnt_.reserve(rows));
-  HIPCHK(launch_poly_rowsum(st_, g_, d_poly_masks_.p, (int)rows, d_poly_cnt_.p));
-  HIPCHK(hipMemcpyAsync(h_poly_cnt_.p, d_poly_cnt_.p, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+  // pinned: [query slots Q | the root edge's op (weighted engine)]
+  static_assert(sizeof(EvOp) == 4 * sizeof(uint32_t), "the op rides behind the query slots");
+  HIPCHK(h_place_q_.reserve(Q + 4));
+  if (sankoff_) {
+    // the backbone at its root leaf, the rest of the tree the parent side (Engine::polytomy_parsimony); the op goes up from pinned
+    // memory, so the copy is queued behind the view launch and the host does not wait for it here
+    const EvOp op{t.plan.up_slot[(size_t)t.shape.tip_nb[(size_t)root_taxon]], (uint32_t)(root_taxon - 1), 0, 0};
+    std::memcpy(h_place_q_.p + Q, &op, sizeof(op));
+    HIPCHK(d_evops_.reserve(1));
+    HIPCHK(reserve_results(1));
+    HIPCHK(hipMemcpyAsync(d_evops_.p, h_place_q_.p + Q, sizeof(op), hipMemcpyHostToDevice, st_));
+    HIPCHK(hipMemsetAsync(d_out(), 0, clear_words(1) * sizeof(uint32_t), st_));
+    HIPCHK(launch_evaluate(st_, g_, vec_rows(), d_evops_.p, 1, d_out()));
+    HIPCHK(hipMemcpyAsync(h_out(), d_out(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+  } else {
+    HIPCHK(d_poly_cnt_.reserve(rows));
+    HIPCHK(h_poly_cnt_.reserve(rows));
+    HIPCHK(launch_poly_rowsum(st_, g_, d_poly_masks_.p, (int)rows, d_poly_cnt_.p));
+    HIPCHK(hipMemcpyAsync(h_poly_cnt_.p, d_poly_cnt_.p, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+  }
   if (Q) {
     // device: [query slots | delta Q x nb | best 2 Q]
     const size_t o_best = Q * nb, out_words = o_best + 2 * Q;
-    HIPCHK(h_place_q_.reserve(Q));
     HIPCHK(d_place_q_.reserve(Q));
     HIPCHK(d_place_out_.reserve(out_words));
     HIPCHK(h_place_out_.reserve(delta ? out_words : 2 * Q));
     for (size_t q = 0; q < Q; q++) h_place_q_.p[q] = (uint32_t)(query_taxa[q] - 1);
     HIPCHK(hipMemcpyAsync(d_place_q_.p, h_place_q_.p, Q * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
     if (timing_) HIPCHK(hipEventRecord(ev2_, st_));
-    HIPCHK(launch_place_costs(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_place_q_.p, (int)Q, d_place_out_.p, (int)nb, place_tile_));
+    place_shape_ = sankoff_ ? place_snk_pick(g_.S, g_.snk16 != 0, (int)Q, (int)nb, place_tile_) : place_pick((int)Q, (int)nb, place_tile_);
+    if (sankoff_)
+      HIPCHK(launch_snk_place_costs(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_place_q_.p, (int)Q, d_place_out_.p, (int)nb, place_tile_, force_big_ != 0));
+    else HIPCHK(launch_place_costs(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_place_q_.p, (int)Q, d_place_out_.p, (int)nb, place_tile_));
     if (best) HIPCHK(launch_place_best(st_, d_place_out_.p, (int)nb, (int)Q, (int)nb, d_place_out_.p + o_best));
     if (timing_) HIPCHK(hipEventRecord(ev3_, st_));
     place_launches_++;
@@ -79,7 +102,8 @@ int Engine::place_costs(int n_inner, const int32_t *first, const int32_t *nbr, i
   float ms = 0.f;
   if (Q && timing_ && hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) place_kernel_ns_ += (uint64_t)((double)ms * 1e6);
   uint32_t len = 0;
-  for (size_t i = 0; i < rows; i++) len += h_poly_cnt_.p[i];
+  if (sankoff_) len = h_out()[0];
+  else for (size_t i = 0; i < rows; i++) len += h_poly_cnt_.p[i];
   if (tree_length) *tree_length = len;
   if (Q && delta) std::copy(h_place_out_.p, h_place_out_.p + Q * nb, delta->begin());
   if (Q && best) {
@@ -105,7 +129,7 @@ int Engine::parsimony_tree(const int32_t *order, std::vector<int32_t> &first, st
       seen[(size_t)order[i]] = 1;
     }
   }
-  if (sankoff_) {
+  if (sankoff_ && !place_weighted_) {
     set_error("taxon insertion: not served on the weighted (-cost) engine (its cost is a min-plus product rooted at the branch)");
     return MPF_E_UNSUPPORTED;
   }
@@ -121,7 +145,8 @@ int Engine::parsimony_tree(const int32_t *order, std::vector<int32_t> &first, st
     const NniBranch at = br[(size_t)best[0].branch];
     if (k == 3 && length_per_step) length_per_step[0] = len;
     if (!placetree::insert_tip(n, first, nbr, q, at.node1, at.node2)) { set_error("parsimony tree: inconsistent lists"); return MPF_E_STATE; }
-    len += best[0].delta;
+    // Fitch: the backbone's length plus the added steps; weighted: addTaxonMPFast's score is the full length at the new taxon's edge
+    len = sankoff_ ? best[0].delta : len + best[0].delta;
     if (length_per_step) length_per_step[k - 2] = len;
   }
   if (n == 3) {
