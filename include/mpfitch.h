@@ -409,7 +409,7 @@ int mpf_polytomy_branch_lengths(mpf_engine *e, int32_t n_inner, const int32_t *f
    mpf_polytomy_parsimony gives it).  mpf_iq_parsimony_tree: length_per_step[0] = the star's length at the leaf order[0];
    length_per_step[k - 2] = the score addTaxonMPFast returned for order[k], i.e. the length of the tree of the first k + 1 taxa
    evaluated at order[k]'s edge (not a sum of a length and a difference); *score = the last.  All views come from one k_poly_snk_views
-   launch, the Q x B x patterns min-plus product from k_snk_place_costs (place.hip), which adds m(A) and m(B) on its way into LDS
+   launch, the Q x B x patterns min-plus product from k_place_costs over its min-plus algebra (place.hip), which adds m(A) and m(B) on its way into LDS
    and transforms nothing.  The 16-bit store ("sankoff_packed") needs no further condition: the sum of three transforms over
    disjoint sides is what its guard 3 n_taxa (max cost + 1) < 2^16 covers.
 

@@ -573,6 +573,12 @@ class Engine {
   void nni_swap(const NniSwap &m);
   std::vector<NniSwap> nni_log_;
   int nni_vw_ = -1;                              // option "nni_tile": -1 = from the geometry, 0 = word-major copy where current, 1 | 2 | 4 = row-major words per lane
+  // the launch shape a *_tile option value (nni_tile, brlen_tile) stands for.  wm_copy: the views read have a word-major copy at all
+  struct TileShape { int vw; bool wm; };
+  TileShape tile_shape(int tile, bool wm_copy = true) const
+  {
+    return TileShape{tile > 0 ? tile : (tile == 0 ? 1 : g_.vw), wm_copy && tile <= 0 && g_.S == 4 && g_.shoff && shadow_ok_};
+  }
   uint64_t nni_launches_ = 0, nni_rollbacks_ = 0, nni_branches_ = 0;
   // option "nni_weighted": the weighted engine serves the plain NNI entries (ParsTree scoring by k_snk_nni_eval, no rollback:
   // iqtree.cpp:2258); "nni_kept_worse" counts the steps whose moves stayed although the tree came out longer than the best of them
@@ -665,7 +671,7 @@ class Engine {
   // taxon insertion: option "place_tile" (0 = from the number of outputs, queries x branches, 1 = the narrow shape, 2 = the wide shape; place.hpp), read-only
   // place_launches (k_place_costs launches) and, under "timing", place_kernel_ns (HIP-event time of k_place_costs + k_place_best)
   int place_tile_ = 0;
-  // option "place_weighted": the weighted engine serves taxon insertion (k_snk_place_costs, place.hip; the full length of the
+  // option "place_weighted": the weighted engine serves taxon insertion (k_place_costs<PlaceMinPlus>, place.hip; the full length of the
   // completed tree evaluated at the new taxon's edge); 0: refused as before.  No effect on a Fitch engine
   int place_weighted_ = 0;
   int place_shape_ = 0;                          // read-only option "place_shape": the shape of the last product launch (1 narrow | 2 wide; 0: none yet)

@@ -61,6 +61,24 @@ __device__ __forceinline__ void atomic_add_u32(uint32_t *p, uint32_t v)
 {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// the two counts of an NNI branch in one add: lo in the low word (a tree length: it never carries), hi in the high word
+__device__ __forceinline__ void atomic_add_pair(unsigned long long *p, uint32_t lo, uint32_t hi)
+{
+  __hip_atomic_fetch_add(p, ((unsigned long long)hi << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The frame of the kernels that give one wave to each (item, tile) of n_items * tiles, four waves to a workgroup: this wave's item,
+// tile and lane; false for the waves past the end of the last workgroup.  The wave index is uniform and is kept in an SGPR.
+__device__ __forceinline__ bool wave_item(int n_items, int tiles, int &item, int &tile, int &lane)
+{
+  lane = threadIdx.x & 63;
+  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  gw = __builtin_amdgcn_readfirstlane(gw);
+  if (gw >= n_items * tiles) return false;
+  item = gw / tiles;
+  tile = gw - item * tiles;
+  return true;
+}
 
 // ---------------------------------------------------------------- vector tiles in registers
 
@@ -108,6 +126,20 @@ __device__ __forceinline__ void load_tile_wm(Tile<4, 1> &t, const uint32_t *wm, 
 {
   const uint4 x = *reinterpret_cast<const uint4 *>(wm + ((size_t)slot * (size_t)Wp + (size_t)w0) * 4);
   t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
+}
+// A lane's words of the view in `slot` for the per-branch kernels: from the rows, or (WM: `vec` is the word-major copy) load_tile_wm's
+// 16-byte load.  The address is formed vector first, in whole vectors of 4 Wp words: the slot is uniform, so that product stays on
+// the scalar unit (load_tile_wm's (slot Wp + w0) 4 costs k_nni_eval four VGPRs more).
+template <int S, int VW, bool WM>
+__device__ __forceinline__ void load_view(Tile<S, VW> &t, const uint32_t *vec, uint32_t slot, int Wp, int w0)
+{
+  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
+  if constexpr (WM) {
+    const uint4 x = *reinterpret_cast<const uint4 *>(vec + (size_t)slot * (size_t)(4 * Wp) + (size_t)w0 * 4);
+    t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
+  } else {
+    load_tile<S, VW>(t, vec, slot, Wp, w0);
+  }
 }
 __device__ __forceinline__ void store_tile_wm(const Tile<4, 1> &t, uint32_t *wm, uint32_t slot, int Wp, int w0)
 {
@@ -308,11 +340,8 @@ template <int S, int VW, int RED>
 __global__ __launch_bounds__(256) void k_newview(uint32_t *__restrict__ vec, const NvOp *__restrict__ ops, int n_ops,
                                                  uint32_t *__restrict__ cntp, uint32_t nslots, int Wp, int tiles)
 {
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_ops * tiles) return;
-  const int op = gw / tiles, tile = gw - op * tiles;
+  int op, tile, lane;
+  if (!wave_item(n_ops, tiles, op, tile, lane)) return;
   newview_one<S, VW, RED>(vec, ops[op], cntp, nslots, Wp, tile, lane);
 }
 
@@ -1277,11 +1306,8 @@ template <int S, int VW, int RED, bool WM = false>
 __global__ __launch_bounds__(256) void k_evaluate(const uint32_t *__restrict__ vec, const EvOp *__restrict__ ops,
                                                   int n_ops, uint32_t *__restrict__ out, int Wp, int tiles)
 {
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_ops * tiles) return;
-  const int op = gw / tiles, tile = gw - op * tiles;
+  int op, tile, lane;
+  if (!wave_item(n_ops, tiles, op, tile, lane)) return;
   const EvOp o = ops[op];
   bool valid;
   const int w0 = lane_word<VW>(tile, lane, Wp, valid);
@@ -1305,11 +1331,8 @@ __global__ __launch_bounds__(256) void k_evaluate(const uint32_t *__restrict__ v
 __global__ __launch_bounds__(256) void k_rows_from_wm(uint32_t *__restrict__ vec, const uint32_t *__restrict__ wm,
                                                       const uint32_t *__restrict__ slots, int n_slots, int Wp, int tiles)
 {
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_slots * tiles) return;
-  const int i = gw / tiles, tile = gw - i * tiles;
+  int i, tile, lane;
+  if (!wave_item(n_slots, tiles, i, tile, lane)) return;
   const uint32_t slot = slots[i];
   bool valid;
   const int w0 = lane_word<1>(tile, lane, Wp, valid);
@@ -1330,36 +1353,23 @@ template <int S, int VW, int RED, bool WM>
 __global__ __launch_bounds__(256) void k_nni_eval(const uint32_t *__restrict__ vec, const NniDesc *__restrict__ desc,
                                                   int n_br, unsigned long long *__restrict__ out, int Wp, int tiles)
 {
-  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_br * tiles) return;
-  const int br = gw / tiles, tile = gw - br * tiles;
+  int br, tile, lane;
+  if (!wave_item(n_br, tiles, br, tile, lane)) return;
   const NniDesc d = desc[br];
   bool valid;
   const int w0 = lane_word<VW>(tile, lane, Wp, valid);
   Tile<S, VW> a, b, c0, c1;
-  if constexpr (WM) {
-    auto ld = [&](Tile<S, VW> &t, uint32_t cid) {
-      const uint4 x = *reinterpret_cast<const uint4 *>(vec + (size_t)cid * (size_t)(4 * Wp) + (size_t)w0 * 4);
-      t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
-    };
-    ld(a, d.a); ld(b, d.b); ld(c0, d.c0); ld(c1, d.c1);
-  } else {
-    load_tile<S, VW>(a, vec, d.a, Wp, w0);
-    load_tile<S, VW>(b, vec, d.b, Wp, w0);
-    load_tile<S, VW>(c0, vec, d.c0, Wp, w0);
-    load_tile<S, VW>(c1, vec, d.c1, Wp, w0);
-  }
+  load_view<S, VW, WM>(a, vec, d.a, Wp, w0);
+  load_view<S, VW, WM>(b, vec, d.b, Wp, w0);
+  load_view<S, VW, WM>(c0, vec, d.c0, Wp, w0);
+  load_view<S, VW, WM>(c1, vec, d.c1, Wp, w0);
   Tile<S, VW> x, y;
   uint32_t m0 = fitch<S, VW>(x, b, c0) + fitch<S, VW>(y, a, c1);
   m0 += empty_count<S, VW>(x, y);
   uint32_t m1 = fitch<S, VW>(x, b, c1) + fitch<S, VW>(y, a, c0);
   m1 += empty_count<S, VW>(x, y);
   const uint32_t t0 = wave_total<RED>(valid ? m0 : 0u), t1 = wave_total<RED>(valid ? m1 : 0u);
-  if (lane == 0 && (t0 | t1))
-    __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane == 0 && (t0 | t1)) atomic_add_pair(out + br, t0, t1);
 }
 
 // ---------------------------------------------------------------- parsimony branch lengths (PhyloTree::fixNegativeBranch, host/brlen.cpp)
@@ -1374,26 +1384,14 @@ template <int S, int VW, int RED, bool WM>
 __global__ __launch_bounds__(256) void k_branch_subst(const uint32_t *__restrict__ vec, const BranchDesc *__restrict__ desc,
                                                       int n_br, uint32_t *__restrict__ out, int Wp, int tiles)
 {
-  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_br * tiles) return;
-  const int br = gw / tiles, tile = gw - br * tiles;
+  int br, tile, lane;
+  if (!wave_item(n_br, tiles, br, tile, lane)) return;
   const BranchDesc d = desc[br];
   bool valid;
   const int w0 = lane_word<VW>(tile, lane, Wp, valid);
   Tile<S, VW> a, b;
-  if constexpr (WM) {
-    auto ld = [&](Tile<S, VW> &t, uint32_t cid) {
-      const uint4 x = *reinterpret_cast<const uint4 *>(vec + (size_t)cid * (size_t)(4 * Wp) + (size_t)w0 * 4);
-      t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
-    };
-    ld(a, d.a); ld(b, d.b);
-  } else {
-    load_tile<S, VW>(a, vec, d.a, Wp, w0);
-    load_tile<S, VW>(b, vec, d.b, Wp, w0);
-  }
+  load_view<S, VW, WM>(a, vec, d.a, Wp, w0);
+  load_view<S, VW, WM>(b, vec, d.b, Wp, w0);
   const uint32_t cost = empty_count<S, VW>(a, b);
   const uint32_t tot = wave_total<RED>(valid ? cost : 0u);
   if (lane == 0 && tot) atomic_add_u32(out + br, tot);
@@ -1459,28 +1457,16 @@ __global__ __launch_bounds__(256) void k_nni_eval_masks(const uint32_t *__restri
                                                         int n_br, unsigned long long *__restrict__ out, int Wp, int tiles,
                                                         uint32_t *__restrict__ plane0, uint32_t *__restrict__ plane1)
 {
-  static_assert(!WM || (S == 4 && VW == 1), "word-major copy: DNA, one word per lane");
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_br * tiles) return;
-  const int br = gw / tiles, tile = gw - br * tiles;
+  int br, tile, lane;
+  if (!wave_item(n_br, tiles, br, tile, lane)) return;
   const NniDesc d = desc[br];
   bool valid;
   const int w0 = lane_word<VW>(tile, lane, Wp, valid);
   Tile<S, VW> a, b, c0, c1;
-  if constexpr (WM) {
-    auto ld = [&](Tile<S, VW> &t, uint32_t cid) {
-      const uint4 x = *reinterpret_cast<const uint4 *>(vec + (size_t)cid * (size_t)(4 * Wp) + (size_t)w0 * 4);
-      t.v[0][0] = x.x; t.v[1][0] = x.y; t.v[2][0] = x.z; t.v[3][0] = x.w;
-    };
-    ld(a, d.a); ld(b, d.b); ld(c0, d.c0); ld(c1, d.c1);
-  } else {
-    load_tile<S, VW>(a, vec, d.a, Wp, w0);
-    load_tile<S, VW>(b, vec, d.b, Wp, w0);
-    load_tile<S, VW>(c0, vec, d.c0, Wp, w0);
-    load_tile<S, VW>(c1, vec, d.c1, Wp, w0);
-  }
+  load_view<S, VW, WM>(a, vec, d.a, Wp, w0);
+  load_view<S, VW, WM>(b, vec, d.b, Wp, w0);
+  load_view<S, VW, WM>(c0, vec, d.c0, Wp, w0);
+  load_view<S, VW, WM>(c1, vec, d.c1, Wp, w0);
   const size_t row = (size_t)(3 * br) * (size_t)Wp + (size_t)w0;
   uint32_t p0[VW], p1[VW];
   (void)three_joins<S, VW>(a, b, c0, c1, p0, p1);
@@ -1490,8 +1476,7 @@ __global__ __launch_bounds__(256) void k_nni_eval_masks(const uint32_t *__restri
   const uint32_t m1 = three_joins<S, VW>(b, c1, a, c0, p0, p1);
   if (valid) { store_row<VW>(plane0 + row + 2 * (size_t)Wp, p0); store_row<VW>(plane1 + row + 2 * (size_t)Wp, p1); }
   const uint32_t t0 = wave_total<RED>(valid ? m0 : 0u), t1 = wave_total<RED>(valid ? m1 : 0u);
-  if (lane == 0 && (t0 | t1))
-    __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane == 0 && (t0 | t1)) atomic_add_pair(out + br, t0, t1);
 }
 
 // ---------------------------------------------------------------- K4: per-pattern scores
@@ -1508,12 +1493,8 @@ template <int S, int VW>
 __global__ __launch_bounds__(256) void k_site_planes(const uint32_t *__restrict__ vec, const EvOp *__restrict__ ops,
                                                      int n_ops, uint32_t *__restrict__ planes, int Wp, int tiles)
 {
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  const int n_chunks = (n_ops + kPlaneChunk - 1) / kPlaneChunk;
-  if (gw >= n_chunks * tiles) return;
-  const int chunk = gw / tiles, tile = gw - chunk * tiles;
+  int chunk, tile, lane;
+  if (!wave_item((n_ops + kPlaneChunk - 1) / kPlaneChunk, tiles, chunk, tile, lane)) return;
   bool valid;
   const int w0 = lane_word<VW>(tile, lane, Wp, valid);
   uint32_t c[kPlanes][VW];
@@ -2533,11 +2514,8 @@ __global__ __launch_bounds__(256) void k_snk_newview(uint32_t *__restrict__ vec,
                                                      const uint32_t *__restrict__ cost, uint32_t *__restrict__ cntp,
                                                      uint32_t nslots, int We, int tiles)
 {
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_ops * tiles) return;
-  const int op = gw / tiles, tile = gw - op * tiles;
+  int op, tile, lane;
+  if (!wave_item(n_ops, tiles, op, tile, lane)) return;
   newview_one_snk<S, PK>(vec, moff, ops[op], cost, cntp, nslots, We, tile, lane);
 }
 
@@ -2566,11 +2544,8 @@ __global__ __launch_bounds__(256) void k_snk_evaluate(const uint32_t *__restrict
                                                       int We, int tiles)
 {
   typedef SnkT<PK> T;
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_ops * tiles) return;
-  const int op = gw / tiles, tile = gw - op * tiles;
+  int op, tile, lane;
+  if (!wave_item(n_ops, tiles, op, tile, lane)) return;
   const EvOp o = ops[op];
   bool valid;
   const int e0 = lane_word<1>(tile, lane, We, valid);
@@ -2615,6 +2590,7 @@ __device__ __forceinline__ void snk_nni_eval_body(const uint32_t *__restrict__ v
                                                   uint16_t *__restrict__ vals, uint32_t npat, uint32_t *__restrict__ vmax)
 {
   typedef SnkT<PK> T;
+  // (wave_item's lines written out: through the helper the tracked 32-row kernel takes two more AGPRs)
   const int lane = threadIdx.x & 63;
   int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   gw = __builtin_amdgcn_readfirstlane(gw);
@@ -2641,8 +2617,7 @@ __device__ __forceinline__ void snk_nni_eval_body(const uint32_t *__restrict__ v
   };
   const typename T::E b0 = move(mc0, mc1), b1 = move(mc1, mc0);
   const uint32_t t0 = wave_total<0>(valid ? T::wsum(b0, pwgt, e0) : 0u), t1 = wave_total<0>(valid ? T::wsum(b1, pwgt, e0) : 0u);
-  if (lane == 0 && (t0 | t1))
-    __hip_atomic_fetch_add(out + br, ((unsigned long long)t1 << 32) | t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane == 0 && (t0 | t1)) atomic_add_pair(out + br, t0, t1);
   if constexpr (VALS) {
     uint32_t m = 0;
     if (valid) {
@@ -2696,11 +2671,8 @@ __global__ __launch_bounds__(256) void k_snk_branch_eval(const uint32_t *__restr
                                                          int We, int tiles)
 {
   typedef SnkT<PK> T;
-  const int lane = threadIdx.x & 63;
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_br * tiles) return;
-  const int br = gw / tiles, tile = gw - br * tiles;
+  int br, tile, lane;
+  if (!wave_item(n_br, tiles, br, tile, lane)) return;
   const BranchDesc d = desc[br];
   bool valid;
   const int e0 = lane_word<1>(tile, lane, We, valid);
@@ -2747,15 +2719,12 @@ __global__ __launch_bounds__(256, (S == 20 && MAXD <= 6) ? 2 : 1) void k_snk_sca
                                                   const uint32_t *__restrict__ costT)
 {
   typedef SnkT<PK> T;
-  const int lane = threadIdx.x & 63;
   // Work items = (scan, tile of 64 elements), scan-major: the 157 tile-waves of a C5 scan read WHOLE rows of its vectors between
   // them (a row is 40 KB of consecutive bytes).  Round 6 tried the Fitch kernels' XCD classes with a tile-major order inside a class
   // (an XCD's waves = neighbouring scans of one tile, for L2 reuse): 31.0 ms against 24.8 -- 256-byte pieces of 20 rows of many
   // vectors are a worse stream for the memory system than whole rows, and 4 MB of L2 hold 40 of these vectors' pieces anyway.
-  int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  gw = __builtin_amdgcn_readfirstlane(gw);
-  if (gw >= n_scans * tiles) return;
-  const int scan = gw / tiles, tile = gw - scan * tiles;
+  int scan, tile, lane;
+  if (!wave_item(n_scans, tiles, scan, tile, lane)) return;
   const ScanHdr h = hdr[scan];
   uint32_t lane_max = 0;                           // (vals != nullptr: largest per-pattern length written by this lane)
   bool valid;
@@ -3013,6 +2982,38 @@ static inline int tiles_of(const Geometry &g) { return (g.Wp + 64 * g.vw - 1) / 
 // weighted mode: elements per state row (patterns, or pattern pairs in the 16-bit packing)
 static inline int snk_elems(const Geometry &g) { return g.snk16 ? g.Wp / 2 : g.Wp; }
 
+// The launch of a Fitch kernel that gives a wave to each (item, tile): (vw words per lane, word_major) -> the compile-time shape and
+// the grid.  Alphabets beyond DNA run one word per lane; the word-major copy (DNA, where there is one) is read one word per lane.
+// launch(S, VW, RED, WM, src, tiles, grid): src = the store that shape reads
+template <class F>
+static hipError_t launch_per_item(const Geometry &g, const uint32_t *vec, int n_items, int vw, bool word_major, F &&launch)
+{
+  const bool wm = word_major && g.S == 4 && g.shoff;
+  if (g.S != 4 || wm) vw = 1;
+  if ((vw != 1 && vw != 2 && vw != 4) || g.Wp % vw) return hipErrorInvalidValue;
+  const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
+  const dim3 grid((unsigned)(((long)n_items * tiles + 3) / 4));
+  auto shape = [&](auto S, auto VW, auto WM) {
+    dispatch_reduce(g, [&](auto RED) { launch(S, VW, RED, WM, WM ? vec + g.shoff : vec, tiles, grid); });
+  };
+  if (wm) shape(int_c<4>(), int_c<1>(), bool_c<true>());
+  else if (g.S == 4 && vw == 2) shape(int_c<4>(), int_c<2>(), bool_c<false>());
+  else if (g.S == 4 && vw == 4) shape(int_c<4>(), int_c<4>(), bool_c<false>());
+  else dispatch_states(g.S, [&](auto S) { shape(S, int_c<1>(), bool_c<false>()); });
+  return hipGetLastError();
+}
+// The same for the weighted kernels: launch(S, PK, BUF, We, tiles, grid), rows of We elements in tiles of 64.
+// BUF: a half of the store sits behind one 32-bit-offset descriptor (it is below 4 GiB and the caller does not ask for wide addresses)
+template <class F>
+static hipError_t launch_snk_per_item(const Geometry &g, int n_items, bool wide_addr, F &&launch)
+{
+  const int We = snk_elems(g), tiles = (We + 63) / 64;
+  const dim3 grid((unsigned)(((long)n_items * tiles + 3) / 4));
+  const bool buf_ok = !wide_addr && (unsigned long long)g.moff * 4ull < (1ull << 32);
+  dispatch_snk(g, [&](auto S, auto PK) { dispatch_bool(buf_ok, [&](auto BUF) { launch(S, PK, BUF, We, tiles, grid); }); });
+  return hipGetLastError();
+}
+
 // Scans beyond the levels that fit registers keep their per-level up-vectors in g.deep_scratch: the batch is cut into launches whose
 // waves (`tiles` per scan, four per workgroup, per_wave scratch words each) fit the area.  launch(s0, ns, grid) issues scans
 // s0 .. s0 + ns - 1.
@@ -3190,14 +3191,10 @@ hipError_t launch_evaluate(hipStream_t st, const Geometry &g, const uint32_t *ve
   const int tiles = tiles_of(g);
   const long waves = (long)n_ops * tiles;
   dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  if (g.sankoff) {
-    const int We = snk_elems(g), stiles = (We + 63) / 64;
-    dim3 sgrid((unsigned)(((long)n_ops * stiles + 3) / 4));
-    dispatch_snk(g, [&](auto S, auto PK) {
+  if (g.sankoff)
+    return launch_snk_per_item(g, n_ops, false, [&](auto S, auto PK, auto, int We, int stiles, dim3 sgrid) {
       hipLaunchKernelGGL((k_snk_evaluate<S, PK>), sgrid, block, 0, st, vec, g.moff, ops, n_ops, g.cost, g.pwgt, out, We, stiles);
     });
-    return hipGetLastError();
-  }
   if (word_major && g.S == 4 && g.shoff) {         // one word per lane whatever g.vw says
     const int wtiles = (g.Wp + 63) / 64;
     dim3 wgrid((unsigned)(((long)n_ops * wtiles + 3) / 4));
@@ -3220,49 +3217,21 @@ hipError_t launch_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *ve
   if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (g.sankoff) return hipErrorInvalidValue;
-  const bool wm = word_major && g.S == 4 && g.shoff;
-  if (g.S != 4 || wm) vw = 1;
-  if (vw != 1 && vw != 2 && vw != 4) return hipErrorInvalidValue;
-  const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
-  const long waves = (long)n_br * tiles;
-  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  auto launch = [&](auto S, auto VW, auto WM) {
-    dispatch_reduce(g, [&](auto RED) {
-      hipLaunchKernelGGL((k_nni_eval<S, VW, RED, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, desc, n_br, out, g.Wp, tiles);
-    });
-  };
-  if (wm) launch(int_c<4>(), int_c<1>(), bool_c<true>());
-  else if (g.S == 4 && vw == 2) launch(int_c<4>(), int_c<2>(), bool_c<false>());
-  else if (g.S == 4 && vw == 4) launch(int_c<4>(), int_c<4>(), bool_c<false>());
-  else dispatch_states(g.S, [&](auto S) { launch(S, int_c<1>(), bool_c<false>()); });
-  return hipGetLastError();
+  return launch_per_item(g, vec, n_br, vw, word_major, [&](auto S, auto VW, auto RED, auto WM, const uint32_t *src, int tiles, dim3 grid) {
+    hipLaunchKernelGGL((k_nni_eval<S, VW, RED, WM>), grid, dim3(256), 0, st, src, desc, n_br, out, g.Wp, tiles);
+  });
 }
 
-// the same shapes as launch_nni_eval; plane0 / plane1: [3 * n_br][Wp] words each (k_nni_eval_masks)
+// plane0 / plane1: [3 * n_br][Wp] words each (k_nni_eval_masks)
 hipError_t launch_nni_eval_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
                                  unsigned long long *out, int vw, bool word_major, uint32_t *plane0, uint32_t *plane1)
 {
   if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (g.sankoff || !plane0 || !plane1) return hipErrorInvalidValue;
-  const bool wm = word_major && g.S == 4 && g.shoff;
-  if (g.S != 4 || wm) vw = 1;
-  if (vw != 1 && vw != 2 && vw != 4) return hipErrorInvalidValue;
-  if (g.Wp % vw) return hipErrorInvalidValue;
-  const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
-  const long waves = (long)n_br * tiles;
-  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  auto launch = [&](auto S, auto VW, auto WM) {
-    dispatch_reduce(g, [&](auto RED) {
-      hipLaunchKernelGGL((k_nni_eval_masks<S, VW, RED, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, desc, n_br, out, g.Wp, tiles,
-                         plane0, plane1);
-    });
-  };
-  if (wm) launch(int_c<4>(), int_c<1>(), bool_c<true>());
-  else if (g.S == 4 && vw == 2) launch(int_c<4>(), int_c<2>(), bool_c<false>());
-  else if (g.S == 4 && vw == 4) launch(int_c<4>(), int_c<4>(), bool_c<false>());
-  else dispatch_states(g.S, [&](auto S) { launch(S, int_c<1>(), bool_c<false>()); });
-  return hipGetLastError();
+  return launch_per_item(g, vec, n_br, vw, word_major, [&](auto S, auto VW, auto RED, auto WM, const uint32_t *src, int tiles, dim3 grid) {
+    hipLaunchKernelGGL((k_nni_eval_masks<S, VW, RED, WM>), grid, dim3(256), 0, st, src, desc, n_br, out, g.Wp, tiles, plane0, plane1);
+  });
 }
 
 hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const NniDesc *desc, int n_br,
@@ -3271,45 +3240,24 @@ hipError_t launch_snk_nni_eval(hipStream_t st, const Geometry &g, const uint32_t
   if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (!g.sankoff || !g.moff || (vals != nullptr) != (vmax != nullptr)) return hipErrorInvalidValue;
-  const int We = snk_elems(g), tiles = (We + 63) / 64;
-  dim3 grid((unsigned)(((long)n_br * tiles + 3) / 4)), block(256);
-  const bool buf_ok = !wide_addr && (unsigned long long)g.moff * 4ull < (1ull << 32);      // the transform half behind one 32-bit-offset descriptor
-  dispatch_snk(g, [&](auto S, auto PK) {
-    dispatch_bool(buf_ok, [&](auto BUF) {
-      if (vals)
-        hipLaunchKernelGGL((k_snk_nni_eval_vals<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles, vals,
-                           (uint32_t)g.Wp, vmax);
-      else
-        hipLaunchKernelGGL((k_snk_nni_eval<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles);
-    });
+  return launch_snk_per_item(g, n_br, wide_addr, [&](auto S, auto PK, auto BUF, int We, int tiles, dim3 grid) {
+    if (vals)
+      hipLaunchKernelGGL((k_snk_nni_eval_vals<S, PK, BUF>), grid, dim3(256), 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles, vals,
+                         (uint32_t)g.Wp, vmax);
+    else
+      hipLaunchKernelGGL((k_snk_nni_eval<S, PK, BUF>), grid, dim3(256), 0, st, vec, g.moff, desc, n_br, g.cost, g.pwgt, out, We, tiles);
   });
-  return hipGetLastError();
 }
 
-// the shapes of launch_nni_eval (k_branch_subst)
 hipError_t launch_branch_subst(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                                uint32_t *out, int vw, bool word_major)
 {
   if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (g.sankoff) return hipErrorInvalidValue;
-  const bool wm = word_major && g.S == 4 && g.shoff;
-  if (g.S != 4 || wm) vw = 1;
-  if (vw != 1 && vw != 2 && vw != 4) return hipErrorInvalidValue;
-  if (g.Wp % vw) return hipErrorInvalidValue;
-  const int tiles = (g.Wp + 64 * vw - 1) / (64 * vw);
-  const long waves = (long)n_br * tiles;
-  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  auto launch = [&](auto S, auto VW, auto WM) {
-    dispatch_reduce(g, [&](auto RED) {
-      hipLaunchKernelGGL((k_branch_subst<S, VW, RED, WM>), grid, block, 0, st, WM ? vec + g.shoff : vec, desc, n_br, out, g.Wp, tiles);
-    });
-  };
-  if (wm) launch(int_c<4>(), int_c<1>(), bool_c<true>());
-  else if (g.S == 4 && vw == 2) launch(int_c<4>(), int_c<2>(), bool_c<false>());
-  else if (g.S == 4 && vw == 4) launch(int_c<4>(), int_c<4>(), bool_c<false>());
-  else dispatch_states(g.S, [&](auto S) { launch(S, int_c<1>(), bool_c<false>()); });
-  return hipGetLastError();
+  return launch_per_item(g, vec, n_br, vw, word_major, [&](auto S, auto VW, auto RED, auto WM, const uint32_t *src, int tiles, dim3 grid) {
+    hipLaunchKernelGGL((k_branch_subst<S, VW, RED, WM>), grid, dim3(256), 0, st, src, desc, n_br, out, g.Wp, tiles);
+  });
 }
 
 hipError_t launch_snk_branch_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
@@ -3318,15 +3266,9 @@ hipError_t launch_snk_branch_eval(hipStream_t st, const Geometry &g, const uint3
   if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_br <= 0) return hipSuccess;
   if (!g.sankoff || !g.moff) return hipErrorInvalidValue;
-  const int We = snk_elems(g), tiles = (We + 63) / 64;
-  dim3 grid((unsigned)(((long)n_br * tiles + 3) / 4)), block(256);
-  const bool buf_ok = !wide_addr && (unsigned long long)g.moff * 4ull < (1ull << 32);      // each half behind one 32-bit-offset descriptor
-  dispatch_snk(g, [&](auto S, auto PK) {
-    dispatch_bool(buf_ok, [&](auto BUF) {
-      hipLaunchKernelGGL((k_snk_branch_eval<S, PK, BUF>), grid, block, 0, st, vec, g.moff, desc, n_br, g.pwgt, out, We, tiles);
-    });
+  return launch_snk_per_item(g, n_br, wide_addr, [&](auto S, auto PK, auto BUF, int We, int tiles, dim3 grid) {
+    hipLaunchKernelGGL((k_snk_branch_eval<S, PK, BUF>), grid, dim3(256), 0, st, vec, g.moff, desc, n_br, g.pwgt, out, We, tiles);
   });
-  return hipGetLastError();
 }
 
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,

@@ -9,33 +9,38 @@
 namespace mpf {
 
 // Tile shapes of k_place_costs (compile-time).  A workgroup of 256 lanes owns TQ queries x TB branches and walks the
-// row in slices of KS words; a lane holds RQ x RB outputs and, in the narrow shape, one of KT interleaved word classes of a slice
-// (summed through LDS at the end: no atomics).
-//   wide   (many queries):  4 rows: 64 x 64, 4 x 4 per lane, KS 16;   20 | 32 rows: 32 x 32, 2 x 2 per lane, KS 4
+// row in slices of KS elements (words of 32 sites; on the weighted engine patterns, or pairs of patterns in the 16-bit store); a lane
+// holds RQ x RB outputs and, in the narrow shape, one of KT interleaved element classes of a slice (summed through LDS at the end:
+// no atomics).
+//   wide   (many queries):  4 rows: 64 x 64, 4 x 4 per lane, KS 16;   32 rows: 32 x 32, 2 x 2 per lane, KS 4;
+//                           20 rows: the 32-row shape, on the weighted engine 64 x 64, 4 x 4 per lane, KS 4
 //   narrow (few outputs, every computeParsimonyTree step): 4 queries x 16 branches, 4 x 1 per lane, KT = KS = 16
 enum { PLACE_AUTO = 0, PLACE_NARROW = 1, PLACE_WIDE = 2 };
-struct PlaceShape { int tq, tb, ks; };
-PlaceShape place_shape(int S, int tile);            // tile: PLACE_NARROW | PLACE_WIDE
-int place_pick(int n_query, int n_br, int tile);    // PLACE_AUTO -> the shape for that many outputs (narrow below 2^18)
+struct PlaceShape { int tq, tb, rq, rb, ks, kt; };
+constexpr PlaceShape place_shape(int S, bool weighted, int tile)      // tile: PLACE_NARROW | PLACE_WIDE
+{
+  if (tile == PLACE_NARROW) return PlaceShape{4, 16, 4, 1, 16, 16};
+  if (S == 4) return PlaceShape{64, 64, 4, 4, 16, 1};
+  return S == 20 && weighted ? PlaceShape{64, 64, 4, 4, 4, 1} : PlaceShape{32, 32, 2, 2, 4, 1};
+}
+// PLACE_AUTO -> the narrow shape below `narrow_below` outputs (queries x branches), the wide one from there on
+int place_pick(int n_query, int n_br, int tile, long long narrow_below);
+long long place_narrow_below();                     // the Fitch engine's line: 2^18
 
 // delta[q * ld + b] = #sites (weight-replicated) at which branch b = (desc[b].a, desc[b].b: slots of its two directed views, a
 // tip's own vector at a pendant branch) joined as above shares no state with the vector in slot qslot[q].  Row-major store only.
 hipError_t launch_place_costs(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                               const uint32_t *qslot, int n_query, uint32_t *delta, int ld, int tile);
-// The weighted (-cost) engine: k_snk_place_costs.  out[q * ld + b] = the FULL weighted length of the tree with the tip in slot
+// The weighted (-cost) engine.  out[q * ld + b] = the FULL weighted length of the tree with the tip in slot
 // qslot[q] in the middle of branch b, evaluated at the new tip's edge (parstree.cpp:439-541, the tip the transformed side):
 //   sum_ptn w * min_i( m(T_q)[i] + m(A_b)[i] + m(B_b)[i] ),   m(v) the stored transform `g.moff` words behind v, A, B = desc[b].a, .b
-// Same scheme as k_place_costs, rows of We = Wp (32-bit store) or Wp / 2 (16-bit store, two patterns per operation) elements:
-//   wide:   4 and 20 rows: 64 x 64, 4 x 4 per lane, KS 16 (4 rows) | 4 (20 rows);   32 rows: 32 x 32, 2 x 2 per lane, KS 4
-//   narrow: 4 queries x 16 branches, 4 x 1 per lane, KT = KS = 16
+// The same kernel over the min-plus algebra, rows of We = Wp (32-bit store) or Wp / 2 (16-bit store, two patterns per operation) elements.
 // wide_addr: 64-bit element offsets (always taken when a half of the store is 4 GiB or more)
-PlaceShape place_snk_shape(int S, int tile);
 // PLACE_AUTO -> narrow below this many outputs (queries x branches).  Both shapes' times grow with the row length alike, so the
 // line is a number of outputs; measured on C3 (profiles/place/timing_weighted.json): the 16-bit store crosses near 3.5e5,
 // the 32-bit store near 2.45e5; 20 rows on a 1200 x 1000 protein input with 768 taxa held out: near 3.4e5 and 2.75e5.  32 rows were
 // not measured and take the 20-row lines
 long long place_snk_narrow_below(int S, bool packed);
-int place_snk_pick(int S, bool packed, int n_query, int n_br, int tile);
 hipError_t launch_snk_place_costs(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                                   const uint32_t *qslot, int n_query, uint32_t *out, int ld, int tile, bool wide_addr);
 // best[2 q] = min_b delta[q * ld + b], best[2 q + 1] = the lowest b that has it (one wave per query)

@@ -59,8 +59,7 @@ int Engine::branch_substitutions(int root_taxon, std::vector<NniBranch> &br, std
     if (sankoff_ && v2 <= n_) h_br_desc_.p[i] = BranchDesc{slot(r1), slot(r2)};
     else h_br_desc_.p[i] = BranchDesc{slot(r2), slot(r1)};
   }
-  const bool wm = brlen_vw_ <= 0 && g_.S == 4 && g_.shoff && shadow_ok_;
-  const int vw = brlen_vw_ > 0 ? brlen_vw_ : (brlen_vw_ == 0 ? 1 : g_.vw);
+  const auto [vw, wm] = tile_shape(brlen_vw_);
   HIPCHK(hipMemcpyAsync(d_br_desc_.p, h_br_desc_.p, nb * sizeof(BranchDesc), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(d_br_out_.p, 0, nb * sizeof(uint32_t), st_));
   if (timing_) HIPCHK(hipEventRecord(ev0_, st_));

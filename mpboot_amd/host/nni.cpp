@@ -81,8 +81,7 @@ int Engine::nni_eval(const std::vector<NniBranch> &br, std::vector<uint32_t> &le
       (*moves)[2 * i + 1] = NniSwap{v1, s1[0], v2, s2[1]};
     }
   }
-  bool wm = nni_vw_ <= 0 && g_.S == 4 && g_.shoff && shadow_ok_;
-  int vw = nni_vw_ > 0 ? nni_vw_ : (nni_vw_ == 0 ? 1 : g_.vw);
+  const auto [vw, wm] = tile_shape(nni_vw_);
   if (nb) {
     HIPCHK(hipMemcpyAsync(d_nni_desc_.p, h_nni_desc_.p, nb * sizeof(NniDesc), hipMemcpyHostToDevice, st_));
     HIPCHK(hipMemsetAsync(d_nni_out_.p, 0, nb * sizeof(unsigned long long), st_));

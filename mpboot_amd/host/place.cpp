@@ -12,7 +12,7 @@
 // tracker books nothing.
 //
 // The weighted (-cost) engine, under the option "place_weighted" (default 0: refused as before): the same lists, the same check,
-// the same one view launch (k_poly_snk_views writes every view with its min-plus transform), then k_snk_place_costs: the FULL
+// the same one view launch (k_poly_snk_views writes every view with its min-plus transform), then k_place_costs over the min-plus algebra: the FULL
 // length of the completed tree evaluated at the new taxon's edge, the taxon the transformed side (parstree.cpp:439-541 with the
 // leaf swap at :449-457).  There is no additive backbone length: *tree_length (the backbone at root_taxon, k_snk_evaluate as
 // mpf_polytomy_parsimony forms it) is reported next to the costs, not added to them.
@@ -87,7 +87,7 @@ int Engine::place_costs(int n_inner, const int32_t *first, const int32_t *nbr, i
     for (size_t q = 0; q < Q; q++) h_place_q_.p[q] = (uint32_t)(query_taxa[q] - 1);
     HIPCHK(hipMemcpyAsync(d_place_q_.p, h_place_q_.p, Q * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
     if (timing_) HIPCHK(hipEventRecord(ev2_, st_));
-    place_shape_ = sankoff_ ? place_snk_pick(g_.S, g_.snk16 != 0, (int)Q, (int)nb, place_tile_) : place_pick((int)Q, (int)nb, place_tile_);
+    place_shape_ = place_pick((int)Q, (int)nb, place_tile_, sankoff_ ? place_snk_narrow_below(g_.S, g_.snk16 != 0) : place_narrow_below());
     if (sankoff_)
       HIPCHK(launch_snk_place_costs(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_place_q_.p, (int)Q, d_place_out_.p, (int)nb, place_tile_, force_big_ != 0));
     else HIPCHK(launch_place_costs(st_, g_, vec_rows(), d_br_desc_.p, (int)nb, d_place_q_.p, (int)Q, d_place_out_.p, (int)nb, place_tile_));

@@ -151,7 +151,7 @@ int Engine::polytomy_branch_substitutions(int n_inner, const int32_t *first, con
   if (sankoff_)
     for (size_t i = 0; i < nb; i++)
       if (br[i].node2 <= n) std::swap(h_br_desc_.p[i].a, h_br_desc_.p[i].b);
-  const int vw = brlen_vw_ > 0 ? brlen_vw_ : (brlen_vw_ == 0 ? 1 : g_.vw);       // (the row-major store only: no word-major copy of these views)
+  const int vw = tile_shape(brlen_vw_, false).vw;                                  // (the row-major store only: no word-major copy of these views)
   HIPCHK(hipMemcpyAsync(d_br_desc_.p, h_br_desc_.p, nb * sizeof(BranchDesc), hipMemcpyHostToDevice, st_));
   HIPCHK(hipMemsetAsync(d_br_out_.p, 0, nb * sizeof(uint32_t), st_));
   if (timing_) HIPCHK(hipEventRecord(ev2_, st_));
