@@ -841,7 +841,12 @@ int mpf_reset_stats(mpf_engine *e);
      "host_poll"       1 (default) = small batches: the host waits for the flag word the scan's last workgroup raises behind the
                        results it writes to pinned memory, instead of a stream synchronisation
      "check_counts"    1 = compare the kernel's candidate counts with the host's, and check the view bookkeeping
-     "force_big"       1 = 64-bit addressing in the scan kernel even below 2 GiB of vectors (set before the first tree)
+     "force_big"       1 = 64-bit addressing in the scan kernel even below 2 GiB of vectors (set before the first tree); on a
+                       weighted engine: 64-bit pointers per row in the scan (k_snk_scan / k_snk_scan_deep) and in the per-branch
+                       kernels, what a half of the store of 4 GiB and more takes by itself -- read-only "snk_scan_wide" /
+                       "snk_scan_deep" tell what the launcher dispatched for the last weighted scan batch (rows through 64-bit
+                       pointers / k_snk_scan_deep), "snk_deep_batches" / "snk_deep_launches" count the deep batches since
+                       creation and the launches they were cut into (option "deep_scratch_kwords")
      "timing"          1 = HIP events around the scan kernels (mpf_stats scan_kernel_ms_total), 2 = around the refresh
                        kernels too (view_kernel_ms_total); an event pair costs about 10 us on the stream */
 int mpf_set_option(mpf_engine *e, const char *key, int64_t value);

@@ -1159,7 +1159,8 @@ int Engine::run_scans(std::vector<ScanPlan> &plans, std::vector<uint32_t> &out_h
     vals_rows_ = (uint32_t)nout;
   }
   HIPCHK(launch_scan(st_, g_, vec_rows(), dhdr, (int)nh, dprog, d_out(), prog_max_depth_, host_direct ? h_out() : nullptr, (uint32_t)nout,
-                     d_done_.p + 16, vals, (uint32_t)g_.Wp, vmax));
+                     d_done_.p + 16, vals, (uint32_t)g_.Wp, vmax, force_big_ != 0, sankoff_ ? &snk_ran_ : nullptr));
+  if (sankoff_ && snk_ran_.deep) { snk_deep_batches_++; snk_deep_launches_ += snk_ran_.launches; }
   if (timing_) HIPCHK(hipEventRecord(ev1_, st_));
   if (host_direct) {           // the kernels wrote the host's result buffers themselves
     cnt_copy_pending_ = false;
@@ -2034,6 +2035,12 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "place_tile") *v = place_tile_;
   else if (key == "place_weighted") *v = place_weighted_;
   else if (key == "place_shape") *v = place_shape_;
+  // what launch_scan dispatched for the last weighted batch (0 before the first): rows through 64-bit pointers (BUF off) / k_snk_scan_deep;
+  // and, since creation, the batches k_snk_scan_deep served and the launches they were cut into
+  else if (key == "snk_scan_wide") *v = snk_ran_.wide;
+  else if (key == "snk_scan_deep") *v = snk_ran_.deep;
+  else if (key == "snk_deep_batches") *v = snk_deep_batches_;
+  else if (key == "snk_deep_launches") *v = snk_deep_launches_;
   else if (key == "place_launches") *v = (int64_t)place_launches_;
   else if (key == "place_kernel_ns") *v = (int64_t)place_kernel_ns_;
   else if (key == "poly_launches") *v = (int64_t)poly_launches_;

@@ -760,6 +760,8 @@ private:
   std::vector<uint32_t> cost_, cost_dev_, costT_dev_;
   bool asym_ = false;                            // the (repaired) cost matrix is not symmetric: evaluations are rooted as the reference roots them
   int force_big_ = 0;
+  SnkScanRan snk_ran_;                           // read-only options "snk_scan_wide" / "snk_scan_deep": what launch_scan dispatched for the last weighted batch
+  int64_t snk_deep_batches_ = 0, snk_deep_launches_ = 0;   // read-only options: batches k_snk_scan_deep served, launches they were cut into
   int snk16_opt_ = 1;                            // allow the packed 16-bit cost arithmetic when the values fit
   std::vector<int32_t> inf_index_;               // informative pattern j -> original pattern index
   DevBuf<uint32_t> d_cost_, d_costT_, d_pwgt_;

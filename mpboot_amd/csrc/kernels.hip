@@ -3273,7 +3273,7 @@ hipError_t launch_snk_branch_eval(hipStream_t st, const Geometry &g, const uint3
 
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,
                        const ScanOp *ops, uint32_t *out, int max_depth, uint32_t *host_out, uint32_t n_out, uint32_t *done,
-                       uint16_t *vals, uint32_t npat, uint32_t *vmax)
+                       uint16_t *vals, uint32_t npat, uint32_t *vmax, bool wide_addr, SnkScanRan *ran)
 {
   if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
   if (n_scans <= 0) return hipSuccess;
@@ -3284,7 +3284,7 @@ hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, c
     const int We = snk_elems(g), stiles = (We + 63) / 64;
     const long waves = (long)n_scans * stiles;
     dim3 sgrid((unsigned)((waves + 3) / 4));
-    const bool buf_ok = (unsigned long long)g.moff * 4ull < (1ull << 32);      // each half of the store behind one 32-bit-offset descriptor
+    const bool buf_ok = !wide_addr && (unsigned long long)g.moff * 4ull < (1ull << 32);      // each half of the store behind one 32-bit-offset descriptor
     // (S, PK) x asymmetric cost matrix (costT) x raw-buffer addressing
     auto dispatch = [&](auto &&f) {
       dispatch_snk(g, [&](auto S, auto PK) {
@@ -3294,13 +3294,16 @@ hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, c
     if (max_depth > scan_reg_depth(g.S, true)) {
       // beyond the levels that fit registers: k_snk_scan_deep
       const int levels = max_depth + 1;
+      if (ran) *ran = SnkScanRan{buf_ok ? 0 : 1, 1, 0};
       return launch_deep(g, (size_t)levels * (size_t)(g.S * 64), stiles, n_scans, [&](long s0, int ns, dim3 dgrid) {
+        if (ran) ran->launches++;
         dispatch([&](auto S, auto PK, auto ASYM, auto BUF) {
           hipLaunchKernelGGL((k_snk_scan_deep<S, PK, ASYM, BUF>), dgrid, block, 0, st, vec, g.moff, hdr + s0, ns, ops, g.cost, g.pwgt, out,
                              We, stiles, vals, npat, vmax, g.costT, g.deep_scratch, levels);
         });
       });
     }
+    if (ran) *ran = SnkScanRan{buf_ok ? 0 : 1, 0, 1};
     dispatch([&](auto S, auto PK, auto ASYM, auto BUF) {
       dispatch_depth<kMaxDepth>(max_depth, [&](auto D) {
         if constexpr (D <= scan_reg_depth(S, true))

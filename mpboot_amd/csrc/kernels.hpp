@@ -264,12 +264,18 @@ hipError_t launch_branch_subst(hipStream_t st, const Geometry &g, const uint32_t
 // (ParsTree::computeParsimonyBranch's dad_branch / node_branch).  wide_addr as launch_snk_nni_eval
 hipError_t launch_snk_branch_eval(hipStream_t st, const Geometry &g, const uint32_t *vec, const BranchDesc *desc, int n_br,
                                   uint32_t *out, bool wide_addr = false);
+// what launch_scan dispatched for a weighted batch: wide = rows read through 64-bit pointers (k_snk_scan / k_snk_scan_deep
+// <..., BUF = false>: a half of the store reaches 4 GiB, or the caller asked for wide addresses), deep = k_snk_scan_deep (more levels
+// than the registers keep), launches = kernel launches the batch took (a deep batch is cut to the scratch)
+struct SnkScanRan { int wide = 0, deep = 0, launches = 0; };
 hipError_t launch_scan(hipStream_t st, const Geometry &g, const uint32_t *vec, const ScanHdr *hdr, int n_scans,
                        const ScanOp *ops, uint32_t *out, int max_depth,
                        uint32_t *host_out = nullptr, uint32_t n_out = 0, uint32_t *done = nullptr,   // as launch_scan_walk
                        // weighted mode, online UFBoot: vals[out index][npat] = per-pattern lengths of every tentative tree
                        // (16 bits each), *vmax = the largest of them (atomic max)
-                       uint16_t *vals = nullptr, uint32_t npat = 0, uint32_t *vmax = nullptr);
+                       uint16_t *vals = nullptr, uint32_t npat = 0, uint32_t *vmax = nullptr,
+                       bool wide_addr = false /* weighted mode: as launch_snk_nni_eval */,
+                       SnkScanRan *ran = nullptr /* weighted mode: what was dispatched */);
 hipError_t launch_scan_walk(hipStream_t st, const Geometry &g, const uint32_t *vec, const uint2 *kids, int n_taxa,
                             const WalkDesc *desc, int n_scans, uint32_t *out, uint32_t *ncand, int max_depth,
                             uint32_t *masks = nullptr, uint2 *info = nullptr,   // masks != nullptr: UFBoot variant (ufboot.hip)

@@ -9,6 +9,7 @@ reference run to pin against (parity status of this mode: unpinned).  What is ch
 import numpy as np
 import pytest
 
+import sankoff_edge_cases as sec
 from helpers import FIXTURES, load_fixture, trace_tokens
 from oracle import pyoracle as po, sankoff_slow
 
@@ -118,3 +119,93 @@ def test_general_costs_against_slow_dp(name):
                 assert sankoff_slow.tree_cost(fx["codes_np"], fx["weights"], moved, cost, fx["datatype"])[0] == int(m)
                 checked += 1
     assert checked > 20
+
+
+# ---- the inputs of tests/test_gpu_sankoff_edges.py (groups A-F, tests/sankoff_edge_cases.py): oracle and plain reference agree on
+#      every one of them, so the reference side of the GPU tests is sound before anything runs on a device
+#      (large group E cases: 2 of the 6 scanned prune nodes at radius 6 -- the GPU test compares group E with the oracle alone)
+def _oracle(case, weights=None):
+    return po.Oracle(case["codes"], case["weights"] if weights is None else weights, datatype=case["datatype"], cost=case["cost"])
+
+
+def _check_tree(o, case, back, weights=None):
+    ref, ptn = sec.slow_tree(case, back, weights)
+    assert o.score_tree(back) == ref
+    got, total = o.pattern_scores()
+    inf = o.informative().astype(bool)
+    assert total == ref and (got[inf] == ptn[inf]).all() and not got[~inf].any()
+    return ref
+
+
+def _check_scans(o, case, back, cur, radius, weights=None, nodes=None):
+    """every candidate of the chosen prune nodes: the oracle's traced length == the plain reference's length of the rearranged tree.
+    A matrix that is not symmetric: the plain reference roots the rearranged tree where the insertion test does (sec.slow_candidate)."""
+    o.reset_nodep()
+    o.set_tree(back)
+    assert o.score_tree() == cur
+    o.seed_ties(po.TIE_RANDOM, 2)
+    n = case["codes"].shape[0]
+    checked = 0
+    for rec in sec.spread(o.nodep()[1:2 * n - 1], case["nodes"] if nodes is None else nodes):
+        o.set_best(cur)
+        o.trace(True)
+        o.rearrange(rec, 1, radius)
+        prune = rec
+        for a, m in zip(*o.get_trace()):
+            if a == -1:
+                prune = rec
+            elif a == -2:
+                prune = int(back[rec])
+            else:
+                assert sec.slow_candidate(case, prune, int(a), back, weights) == int(m), (case["name"], prune, int(a))
+                checked += 1
+    return checked
+
+
+@pytest.mark.parametrize("key", sec.CASE_KEYS, ids=["-".join(str(x) for x in k) for k in sec.CASE_KEYS])
+def test_edge_case_inputs_against_slow_dp(key):
+    case = sec.get_case(key)
+    o = _oracle(case)
+    if case["ninf"] is not None:
+        assert o.num_informative == case["ninf"]
+    n = case["codes"].shape[0]
+    cur = _check_tree(o, case, case["back"])
+    for b in case.get("every_tree", ()):
+        _check_tree(o, case, b)
+    checked = sum(_check_scans(o, case, case["back"], cur, r, nodes=case.get("slow_nodes")) for r in case.get("slow_radii", case["radii"]))
+    assert checked > 0 or case["ninf"] == 0
+    for w in case.get("weight_vectors", ()):
+        o.set_weights(w)
+        cw = _check_tree(o, case, case["back"], w)
+        assert _check_scans(o, case, case["back"], cw, 6, w) > 0
+
+
+@pytest.mark.parametrize("gate,matrix", sec.D_PARAMS)
+def test_largest_stored_value_inside_the_16_bit_gate(gate, matrix):
+    """what the packed side of each group D case stores: the largest entry of any directed view or transform, and the largest sum of
+    three transforms, over the start tree and every rearrangement of the 8 scanned prune nodes at radius 6 -- both below 2^16, and
+    the view entries below 2^15 (about n x the largest closed entry)"""
+    case = sec.case_d(gate, matrix, 0)
+    n = case["codes"].shape[0]
+    packed, highest = sec.expect_packed(case["cost"], case["datatype"], n)
+    assert packed and not sec.expect_packed(sec.case_d(gate, matrix, 1)["cost"], case["datatype"], n)[0]
+    o = _oracle(case)
+    o.reset_nodep()
+    o.set_tree(case["back"])
+    cur = o.score_tree()
+    moves = []
+    for rec in sec.spread(o.nodep()[1:2 * n - 1], case["nodes"]):
+        o.set_best(cur)
+        o.trace(True)
+        o.rearrange(rec, 1, 6)
+        prune = rec
+        for a in o.get_trace()[0]:
+            prune = rec if a == -1 else int(case["back"][rec]) if a == -2 else prune
+            if a >= 0:
+                moves.append((prune, int(a)))
+    # (on the matrix and the rows the kernels carry: binary codes 1, 2, 3 are DNA codes of the 4-row kernels, the two added rows filled)
+    top_view, top_sum = sankoff_slow.largest_entries(case["codes"], case["back"], sec.closed_kernel_matrix(case["cost"], case["datatype"]),
+                                                     sankoff_slow.DNA if case["datatype"] == sec.BIN else case["datatype"], moves)
+    print(f"\n{case['name']}: largest view entry {top_view}, largest sum of three {top_sum}, n x highest_cost {n * highest}")
+    assert top_view <= n * highest < 32768 and top_view < 32768
+    assert top_sum < 3 * n * highest < 65536
