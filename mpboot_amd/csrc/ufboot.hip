@@ -738,7 +738,8 @@ hipError_t launch_join_masks(hipStream_t st, const Geometry &g, const uint32_t *
 
 template <int MT, int NT, int WM, int WN, int KS, int NS, int EXPR = 0, bool M32 = false>
 static hipError_t launch_bitgemm_t(hipStream_t st, const uint32_t *masks, int rows_padded, int Wp, const uint8_t *Wt, int Bp, int32_t *C,
-                                   int mult, int accumulate, const uint32_t *rowsel, const uint32_t *row_limit, long want_default = 192)
+                                   int mult, int accumulate, const uint32_t *rowsel, const uint32_t *row_limit, BitgemmRan *ran,
+                                   long want_default = 192)
 {
   constexpr int TM = 16 * MT * WM;
   const int row_blocks = rows_padded / TM, col_blocks = Bp / (16 * NT * WN);
@@ -767,13 +768,15 @@ static hipError_t launch_bitgemm_t(hipStream_t st, const uint32_t *masks, int ro
   constexpr size_t lds = gemm_lds<MT, NT, WM, WN, KS, NS>();
   const hipError_t e = lds_opt_in<k_bitgemm<MT, NT, WM, WN, KS, NS, EXPR, M32>>((int)lds);
   if (e != hipSuccess) return e;
+  if (ran) *ran = BitgemmRan{TM, 16 * NT * WN, ksplit, per, (int)gx, atomic, M32 ? 1 : 0};
   hipLaunchKernelGGL((k_bitgemm<MT, NT, WM, WN, KS, NS, EXPR, M32>), dim3(gx, (unsigned)ksplit), dim3(64 * WM * WN), lds, st, masks, Wp, Wt, Bp, C, mult, atomic, row_blocks, per, rowsel, row_limit);
   return hipGetLastError();
 }
 
 hipError_t launch_bitgemm(hipStream_t st, const uint32_t *masks, int rows_padded, int Wp, const uint8_t *Wt, int Bp, int32_t *C,
-                          int mult, int accumulate, const uint32_t *rowsel, const uint32_t *row_limit)
+                          int mult, int accumulate, const uint32_t *rowsel, const uint32_t *row_limit, BitgemmRan *ran)
 {
+  if (ran) *ran = BitgemmRan{};
   if (rows_padded <= 0) return hipSuccess;
   // 256-sample column blocks when the (padded) sample count allows, else 128-sample blocks with twice the rows per
   // workgroup (sample-sharded runs: 1000 samples over 8 GPUs = 125 per rank)
@@ -785,29 +788,29 @@ hipError_t launch_bitgemm(hipStream_t st, const uint32_t *masks, int rows_padded
     // (C3 climb from a random tree, 1000 samples, product kernels in total: 512 x 128 tiles 0.298 s, 256 x 128 0.253 s, 128 x 128
     //  0.234 s, 128 x 256 0.264 s -- fewer K-splits per output element, i.e. fewer atomic adds into C, and all CUs busy)
     static const int small_v = std::getenv("MPF_GEMM_SMALL") ? std::atoi(std::getenv("MPF_GEMM_SMALL")) : 2;
-    if (small_v == 1 && rows_padded <= 1024) return launch_bitgemm_t<4, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (small_v == 2 && rows_padded <= 2048) return launch_bitgemm_t<1, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, 256);
-    if (small_v == 3 && rows_padded <= 2048) return launch_bitgemm_t<2, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (small_v == 4 && rows_padded <= 2048) return launch_bitgemm_t<1, 16, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
+    if (small_v == 1 && rows_padded <= 1024) return launch_bitgemm_t<4, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (small_v == 2 && rows_padded <= 2048) return launch_bitgemm_t<1, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran, 256);
+    if (small_v == 3 && rows_padded <= 2048) return launch_bitgemm_t<2, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (small_v == 4 && rows_padded <= 2048) return launch_bitgemm_t<1, 16, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
 #ifdef MPF_EXPERIMENTS                     // (knock-out variants of tools/gemm_bounds.sh, wrong results on purpose: `make EXPERIMENTS=1` only)
     static const int expr = std::getenv("MPF_GEMM_EXPERIMENT") ? std::atoi(std::getenv("MPF_GEMM_EXPERIMENT")) : 0;
-    if (expr == 1) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 1>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (expr == 2) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (expr == 3) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 3>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (expr == 6) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 6>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (expr == 4) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 4>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
+    if (expr == 1) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 1>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (expr == 2) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (expr == 3) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 3>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (expr == 6) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 6>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (expr == 4) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 4>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
 #endif
     // variants (all within 0.43-0.49 of the nominal peak, tools/gemm_bounds.sh): 0 = two k-blocks per stage, four stages in
     // the ring; 1 / 3 = 4 x 2 waves of 64 rows x 128 samples; default = 8 x 1 waves of 32 rows x 256 samples, four k-blocks
     // per stage, two stages
-    if (variant == 4) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 0, true>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (variant == 5) return launch_bitgemm_t<4, 8, 4, 2, 4, 2, 0, true>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (variant == 1) return launch_bitgemm_t<2, 16, 8, 1, 2, 4>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (variant == 2) return launch_bitgemm_t<4, 8, 4, 2, 2, 4>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    if (variant == 3) return launch_bitgemm_t<4, 8, 4, 2, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
-    return launch_bitgemm_t<2, 16, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
+    if (variant == 4) return launch_bitgemm_t<2, 16, 8, 1, 4, 2, 0, true>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (variant == 5) return launch_bitgemm_t<4, 8, 4, 2, 4, 2, 0, true>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (variant == 1) return launch_bitgemm_t<2, 16, 8, 1, 2, 4>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (variant == 2) return launch_bitgemm_t<4, 8, 4, 2, 2, 4>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    if (variant == 3) return launch_bitgemm_t<4, 8, 4, 2, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
+    return launch_bitgemm_t<2, 16, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
   }
-  return launch_bitgemm_t<4, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit);
+  return launch_bitgemm_t<4, 8, 8, 1, 4, 2>(st, masks, rows_padded, Wp, Wt, Bp, C, mult, accumulate, rowsel, row_limit, ran);
 }
 
 int ufb_row_padding(int rows, int Bp)

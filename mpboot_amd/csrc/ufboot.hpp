@@ -16,8 +16,12 @@ hipError_t launch_join_masks(hipStream_t st, const Geometry &g, const uint32_t *
 // C[rows_padded][Bp] = (accumulate ? C : 0) + mult * masks x Wt; rows_padded % kUfbRowTile == 0, Bp % kUfbColTile == 0
 // rowsel (optional, rows_padded entries): output row i multiplies mask row rowsel[i]
 // row_limit (optional, device word): row blocks that start at or behind *row_limit are skipped (their part of C is left as it is)
+// what launch_bitgemm dispatched: the workgroup tile (rows x samples), the K-splits (grid.y) and the k-blocks of each, grid.x,
+// whether the workgroups add into C with atomics, and whether the kernel runs on the 32x32x32 MFMA forms
+struct BitgemmRan { int tm = 0, tn = 0, ksplit = 0, kb_per_split = 0, grid_x = 0, atomic = 0, m32 = 0; };
 hipError_t launch_bitgemm(hipStream_t st, const uint32_t *masks, int rows_padded, int Wp, const uint8_t *Wt, int Bp, int32_t *C,
-                          int mult, int accumulate, const uint32_t *rowsel = nullptr, const uint32_t *row_limit = nullptr);
+                          int mult, int accumulate, const uint32_t *rowsel = nullptr, const uint32_t *row_limit = nullptr,
+                          BitgemmRan *ran = nullptr);
 hipError_t launch_colsum(hipStream_t st, const int32_t *C, int rows, int Bp, int32_t *rt);
 // rt += C[row] - C[home]
 hipError_t launch_rt_update(hipStream_t st, int32_t *rt, const int32_t *C, int Bp, uint32_t row, uint32_t home);
