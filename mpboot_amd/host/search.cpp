@@ -17,6 +17,7 @@
 #include "../csrc/engine.hpp"
 #include "../csrc/grow.hpp"
 #include "simd_util.hpp"
+#include "spr_rule.hpp"
 
 namespace mpf {
 
@@ -159,15 +160,9 @@ int Engine::spr_sweeps_run(int mintrav, int maxtrav, SweepCursor &cur, uint32_t 
         long sel = -1;
         // a candidate worse than the best so far changes nothing (no counter, no draw): that is nearly all of them, so
         // the loop runs over the parts' output blocks with that test first
+        auto draw = [&] { return tie_draw(); };
         auto offer = [&](uint32_t mp, long c) {
-          if (mp > best_) return;
-          if (tie_mode_ == MPF_TIE_RANDOM) {
-            if (mp < best_) hits_ = 1;
-            else hits_++;
-            if (mp < best_ || tie_draw() <= 1.0 / (double)hits_) { best_ = mp; sel = c; }
-          } else if (mp < best_) {
-            best_ = mp; sel = c;
-          }
+          if (sprrule::offer(tie_mode_, mp, best_, hits_, draw)) sel = c;
         };
         if (pl.walked) {
           long c = 0;
@@ -186,16 +181,7 @@ int Engine::spr_sweeps_run(int mintrav, int maxtrav, SweepCursor &cur, uint32_t 
           insert_rec_ = candidate_record(pl, (size_t)sel);
           remove_rec_ = sel < pl.n_p ? pl.rec : back_[pl.rec];
         }
-        bool accept;
-        if (tie_mode_ == MPF_TIE_RANDOM) {
-          if (best_ == randomMP) iter_hits++;
-          if (best_ < randomMP) iter_hits = 1;
-          accept = (best_ < randomMP || (best_ == randomMP && tie_draw() <= 1.0 / (double)iter_hits)) &&
-                   remove_rec_ >= 0 && insert_rec_ >= 0;
-        } else {
-          accept = best_ < randomMP;
-        }
-        if (accept) {
+        if (sprrule::accept(tie_mode_, best_, randomMP, iter_hits, remove_rec_ >= 0 && insert_rec_ >= 0, draw)) {      // :3306-3311
           moves_.push_back(Move{remove_rec_, insert_rec_, best_});
           apply_move(remove_rec_, insert_rec_);
           randomMP = best_;
@@ -360,11 +346,7 @@ int Engine::addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *inser
       const int c = stack.back();
       stack.pop_back();
       const uint32_t mp = (sankoff_ ? 0u : len) + out[out_of[(size_t)c]];   // weighted: the join kernel returns the full length
-      if (tie_mode_ == MPF_TIE_RANDOM) {
-        if (mp < best_) hits_ = 1;
-        else if (mp == best_) hits_++;
-        if (mp < best_ || (mp == best_ && tie_draw() <= 1.0 / (double)hits_)) { best_ = mp; insert_rec_ = c; }
-      } else if (mp < best_) { best_ = mp; insert_rec_ = c; }
+      if (sprrule::offer(tie_mode_, mp, best_, hits_, [&] { return tie_draw(); })) insert_rec_ = c;      // :3001-3008
       if (!tip(c) && sc_[c] > 0) {
         stack.push_back(back_[nx(nx(c))]);
         stack.push_back(back_[nx(c)]);

@@ -450,6 +450,33 @@ void Engine::ufb_flush_pending(const ScanPlan &pl)
   u.pending.clear();
 }
 
+// sample-sharded run: every rank replays the events of all ranks -- one all-gather per batch, events <- the ranks' lists in rank order
+int Engine::ufb_gather_events(std::vector<UfbEvent> &events, uint32_t tag)
+{
+  static_assert(sizeof(UfbEvent) == sizeof(mpf_ufb_event), "event layouts must match");
+  UfbState &u = *ufb_;
+  const mpf_ufb_event *all = nullptr;
+  uint32_t n_all_ev = 0;
+  if (u.exchange(u.exchange_arg, tag, reinterpret_cast<const mpf_ufb_event *>(events.data()), (uint32_t)events.size(), &all, &n_all_ev) != 0) {
+    set_error("online UFBoot: event exchange failed (ranks out of step?)");
+    return MPF_E_STATE;
+  }
+  const UfbEvent *pa = reinterpret_cast<const UfbEvent *>(all);
+  events.assign(pa, pa + n_all_ev);
+  return MPF_OK;
+}
+
+// ... and the closing handshake of a tracked climb: a rank that took another path would be in the middle of a batch here
+int Engine::ufb_close_exchange()
+{
+  UfbState &u = *ufb_;
+  if (!u.exchange) return MPF_OK;
+  const mpf_ufb_event *all = nullptr;
+  uint32_t n_all_ev = 0;
+  if (u.exchange(u.exchange_arg, 0xFFFFFFFFu, nullptr, 0, &all, &n_all_ev) != 0) { set_error("online UFBoot: ranks out of step at the end of the climb"); return MPF_E_STATE; }
+  return MPF_OK;
+}
+
 // the tentatively inserted topology of one insertion test: subtree p re-inserted into branch q
 void Engine::ufb_candidate_topology(int p, int q, std::vector<int32_t> &bk) const
 {
@@ -715,8 +742,6 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
   std::vector<UfbEvent> events, ev_tmp;
   std::vector<uint32_t> ev_count;
   std::vector<uint32_t> small, sel_rows, crow, self_list;
-  std::vector<int32_t> mh_bk;                      // -mulhits: a candidate's topology and its canonical form
-  std::string mh_key;
   bool have_C = false;
   uint32_t exchange_tag = 0;
   if (!u.rt_valid) { int rc = ufb_current_tree_reps(); if (rc) return rc; }
@@ -748,6 +773,16 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
   bool moot_on = false;
   std::vector<int32_t> lcol;                       // ratchet: the original-frequency column of the product, per mask row
   uint32_t sw_mp_max = 0;
+  // what this loop puts into the shared visit replay (ufb_replay_visit, host/ufboot_common.hpp): device-walked parts with the
+  // skip-ahead under a plain cut-off, and a ratchet candidate's length on the original alignment from the product's column
+  struct Visit : UfbPartsVisit {
+    const UfbState *u = nullptr;
+    const uint2 *hinfo = nullptr;
+    const std::vector<int32_t> *lcol = nullptr;
+    uint32_t stale_len(uint32_t idx, uint32_t home) const { return (uint32_t)((int64_t)u->rt_orig - (int64_t)(*lcol)[(size_t)home] + (int64_t)(*lcol)[(size_t)hinfo[idx].x]); }
+  } V;
+  V.e = this; V.u = &u; V.events = &events; V.lcol = &lcol; V.log_open = &log_open;
+  V.ratchet = ratchet; V.store_trees = store_trees; V.defer = defer; V.host_self = host_self;
   do {
     int i = 1;
     if (resume_i > 0) { i = resume_i; resume_i = 0; }          // (the sweep the quiet stretch handed over: order and startMP stand)
@@ -780,14 +815,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
       const int np = hi - i + 1;
       // ---- the first prune node with a strictly better candidate ends the batch for certain: nothing behind it
       //      needs REPS (a tie may end it earlier; then the tail of the product is simply not used)
-      int jstar = np - 1;
-      for (int j = 0; j < np && !chained; j++) {
-        const ScanPlan &pl = plans[(size_t)j];
-        uint32_t m = UINT32_MAX;
-        for (int pi = 0; pi < pl.n_parts; pi++)
-          for (int k = 0; k < pl.part_cnt[pi]; k++) m = std::min(m, out[pl.part_off[pi] + (uint32_t)k]);
-        if (m != UINT32_MAX && pl.base + m < randomMP) { jstar = j; break; }
-      }
+      const int jstar = chained ? np - 1 : ufb_first_better(plans, np, out, randomMP);
       const double lim = -u.logl_cutoff + 1e-4;
       const uint32_t mp_max = have_cut ? (lim <= 0.0 ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
       const bool none_pass = have_cut && lim <= 0.0;
@@ -1034,25 +1062,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
         if (ratchet && have_C) lcol.assign(u.h_col.p, u.h_col.p + n_rows);
         // a chained batch was multiplied and extracted as a whole: what lies behind the first prune node with a strictly better
         // candidate is never replayed (the batch ends there at the latest) -- dropped before the sort
-        uint32_t idx_cut = n_idx;
-        if (chained) {
-          int js = np - 1;
-          for (int j = 0; j < np; j++) {
-            const ScanPlan &pl = plans[(size_t)j];
-            uint32_t m = UINT32_MAX;
-            for (int pi = 0; pi < pl.n_parts; pi++)
-              for (int k = 0; k < pl.part_cnt[pi]; k++) m = std::min(m, out[pl.part_off[pi] + (uint32_t)k]);
-            if (m != UINT32_MAX && pl.base + m < randomMP) { js = j; break; }
-          }
-          if (js < np - 1) {
-            idx_cut = 0;
-            for (int j = 0; j <= js; j++) {
-              const ScanPlan &pl = plans[(size_t)j];
-              if (pl.self_idx >= 0) idx_cut = std::max(idx_cut, (uint32_t)pl.self_idx + 1u);
-              for (int pi = 0; pi < pl.n_parts; pi++) idx_cut = std::max(idx_cut, pl.part_off[pi] + (uint32_t)pl.part_cnt[pi] + 1u);
-            }
-          }
-        }
+        const uint32_t idx_cut = chained ? ufb_index_cut(plans, np, out, randomMP, n_idx) : n_idx;
         const bool fused_sort = !u.exchange && n_ev >= 512;
         if (fused_sort) {
           // straight from the pinned copy: local column -> sample of the run, ordered by sample (first counting pass)
@@ -1086,18 +1096,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
           }
           n_ev = (uint32_t)events.size();
         }
-        if (u.exchange) {
-          // sample-sharded run: every rank replays the events of all ranks (one all-gather per batch)
-          static_assert(sizeof(UfbEvent) == sizeof(mpf_ufb_event), "event layouts must match");
-          const mpf_ufb_event *all = nullptr;
-          uint32_t n_all_ev = 0;
-          if (u.exchange(u.exchange_arg, exchange_tag++, reinterpret_cast<const mpf_ufb_event *>(events.data()), (uint32_t)events.size(), &all, &n_all_ev) != 0) {
-            set_error("online UFBoot: event exchange failed (ranks out of step?)");
-            return MPF_E_STATE;
-          }
-          const UfbEvent *pa = reinterpret_cast<const UfbEvent *>(all);
-          events.assign(pa, pa + n_all_ev);
-        }
+        if (u.exchange) { int rc2 = ufb_gather_events(events, exchange_tag++); if (rc2) return rc2; }
         if (!fused_sort) sort_events(events, ev_tmp, ev_count, n_idx, (uint32_t)u.B);
         u.events += n_ev;
         t0 = now_ms();
@@ -1131,139 +1130,19 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
         }
         moot_on = true;
       }
-      // ---- host replay in the reference's order
-      size_t ep = 0;
+      // ---- host replay in the reference's order (ufb_replay_visit, host/ufboot_common.hpp)
+      V.out = out; V.hinfo = hinfo; V.h_rt = u.h_rt.p; V.ep = 0;
+      V.none_pass = none_pass; V.mp_max = mp_max; V.skip_ahead = have_cut && !ratchet && !store_trees;
+      V.product_self = ran_events; V.product_cand = have_C;      // (have_C: a ratchet batch with candidates always has its product)
+      V.moot = moot_on ? &moot : nullptr;
       bool moved = false;
       int j = i;
       for (; j <= hi && !moved; j++) {
         const ScanPlan &pl = plans[(size_t)(j - i)];
-        const int32_t cur_plan = (int32_t)(j - i);
-        if (tie_mode_ == MPF_TIE_RANDOM) {
-          insert_rec_ = remove_rec_ = -1;
-          hits_ = 1;
-        }
-        long sel = -1;
-        uint32_t sel_idx = 0, sel_home = 0;
-        size_t c = 0;
-        // the update rule of one booked tree (iqtree.cpp:3684-3731) over the samples whose events name output index idx
-        // treels.find(tree_str) / treels[tree_str] = tree_index (iqtree.cpp:3500-3514, :3689-3707): a topology that some
-        // sample accepted before keeps the index of that first tree
-        auto topology_key = [&](uint32_t cand_code) -> const std::string & {
-          if (cand_code == 0xFFFFFFFFu) {
-            if (u.self_key_epoch != (uint64_t)topo_epoch_) { canonical_topology(back_, u.self_key); u.self_key_epoch = (uint64_t)topo_epoch_; }
-            return u.self_key;
-          }
-          ufb_candidate_topology(cand_code < (uint32_t)pl.n_p ? pl.rec : back_[pl.rec], candidate_record(pl, (size_t)cand_code), mh_bk);
-          canonical_topology(mh_bk, mh_key);
-          return mh_key;
-        };
-        auto lookup_topology = [&](int64_t tree_index, uint32_t cand_code) -> int64_t {
-          const double tl = now_ms();
-          const int64_t ti = u.topo_index.emplace(topology_key(cand_code), tree_index).first->second;
-          u.t_lookup += now_ms() - tl;
-          u.lookups++;
-          return ti;
-        };
-        // the update rule of one booked tree for one sample (b, score s): shared by the events the device extracted and by the
-        // current tree's own bookings, which the host walks through itself
-        const UfbDeferCtx dctx{defer, cur_plan, &log_open, moot_on ? &moot : nullptr};
-        auto one_event = [&](const uint32_t b, const uint32_t s, int64_t &tree_index, bool &looked_up, const uint32_t cand_code) {
-          ufb_one_event(b, s, tree_index, looked_up, cand_code, lookup_topology, dctx);      // (host/ufboot_common.hpp)
-        };
-        auto replay_events = [&](uint32_t idx, int64_t tree_index, uint32_t cand_code) {
-          while (ep < events.size() && events[ep].idx < idx) ep++;
-          bool looked_up = store_trees;              // (-storetrees: tree_str is set at the top, no lookup per sample)
-          for (; ep < events.size() && events[ep].idx == idx; ep++) one_event(events[ep].b, events[ep].s, tree_index, looked_up, cand_code);
-        };
-        // the current tree scores R_T[b] for every sample: no device events for its slots (they would be B per prune-node visit,
-        // 2.0e6 per move-less C3 sweep, all to be copied and ordered) -- the host has R_T and offers it to every sample in order
-        auto replay_self = [&](int64_t tree_index) {
-          if (defer) { ufb_self_default(u.h_rt.p, tree_index, cur_plan, log_open, u.draws, moot_on ? &moot : nullptr); return; }
-          bool looked_up = store_trees;
-          for (int c2 = 0; c2 < u.Bl; c2++) one_event((uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2], tree_index, looked_up, 0xFFFFFFFFu);
-        };
-        // one tree arriving at saveCurrentTree with length cur_len: its index in treels_logl, or -1 when nothing is booked.
-        // Default: the cut-off test, then a new index (iqtree.cpp:3343-3348).  -storetrees: looked up by topology first
-        // (:3302-3341); one met before is skipped unless the length improved on the recorded one, and then it goes on under
-        // its old index without the cut-off test.
-        auto book_tree = [&](uint32_t cur_len, bool passes_cut, uint32_t cand_code) -> int64_t {
-          return ufb_book_tree(cur_len, passes_cut, cand_code, store_trees, topology_key);
-        };
-        if (pl.self_idx >= 0) {
-          // rearrangeParsimony's evaluateParsimony(p) + pllSaveCurrentTreeSprParsimony (sprparsimony.cpp:2285-2289): the
-          // current tree, length randomMP, once per prune node and before any of its insertion tests
-          bool pass;
-          if (!ratchet) pass = !none_pass && randomMP <= mp_max;
-          else {
-            pass = (store_trees || !u.gate_closed) && ran_events && !none_pass && u.stale_len <= mp_max;
-            if (!pass) u.gate_closed = true;
-          }
-          u.cur_logl_now = -(int32_t)(ratchet ? u.stale_len : randomMP);
-          const int64_t tree_index = book_tree(ratchet ? u.stale_len : randomMP, pass, 0xFFFFFFFFu);
-          if (tree_index >= 0) {
-            if (host_self) replay_self(tree_index); else replay_events((uint32_t)pl.self_idx, tree_index, 0xFFFFFFFFu);
-            if (ratchet) u.stale_len = u.rt_orig;        // _pattern_pars now holds the current tree
-          }
-        }
-        for (int pi = 0; pi < pl.n_parts; pi++) {
-          const uint32_t home = pl.part_off[pi] + (uint32_t)pl.part_cnt[pi];
-          for (int k = 0; k < pl.part_cnt[pi]; k++, c++) {
-            if (have_cut && !ratchet && !store_trees) {
-              // under a cut-off most insertion tests change nothing: not booked (above the cut-off) and longer than the best tree so
-              // far (no counter, no draw) -- on to the next one that is either (best_ only falls while the block is read)
-              const uint32_t lim_len = std::max(none_pass ? 0u : mp_max, best_);
-              const int k2 = lim_len >= pl.base ? first_le(out + pl.part_off[pi], k, pl.part_cnt[pi], lim_len - pl.base) : pl.part_cnt[pi];
-              c += (size_t)(k2 - k);
-              k = k2;
-              if (k >= pl.part_cnt[pi]) break;
-            }
-            const uint32_t idx = pl.part_off[pi] + (uint32_t)k;
-            const uint32_t mp = pl.base + out[idx];
-            // saveCurrentTree(-mp) (reference sprparsimony.cpp:2163-2166), before the SPR tie rule
-            bool pass;
-            if (!ratchet) pass = !none_pass && mp <= mp_max;
-            else {
-              // iqtree.cpp:3283-3295 then :3343: the filter sees the length booked last; a tree that fails leaves
-              // _pattern_pars as it is, so every later candidate of the climb fails too (-storetrees: unless a known
-              // topology gets in past the cut-off)
-              pass = (store_trees || !u.gate_closed) && have_C && !none_pass && u.stale_len <= mp_max;     // (have_C: a ratchet batch with candidates always has its product)
-              if (!pass) u.gate_closed = true;
-            }
-            u.cur_logl_now = -(int32_t)(ratchet ? u.stale_len : mp);
-            const int64_t tree_index = book_tree(ratchet ? u.stale_len : mp, pass, (uint32_t)c);          // iqtree.cpp:3302-3348
-            if (tree_index >= 0) {
-              replay_events(idx, tree_index, (uint32_t)c);
-              // pllComputePatternParsimony (:3365) has now refreshed _pattern_pars for THIS candidate: its length on the
-              // original alignment is what the next call will see
-              if (ratchet) u.stale_len = (uint32_t)((int64_t)u.rt_orig - (int64_t)lcol[(size_t)home] + (int64_t)lcol[(size_t)hinfo[idx].x]);
-            }
-            // testInsertParsimony's tie rule (reference :2168-2176 / fastDNAparsimony.c:1224-1229)
-            if (tie_mode_ == MPF_TIE_RANDOM) {
-              if (mp < best_) hits_ = 1;
-              else if (mp == best_) hits_++;
-              if (mp < best_ || (mp == best_ && tie_draw() <= 1.0 / (double)hits_)) { best_ = mp; sel = (long)c; sel_idx = idx; sel_home = home; }
-            } else if (mp < best_) {
-              best_ = mp; sel = (long)c; sel_idx = idx; sel_home = home;
-            }
-          }
-        }
-        if (sel >= 0) {
-          insert_rec_ = candidate_record(pl, (size_t)sel);
-          remove_rec_ = sel < pl.n_p ? pl.rec : back_[pl.rec];
-        }
-        if (!defer) ufb_flush_pending(pl);
-        else if (log_open) { u.log.push_back(UfbState::LogEntry{0xFFFFFFFFu, 0u, 0, cur_plan}); log_open = false; }
-        bool accept;
-        if (tie_mode_ == MPF_TIE_RANDOM) {
-          if (best_ == randomMP) iter_hits++;
-          if (best_ < randomMP) iter_hits = 1;
-          accept = (best_ < randomMP || (best_ == randomMP && tie_draw() <= 1.0 / (double)iter_hits)) &&
-                   remove_rec_ >= 0 && insert_rec_ >= 0;
-        } else {
-          accept = best_ < randomMP;
-        }
-        if (accept) {
-          if (sel < 0) { set_error("online UFBoot: accepted move without a candidate of this prune node"); return MPF_E_STATE; }
+        V.cur_plan = (int32_t)(j - i);
+        { int rc2 = ufb_replay_visit(pl, V, randomMP, iter_hits); if (rc2) return rc2; }
+        const uint32_t sel_idx = V.sel_idx, sel_home = V.sel_home;
+        if (V.accept) {
           // the accepted candidate becomes the current tree: R_T += C[cand] - C[home]
           {
             uint32_t rc_ = 0xFFFFFFFFu, rh_ = 0xFFFFFFFFu;
@@ -1315,12 +1194,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
   } while (randomMP < startMP && !visits_out());
   ufb_drain_log();
   climb_finished(total);
-  if (u.exchange) {
-    // closing handshake: a rank that took another path would be in the middle of a batch here
-    const mpf_ufb_event *all = nullptr;
-    uint32_t n_all_ev = 0;
-    if (u.exchange(u.exchange_arg, 0xFFFFFFFFu, nullptr, 0, &all, &n_all_ev) != 0) { set_error("online UFBoot: ranks out of step at the end of the climb"); return MPF_E_STATE; }
-  }
+  { int rc = ufb_close_exchange(); if (rc) return rc; }
   if (final_score) *final_score = randomMP;
   abort_guard.ok = true;
   return MPF_OK;

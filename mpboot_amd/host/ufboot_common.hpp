@@ -17,6 +17,7 @@
 #include "../csrc/engine.hpp"
 #include "lcg_block.hpp"
 #include "simd_util.hpp"
+#include "spr_rule.hpp"
 
 namespace mpf {
 
@@ -159,11 +160,12 @@ void Engine::ufb_one_event(const uint32_t b, const uint32_t s, int64_t &tree_ind
   bool accept = false;
   if (s < bs) accept = true;                                    // rell > boot_logl + epsilon (:3686)
   else if (s == bs) {                                           // rell > boot_logl - epsilon: tie, draw (:3687-3688)
-    u.draws++;
+    ++*(dc.draws ? dc.draws : &u.draws);
     accept = tie_draw() <= 1.0 / (double)(u.boot_counts[b] + 1);
   }
   if (accept && u.cut_btrees) u.boot_orig[b] = u.cur_logl_now;                  // :3716-3718
   if (accept && dc.on) {
+    // (deferred: nothing of the state a pipelined climb's worker thread owns -- refs, boot_trees, store, topo_index -- is touched)
     u.log.push_back(UfbState::LogEntry{b, cand_code, tree_index, dc.cur_plan});
     *dc.log_open = true;
     if (dc.moot && cand_code != 0xFFFFFFFFu && dc.moot->flag[b]) { dc.moot->flag[b] = 0; dc.moot->n_set--; }   // (it points elsewhere now)
@@ -188,9 +190,10 @@ void Engine::ufb_one_event(const uint32_t b, const uint32_t s, int64_t &tree_ind
 // One tree arriving at saveCurrentTree with length cur_len: its index in treels_logl, or -1 when nothing is booked.
 // Default: the cut-off test, then a new index (iqtree.cpp:3343-3348).  -storetrees: looked up by topology first
 // (:3302-3341; key(cand_code) = its canonical form); one met before is skipped unless the length improved on the recorded one,
-// and then it goes on under its old index without the cut-off test.
+// and then it goes on under its old index without the cut-off test.  grow_refs = false: a pipelined climb's worker thread owns the
+// reference counts and sizes them itself.
 template <class KeyFn>
-int64_t Engine::ufb_book_tree(uint32_t cur_len, bool passes_cut, uint32_t cand_code, bool store_trees, KeyFn key)
+int64_t Engine::ufb_book_tree(uint32_t cur_len, bool passes_cut, uint32_t cand_code, bool store_trees, KeyFn key, bool grow_refs)
 {
   UfbState &u = *ufb_;
   if (store_trees) {
@@ -206,8 +209,205 @@ int64_t Engine::ufb_book_tree(uint32_t cur_len, bool passes_cut, uint32_t cand_c
     u.topo_index.emplace(k, (int64_t)u.treels.size());
   } else if (!passes_cut) return -1;
   u.treels.push_back(cur_len);
-  u.refs.push_back(0);
+  if (grow_refs) u.refs.push_back(0);
   return (int64_t)u.treels.size() - 1;
+}
+
+// ---- one prune-node visit of a tracked climb ---------------------------------------------------------------------------------
+// What a visit books around the two rules of spr_rule.hpp, in the reference's order: the current tree first (saveCurrentTree in
+// front of the insertion tests, sprparsimony.cpp:2285-2289), every candidate before the tie rule sees it (:2163-2166), the
+// cut-off test or the ratchet gate and the stale length with each booking, the pending trees or the log closed behind the scan,
+// then the sweep's accept rule.  Every draw comes from one stream, so this order IS the behaviour.
+// The three tracked loops fill in this state per batch and derive from it what differs between them:
+//   bool next(const ScanPlan &, Cursor &, Cand &)        the visit's insertion tests in the reference's order
+//   uint32_t stale_len(uint32_t idx, uint32_t home)      ratchet: a booked candidate's length on the original alignment
+//   bool name_move(const ScanPlan &, long sel)           the selected move's records into insert_rec_ / remove_rec_
+struct Engine::UfbVisit {
+  struct Cand { size_t c; uint32_t idx, mp, home; };     // its number in the visit, output index, length, home index of its part
+  struct Cursor { int pi = 0, k = 0; size_t c = 0; };    // where next() stands in the visit (a local of the replay: it stays in registers)
+  Engine *e = nullptr;
+  // the batch: the scan's costs, the events in replay order and how far they have been read
+  const uint32_t *out = nullptr;
+  const std::vector<UfbEvent> *events = nullptr;
+  size_t ep = 0;
+  // what is booked: the cut-off (none_pass, mp_max), the ratchet gate (product_*: the batch has the REPS it reads), -storetrees
+  bool ratchet = false, store_trees = false, none_pass = false, product_self = true, product_cand = true;
+  uint32_t mp_max = UINT32_MAX;
+  // the update rule: deferred (acceptances go to the log) or in place; the current tree's bookings from R_T on the host (h_rt) or
+  // from events; self_row: the current tree has a cost and a product row of its own at every visit (asymmetric cost matrix)
+  bool defer = false, host_self = true, self_row = false;
+  const int32_t *h_rt = nullptr;
+  bool *log_open = nullptr;
+  SelfMoot *moot = nullptr;
+  // a pipelined climb: worker_books = its log goes to a worker thread (option ufb_thread), which then owns refs, boot_trees, store
+  // and topo_index; draws = its own counter, with or without that thread (null: UfbState::draws)
+  bool worker_books = false;
+  uint64_t *draws = nullptr;
+  int32_t cur_plan = 0;
+  // the visit's outcome
+  long sel = -1;
+  uint32_t sel_idx = 0, sel_home = 0;
+  bool accept = false;
+  std::vector<int32_t> mh_bk;                      // a candidate's topology and its canonical form
+  std::string mh_key;
+
+  uint32_t stale_len(uint32_t, uint32_t) const { return 0; }
+  bool name_move(const ScanPlan &pl, long s)
+  {
+    e->insert_rec_ = e->candidate_record(pl, (size_t)s);
+    e->remove_rec_ = s < pl.n_p ? pl.rec : e->back_[pl.rec];
+    return true;
+  }
+};
+
+// the insertion tests of a device-walked plan: part after part, idx = part_off + k, mp = base + out[idx], home = part_off + part_cnt
+struct Engine::UfbPartsVisit : Engine::UfbVisit {
+  // under a plain cut-off most insertion tests change nothing: not booked (above the cut-off) and longer than the best tree so far
+  // (no counter, no draw) -- on to the next one that is either (best_ only falls while the block is read)
+  bool skip_ahead = false;
+  bool next(const ScanPlan &pl, Cursor &at, Cand &cd) const
+  {
+    for (; at.pi < pl.n_parts; at.pi++, at.k = 0) {
+      const int cnt = pl.part_cnt[at.pi];
+      if (skip_ahead && at.k < cnt) {
+        const uint32_t lim_len = std::max(none_pass ? 0u : mp_max, e->best_);
+        const int k2 = lim_len >= pl.base ? first_le(out + pl.part_off[at.pi], at.k, cnt, lim_len - pl.base) : cnt;
+        at.c += (size_t)(k2 - at.k);
+        at.k = k2;
+      }
+      if (at.k < cnt) {
+        const uint32_t idx = pl.part_off[at.pi] + (uint32_t)at.k++;
+        cd = Cand{at.c++, idx, pl.base + out[idx], pl.part_off[at.pi] + (uint32_t)cnt};
+        return true;
+      }
+    }
+    return false;
+  }
+};
+
+template <class Loop>
+int Engine::ufb_replay_visit(const ScanPlan &pl, Loop &L, uint32_t randomMP, unsigned &iter_hits)
+{
+  UfbState &u = *ufb_;
+  if (tie_mode_ == MPF_TIE_RANDOM) {
+    insert_rec_ = remove_rec_ = -1;
+    hits_ = 1;
+  }
+  L.sel = -1;
+  L.accept = false;
+  auto draw = [&] { return tie_draw(); };
+  // treels.find(tree_str) / treels[tree_str] = tree_index (iqtree.cpp:3500-3514, :3689-3707): a topology that some sample
+  // accepted before keeps the index of that first tree
+  auto topology_key = [&](uint32_t cand_code) -> const std::string & {
+    if (cand_code == 0xFFFFFFFFu) {
+      if (u.self_key_epoch != (uint64_t)topo_epoch_) { canonical_topology(back_, u.self_key); u.self_key_epoch = (uint64_t)topo_epoch_; }
+      return u.self_key;
+    }
+    ufb_candidate_topology(cand_code < (uint32_t)pl.n_p ? pl.rec : back_[pl.rec], candidate_record(pl, (size_t)cand_code), L.mh_bk);
+    canonical_topology(L.mh_bk, L.mh_key);
+    return L.mh_key;
+  };
+  auto lookup_topology = [&](int64_t tree_index, uint32_t cand_code) -> int64_t {
+    const double tl = now_ms();
+    const int64_t ti = u.topo_index.emplace(topology_key(cand_code), tree_index).first->second;
+    u.t_lookup += now_ms() - tl;
+    u.lookups++;
+    return ti;
+  };
+  uint64_t *draws = L.draws ? L.draws : &u.draws;
+  const UfbDeferCtx dctx{L.defer, L.cur_plan, L.log_open, L.moot, draws};
+  // the update rule of one booked tree over the samples whose events name output index idx
+  auto replay_events = [&](uint32_t idx, int64_t tree_index, uint32_t cand_code) {
+    const std::vector<UfbEvent> &ev = *L.events;
+    while (L.ep < ev.size() && ev[L.ep].idx < idx) L.ep++;
+    bool looked_up = L.store_trees;                // (-storetrees: tree_str is set at the top, no lookup per sample)
+    for (; L.ep < ev.size() && ev[L.ep].idx == idx; L.ep++) ufb_one_event(ev[L.ep].b, ev[L.ep].s, tree_index, looked_up, cand_code, lookup_topology, dctx);
+  };
+  // one tree of length len arriving at saveCurrentTree.  A re-weighted (ratchet) climb is filtered by the length booked last
+  // (iqtree.cpp:3283-3295 then :3343): a tree that fails leaves _pattern_pars as it is, so every later tree of the climb fails too
+  // (-storetrees: unless a known topology gets in past the cut-off)
+  // (copies: the bookings below write through pointers the compiler cannot tell from L's fields)
+  const bool ratchet = L.ratchet, store_trees = L.store_trees, none_pass = L.none_pass, grow_refs = !L.worker_books;
+  const uint32_t mp_max = L.mp_max;
+  auto book = [&](uint32_t len, bool product, uint32_t cand_code) -> int64_t {
+    bool pass;
+    if (!ratchet) pass = !none_pass && len <= mp_max;
+    else {
+      pass = (store_trees || !u.gate_closed) && product && !none_pass && u.stale_len <= mp_max;
+      if (!pass) u.gate_closed = true;
+    }
+    const uint32_t cur_len = ratchet ? u.stale_len : len;
+    u.cur_logl_now = -(int32_t)cur_len;
+    return ufb_book_tree(cur_len, pass, cand_code, store_trees, topology_key, grow_refs);
+  };
+  if (pl.self_idx >= 0) {
+    // rearrangeParsimony's evaluateParsimony(p) + pllSaveCurrentTreeSprParsimony (sprparsimony.cpp:2285-2289): the current tree,
+    // once per prune node and before any of its insertion tests
+    const uint32_t self_idx = (uint32_t)pl.self_idx;
+    int64_t tree_index = book(L.self_row ? L.out[self_idx] : randomMP, L.product_self, 0xFFFFFFFFu);
+    if (tree_index >= 0) {
+      // it scores R_T[b] for every sample: no device events for its slots where the host has R_T (they would be B per visit, 2.0e6
+      // per move-less C3 sweep, all to be copied and ordered) -- the host offers it to every sample in order
+      if (!L.host_self) replay_events(self_idx, tree_index, 0xFFFFFFFFu);
+      else if (L.defer) ufb_self_default(L.h_rt, tree_index, L.cur_plan, *L.log_open, *draws, L.moot);
+      else {
+        bool looked_up = L.store_trees;
+        for (int c2 = 0; c2 < u.Bl; c2++) ufb_one_event((uint32_t)u.ids[(size_t)c2], (uint32_t)L.h_rt[c2], tree_index, looked_up, 0xFFFFFFFFu, lookup_topology, dctx);
+      }
+      if (L.ratchet) u.stale_len = L.self_row ? L.stale_len(self_idx, self_idx) : u.rt_orig;     // _pattern_pars now holds the current tree
+    }
+  }
+  const bool product_cand = L.product_cand;
+  typename Loop::Cursor at;
+  typename Loop::Cand cd, taken{0, 0, 0, 0};
+  long sel = -1;
+  while (L.next(pl, at, cd)) {
+    const int64_t tree_index = book(cd.mp, product_cand, (uint32_t)cd.c);        // saveCurrentTree(-mp), sprparsimony.cpp:2163-2166
+    if (tree_index >= 0) {
+      replay_events(cd.idx, tree_index, (uint32_t)cd.c);
+      // pllComputePatternParsimony (iqtree.cpp:3365) has now refreshed _pattern_pars for THIS candidate: its length on the
+      // original alignment is what the next call will see
+      if (ratchet) u.stale_len = L.stale_len(cd.idx, cd.home);
+    }
+    if (sprrule::offer(tie_mode_, cd.mp, best_, hits_, draw)) { sel = (long)cd.c; taken = cd; }
+  }
+  L.sel = sel; L.sel_idx = taken.idx; L.sel_home = taken.home;
+  if (L.sel >= 0 && !L.name_move(pl, L.sel)) return MPF_E_STATE;
+  // topologies of the trees accepted during this scan that some sample still points to, or the end-of-prune-node mark of the log
+  if (!L.defer) ufb_flush_pending(pl);
+  else if (*L.log_open) { u.log.push_back(UfbState::LogEntry{0xFFFFFFFFu, 0u, 0, L.cur_plan}); *L.log_open = false; }
+  L.accept = sprrule::accept(tie_mode_, best_, randomMP, iter_hits, remove_rec_ >= 0 && insert_rec_ >= 0, draw);
+  if (L.accept && L.sel < 0) { set_error("online UFBoot: accepted move without a candidate of this prune node"); return MPF_E_STATE; }
+  return MPF_OK;
+}
+
+// ---- the batch scaffolding of the tracked loops ------------------------------------------------------------------------------
+// the first prune node of a batch with a strictly better candidate than the current tree ends the batch for certain (a tie may end
+// it earlier): its number, or np - 1
+static inline int ufb_first_better(const std::vector<ScanPlan> &plans, int np, const uint32_t *out, uint32_t randomMP)
+{
+  for (int j = 0; j < np; j++) {
+    const ScanPlan &pl = plans[(size_t)j];
+    uint32_t m = UINT32_MAX;
+    for (int pi = 0; pi < pl.n_parts; pi++)
+      for (int k = 0; k < pl.part_cnt[pi]; k++) m = std::min(m, out[pl.part_off[pi] + (uint32_t)k]);
+    if (m != UINT32_MAX && pl.base + m < randomMP) return j;
+  }
+  return np - 1;
+}
+
+// what lies behind that prune node is never replayed: one past the last output index in front of it (n_idx: the whole batch)
+static inline uint32_t ufb_index_cut(const std::vector<ScanPlan> &plans, int np, const uint32_t *out, uint32_t randomMP, uint32_t n_idx)
+{
+  const int js = ufb_first_better(plans, np, out, randomMP);
+  if (js == np - 1) return n_idx;
+  uint32_t cut = 0;
+  for (int j = 0; j <= js; j++) {
+    const ScanPlan &pl = plans[(size_t)j];
+    if (pl.self_idx >= 0) cut = std::max(cut, (uint32_t)pl.self_idx + 1u);
+    for (int pi = 0; pi < pl.n_parts; pi++) cut = std::max(cut, pl.part_off[pi] + (uint32_t)pl.part_cnt[pi] + 1u);
+  }
+  return cut;
 }
 
 }  // namespace mpf

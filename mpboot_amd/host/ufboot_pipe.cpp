@@ -13,6 +13,9 @@ namespace mpf {
 // batch (all draws in the reference's order, one stream) then runs beside the next batch's device work and must arrive at the
 // very decision taken early (checked).  Where a draw decides (ties with the current tree, two cheapest candidates) the batch is
 // taken as before: replay first, then move.
+// Shared with the other tracked loops (host/ufboot_common.hpp): the replay of a prune-node visit -- here with the deferred default
+// rule, nothing filtered, and the tracker's deferred state left to the worker thread --, the end of a batch from its costs and the
+// exchange of a sharded run.  This loop's own: the pipeline, and the checks of the replay against a decision taken early.
 int Engine::spr_sweeps_ufboot_pipe(int mintrav, int maxtrav, uint32_t randomMP, uint32_t *final_score)
 {
   UfbState &u = *ufb_;
@@ -113,6 +116,20 @@ int Engine::spr_sweeps_ufboot_pipe(int mintrav, int maxtrav, uint32_t randomMP, 
     }
   } abort_guard{this, &worker};
   uint64_t n_draws = 0;                            // (added to the tracker's counter at the end: its word shares a cache line with the worker's)
+  // what this loop puts into the shared visit replay (ufb_replay_visit, host/ufboot_common.hpp): device-walked parts, and a move
+  // already taken from the costs -- it was named before it was applied, and the replay must select it where the costs said so
+  struct Visit : UfbPartsVisit {
+    bool early = false, early_here = false;
+    int ins = -1, rem = -1;
+    bool name_move(const ScanPlan &pl, long s)
+    {
+      if (early_here) { e->insert_rec_ = ins; e->remove_rec_ = rem; return true; }
+      if (early) { set_error("online UFBoot: the replay selects a candidate where the costs said none is"); return false; }
+      return UfbPartsVisit::name_move(pl, s);
+    }
+  } V;
+  V.e = this; V.events = &events; V.log_open = &log_open;
+  V.defer = true; V.host_self = host_self; V.worker_books = use_worker; V.draws = &n_draws;
 
   // plan + enqueue the whole chain of the batch [i, i + b): refresh, masked scan, mid (C <- 0, self slots, scan results to the host),
   // product, extraction (events and R_T to the host)
@@ -325,25 +342,7 @@ int Engine::spr_sweeps_ufboot_pipe(int mintrav, int maxtrav, uint32_t randomMP, 
       double t1 = now_ms();
       u.t_dev += t1 - t0;
       // what lies behind the batch's certain end is never replayed: dropped before the sort
-      uint32_t idx_cut = B.n_idx;
-      {
-        int js = B.np - 1;
-        for (int j = 0; j < B.np; j++) {
-          const ScanPlan &pl = B.plans[(size_t)j];
-          uint32_t m = UINT32_MAX;
-          for (int pi = 0; pi < pl.n_parts; pi++)
-            for (int k = 0; k < pl.part_cnt[pi]; k++) m = std::min(m, out[pl.part_off[pi] + (uint32_t)k]);
-          if (m != UINT32_MAX && pl.base + m < randomMP) { js = j; break; }
-        }
-        if (js < B.np - 1) {
-          idx_cut = 0;
-          for (int j = 0; j <= js; j++) {
-            const ScanPlan &pl = B.plans[(size_t)j];
-            if (pl.self_idx >= 0) idx_cut = std::max(idx_cut, (uint32_t)pl.self_idx + 1u);
-            for (int pi = 0; pi < pl.n_parts; pi++) idx_cut = std::max(idx_cut, pl.part_off[pi] + (uint32_t)pl.part_cnt[pi] + 1u);
-          }
-        }
-      }
+      const uint32_t idx_cut = ufb_index_cut(B.plans, B.np, out, randomMP, B.n_idx);
       if (B.device && u.p_flag_s[B.par].p[2] != idx_cut) { set_error("online UFBoot: the device's end of the batch differs from the host's"); return MPF_E_STATE; }
       {
         const UfbEvent *src = u.p_ev[B.par].p;
@@ -363,14 +362,7 @@ int Engine::spr_sweeps_ufboot_pipe(int mintrav, int maxtrav, uint32_t randomMP, 
                   if ((uint32_t)u.p_rt[B.par].p[c2] <= u.boot_score[(size_t)u.ids[(size_t)c2]])
                     events.push_back(UfbEvent{(uint32_t)B.plans[(size_t)jj].self_idx, (uint32_t)u.ids[(size_t)c2], (uint32_t)u.p_rt[B.par].p[c2]});
           n_ev = (uint32_t)events.size();
-          const mpf_ufb_event *all = nullptr;
-          uint32_t n_all_ev = 0;
-          if (u.exchange(u.exchange_arg, exchange_tag++, reinterpret_cast<const mpf_ufb_event *>(events.data()), (uint32_t)events.size(), &all, &n_all_ev) != 0) {
-            set_error("online UFBoot: event exchange failed (ranks out of step?)");
-            return MPF_E_STATE;
-          }
-          const UfbEvent *pa = reinterpret_cast<const UfbEvent *>(all);
-          events.assign(pa, pa + n_all_ev);
+          { int rc = ufb_gather_events(events, exchange_tag++); if (rc) return rc; }
           uint32_t n_keys = B.n_idx;
           for (int jj = 0; jj < B.np; jj++) n_keys = std::max(n_keys, (uint32_t)(B.plans[(size_t)jj].self_idx + 1));
           sort_events(events, ev_tmp, ev_count, n_keys, (uint32_t)u.B);
@@ -408,94 +400,20 @@ int Engine::spr_sweeps_ufboot_pipe(int mintrav, int maxtrav, uint32_t randomMP, 
       }
       t0 = now_ms();
       u.t_sort += t0 - t1;
-      // ---- replay in the reference's order (Engine::spr_sweeps_ufboot's, reduced to the default rule without a cut-off)
-      const int32_t *h_rt = u.p_rt[B.par].p;
-      size_t ep = 0;
+      // ---- replay in the reference's order (ufb_replay_visit): the default rule, deferred, nothing filtered
+      V.out = out; V.h_rt = u.p_rt[B.par].p; V.ep = 0;
+      V.early = early; V.ins = d.ins; V.rem = d.rem;
       bool moved = false;
       int j = i;
       for (; j <= B.hi && !moved; j++) {
-        const ScanPlan &pl = B.plans[(size_t)(j - i)];
-        const int32_t cur_plan = (int32_t)(j - i);
-        if (tie_mode_ == MPF_TIE_RANDOM) {
-          insert_rec_ = remove_rec_ = -1;
-          hits_ = 1;
-        }
-        long sel = -1;
-        uint32_t sel_idx = 0, sel_home = 0;
-        size_t c = 0;
-        auto one_event = [&](const uint32_t b, const uint32_t s, const int64_t tree_index, const uint32_t cand_code) {
-          uint32_t &bs = u.boot_score[b];
-          bool accept = false;
-          if (s < bs) accept = true;                                    // rell > boot_logl + epsilon (iqtree.cpp:3686)
-          else if (s == bs) {                                           // rell > boot_logl - epsilon: tie, draw (:3687-3688)
-            n_draws++;
-            accept = tie_draw() <= 1.0 / (double)(u.boot_counts[b] + 1);
-          }
-          if (accept) {
-            u.log.push_back(UfbState::LogEntry{b, cand_code, tree_index, cur_plan});
-            log_open = true;
-            if (u.cut_btrees) u.boot_orig[b] = u.cur_logl_now;                          // :3716-3718
-            if (s < bs) { u.boot_counts[b] = 1; bs = s; }              // :3710-3719
-          }
-          if (s == bs) u.boot_counts[b]++;                              // :3728-3730
-        };
-        auto book = [&](uint32_t len) -> int64_t {                      // iqtree.cpp:3343-3348 without a cut-off
-          u.treels.push_back(len);
-          if (!use_worker) u.refs.push_back(0);                         // (the worker sizes the reference counts itself)
-          return (int64_t)u.treels.size() - 1;
-        };
-        if (pl.self_idx >= 0) {
-          // the current tree, once per prune node and before its insertion tests (sprparsimony.cpp:2285-2289)
-          u.cur_logl_now = -(int32_t)randomMP;
-          const int64_t tree_index = book(randomMP);
-          if (host_self) {
-            ufb_self_default(h_rt, tree_index, cur_plan, log_open, n_draws);
-          } else {
-            const uint32_t idx = (uint32_t)pl.self_idx;
-            while (ep < events.size() && events[ep].idx < idx) ep++;
-            for (; ep < events.size() && events[ep].idx == idx; ep++) one_event(events[ep].b, events[ep].s, tree_index, 0xFFFFFFFFu);
-          }
-        }
-        for (int pi = 0; pi < pl.n_parts; pi++) {
-          const uint32_t home = pl.part_off[pi] + (uint32_t)pl.part_cnt[pi];
-          for (int k = 0; k < pl.part_cnt[pi]; k++, c++) {
-            const uint32_t idx = pl.part_off[pi] + (uint32_t)k;
-            const uint32_t mp = pl.base + out[idx];
-            u.cur_logl_now = -(int32_t)mp;
-            const int64_t tree_index = book(mp);                        // saveCurrentTree(-mp), sprparsimony.cpp:2163-2166
-            while (ep < events.size() && events[ep].idx < idx) ep++;
-            for (; ep < events.size() && events[ep].idx == idx; ep++) one_event(events[ep].b, events[ep].s, tree_index, (uint32_t)c);
-            if (tie_mode_ == MPF_TIE_RANDOM) {                          // testInsertParsimony's tie rule (:2168-2176)
-              if (mp < best_) hits_ = 1;
-              else if (mp == best_) hits_++;
-              if (mp < best_ || (mp == best_ && tie_draw() <= 1.0 / (double)hits_)) { best_ = mp; sel = (long)c; sel_idx = idx; sel_home = home; }
-            } else if (mp < best_) {
-              best_ = mp; sel = (long)c; sel_idx = idx; sel_home = home;
-            }
-          }
-        }
-        const bool early_here = early && d.moved && (j - i) == d.j;
-        if (sel >= 0) {
-          if (early_here) { insert_rec_ = d.ins; remove_rec_ = d.rem; }          // (named before the move was applied)
-          else if (early) { set_error("online UFBoot: the replay selects a candidate where the costs said none is"); return MPF_E_STATE; }
-          else {
-            insert_rec_ = candidate_record(pl, (size_t)sel);
-            remove_rec_ = sel < pl.n_p ? pl.rec : back_[pl.rec];
-          }
-        }
-        if (log_open) { u.log.push_back(UfbState::LogEntry{0xFFFFFFFFu, 0u, 0, cur_plan}); log_open = false; }
-        bool accept;
-        if (tie_mode_ == MPF_TIE_RANDOM) {                              // :3306-3311
-          if (best_ == randomMP) iter_hits++;
-          if (best_ < randomMP) iter_hits = 1;
-          accept = (best_ < randomMP || (best_ == randomMP && tie_draw() <= 1.0 / (double)iter_hits)) &&
-                   remove_rec_ >= 0 && insert_rec_ >= 0;
-        } else {
-          accept = best_ < randomMP;
-        }
+        V.cur_plan = (int32_t)(j - i);
+        const bool early_here = V.early_here = early && d.moved && (j - i) == d.j;
+        { int rc = ufb_replay_visit(B.plans[(size_t)(j - i)], V, randomMP, iter_hits); if (rc) return rc; }
+        const bool accept = V.accept;
+        const long sel = V.sel;
+        const uint32_t sel_idx = V.sel_idx, sel_home = V.sel_home;
         if (early && accept != early_here) { set_error("online UFBoot: the replay's decision differs from the one taken from the costs"); return MPF_E_STATE; }
         if (accept) {
-          if (sel < 0) { set_error("online UFBoot: accepted move without a candidate of this prune node"); return MPF_E_STATE; }
           if (early) {
             if (sel != d.sel || best_ != d.score) { set_error("online UFBoot: the replay's move differs from the one taken from the costs"); return MPF_E_STATE; }
           } else {
@@ -550,12 +468,7 @@ int Engine::spr_sweeps_ufboot_pipe(int mintrav, int maxtrav, uint32_t randomMP, 
   if (u.refs.size() < u.treels.size()) u.refs.resize(u.treels.size(), 0);
   if (recording.f) books::rec::write_state(recording.f, 'E', u, u.treels.size());
   climb_finished(total);
-  if (u.exchange) {
-    // closing handshake: a rank that took another path would be in the middle of a batch here
-    const mpf_ufb_event *all = nullptr;
-    uint32_t n_all_ev = 0;
-    if (u.exchange(u.exchange_arg, 0xFFFFFFFFu, nullptr, 0, &all, &n_all_ev) != 0) { set_error("online UFBoot: ranks out of step at the end of the climb"); return MPF_E_STATE; }
-  }
+  { int rc = ufb_close_exchange(); if (rc) return rc; }
   if (final_score) *final_score = randomMP;
   abort_guard.ok = true;
   return MPF_OK;

@@ -52,6 +52,7 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
       uint32_t best = randomMP;
       TieRng rng;
       rng.seed(tie_seeds ? tie_seeds[b] : b);
+      auto draw = [&] { return rng.next(); };
       uint64_t iter_hits = 1;
       uint32_t done_visits = 0;                             // visits [0, done_visits) of the sweep are behind us
       bool moved = false;
@@ -65,21 +66,9 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
         // this visit: testInsertParsimony's rule over its events (:2168-2176), bestTreeScoreHits = 1 at its start
         uint64_t hits = 1;
         bool sel = false;
-        for (; ep < all.size() && all[ep].col == (uint32_t)c && all[ep].visit == v; ep++) {
-          const uint32_t mp = all[ep].s;
-          if (mp > best) continue;
-          if (mp < best) hits = 1;
-          else hits++;
-          bool take = mp < best;
-          if (!take) take = rng.next() <= 1.0 / (double)hits;
-          if (take) { best = mp; sel = true; }
-        }
-        bool accept = best < randomMP;
-        if (!accept) {                                      // best == randomMP
-          iter_hits++;
-          accept = rng.next() <= 1.0 / (double)iter_hits;
-        }
-        if (accept && sel) { moved = true; move_visit = v; }
+        for (; ep < all.size() && all[ep].col == (uint32_t)c && all[ep].visit == v; ep++)
+          if (sprrule::offer(MPF_TIE_RANDOM, all[ep].s, best, hits, draw)) sel = true;
+        if (sprrule::accept(MPF_TIE_RANDOM, best, randomMP, iter_hits, sel, draw)) { moved = true; move_visit = v; }
         done_visits = v + 1u;
       }
       while (ep < all.size() && all[ep].col == (uint32_t)c) ep++;

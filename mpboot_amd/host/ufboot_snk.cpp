@@ -8,8 +8,10 @@ namespace mpf {
 // minima the evaluate has just taken.  The scan writes them for every insertion test (k_snk_scan, 16 bits each), k_vals_planes
 // slices them into bit planes and REPS = sum_k 2^k (plane k x weights) on the matrix cores; the current tree's own row is
 // multiplied along with every batch and serves as the "home" row of the event formula, so that a candidate's score is its own
-// product row and the current tree's slots score R_T.  Scans are host-planned (as every weighted scan), everything else --
-// cut-off filter, ratchet rule, update rules, replay order -- is the code path of spr_sweeps_ufboot.
+// product row and the current tree's slots score R_T.  Scans are host-planned (as every weighted scan).  Shared with the other
+// tracked loops (host/ufboot_common.hpp): the replay of a prune-node visit -- cut-off filter, ratchet gate, update rules, the two
+// SPR rules, in the reference's order -- and the exchange of a sharded run; this loop's own: the batch's device work, a plan's
+// candidate list, and a booked tree's length on the original alignment straight from its product row.
 int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, uint32_t *final_score)
 {
   UfbState &u = *ufb_;
@@ -29,8 +31,7 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
   std::vector<UfbEvent> events, ev_tmp;
   std::vector<uint32_t> ev_count, small;
   std::vector<uint2> hinfo;
-  std::vector<int32_t> mh_bk, lcol;
-  std::string mh_key;
+  std::vector<int32_t> lcol;
   const bool ratchet = u.ratchet;
   const bool store_trees = u.store_trees;          // -storetrees (iqtree.cpp:3302-3346)
   // (an asymmetric matrix gives the CURRENT tree another length and another row at every prune node's visit -- it is evaluated at
@@ -40,6 +41,20 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
   const int oc = u.Bl;
   if (ratchet) u.gate_closed = false;
   bool stale_init = false;                         // ratchet: _pattern_pars of the climb's start tree, known after the first product
+  // (no deferred mode on this engine; asym: the current tree's bookings have the visit's slot as their cost and their row)
+  struct Visit : UfbVisit {
+    const std::vector<int32_t> *lcol = nullptr;
+    bool next(const ScanPlan &pl, Cursor &at, Cand &cd) const
+    {
+      if (at.c >= pl.cands.size()) return false;
+      const uint32_t idx = pl.cands[at.c].out;
+      cd = Cand{at.c++, idx, out[idx], 0u};
+      return true;
+    }
+    uint32_t stale_len(uint32_t idx, uint32_t) const { return (uint32_t)(*lcol)[(size_t)idx]; }
+  } V;
+  V.e = this; V.events = &events; V.lcol = &lcol;
+  V.ratchet = ratchet; V.store_trees = store_trees; V.host_self = host_self; V.self_row = asym;
   do {
     startMP = randomMP;
     node_rectifier();
@@ -171,17 +186,7 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
         }
         events.assign(u.h_ev.p, u.h_ev.p + n_ev);
         for (UfbEvent &ev : events) ev.b = (uint32_t)u.ids[(size_t)ev.b];
-        if (u.exchange) {
-          // sample-sharded run: every rank replays the events of all ranks (one all-gather per batch)
-          const mpf_ufb_event *all = nullptr;
-          uint32_t n_all_ev = 0;
-          if (u.exchange(u.exchange_arg, exchange_tag++, reinterpret_cast<const mpf_ufb_event *>(events.data()), (uint32_t)events.size(), &all, &n_all_ev) != 0) {
-            set_error("online UFBoot: event exchange failed (ranks out of step?)");
-            return MPF_E_STATE;
-          }
-          const UfbEvent *pa = reinterpret_cast<const UfbEvent *>(all);
-          events.assign(pa, pa + n_all_ev);
-        }
+        if (u.exchange) { int rc2 = ufb_gather_events(events, exchange_tag++); if (rc2) return rc2; }
         sort_events(events, ev_tmp, ev_count, std::max<uint32_t>(n_idx, 1u), (uint32_t)u.B);
         u.events += n_ev;
         if (ratchet) {
@@ -191,114 +196,13 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
         }
       }
       // ---- host replay in the reference's order
-      size_t ep = 0;
+      V.out = out; V.h_rt = u.h_rt.p; V.ep = 0;
+      V.none_pass = none_pass; V.mp_max = mp_max; V.product_self = V.product_cand = have_C;
       bool moved = false;
       int j = i;
       for (; j <= hi && !moved; j++) {
-        const ScanPlan &pl = plans[(size_t)(j - i)];
-        if (tie_mode_ == MPF_TIE_RANDOM) {
-          insert_rec_ = remove_rec_ = -1;
-          hits_ = 1;
-        }
-        long sel = -1;
-        auto topology_key = [&](uint32_t cand_code) -> const std::string & {
-          if (cand_code == 0xFFFFFFFFu) {
-            if (u.self_key_epoch != (uint64_t)topo_epoch_) { canonical_topology(back_, u.self_key); u.self_key_epoch = (uint64_t)topo_epoch_; }
-            return u.self_key;
-          }
-          ufb_candidate_topology(cand_code < (uint32_t)pl.n_p ? pl.rec : back_[pl.rec], pl.cands[(size_t)cand_code].q, mh_bk);
-          canonical_topology(mh_bk, mh_key);
-          return mh_key;
-        };
-        auto cand_topology_key = [&](uint32_t cand_code, int64_t tree_index) -> int64_t {
-          return u.topo_index.emplace(topology_key(cand_code), tree_index).first->second;
-        };
-        // the update rule of one booked tree for one sample (b, score s): shared by the events the device extracted and by the
-        // current tree's own bookings, which the host walks through itself
-        const UfbDeferCtx dctx{};                   // (no deferred mode on this engine)
-        auto one_event = [&](const uint32_t b, const uint32_t s, int64_t &tree_index, bool &looked_up, const uint32_t cand_code) {
-          ufb_one_event(b, s, tree_index, looked_up, cand_code, [&](int64_t ti, uint32_t cc) { return cand_topology_key(cc, ti); }, dctx);
-        };
-        auto replay_events = [&](uint32_t idx, int64_t tree_index, uint32_t cand_code) {
-          while (ep < events.size() && events[ep].idx < idx) ep++;
-          bool looked_up = store_trees;              // (-storetrees: tree_str is set at the top, no lookup per sample)
-          for (; ep < events.size() && events[ep].idx == idx; ep++) one_event(events[ep].b, events[ep].s, tree_index, looked_up, cand_code);
-        };
-        // the current tree scores R_T[b] for every sample: no device events for its slots (they would be B per prune-node visit,
-        // 2.0e6 per move-less C3 sweep, all to be copied and ordered) -- the host has R_T and offers it to every sample in order
-        auto replay_self = [&](int64_t tree_index) {
-          bool looked_up = store_trees;
-          for (int c2 = 0; c2 < u.Bl; c2++) one_event((uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2], tree_index, looked_up, 0xFFFFFFFFu);
-        };
-        // one tree arriving at saveCurrentTree with length cur_len: its index in treels_logl, or -1 when nothing is booked.
-        // Default: the cut-off test, then a new index (iqtree.cpp:3343-3348).  -storetrees: looked up by topology first
-        // (:3302-3341); one met before is skipped unless the length improved on the recorded one, and then it goes on under
-        // its old index without the cut-off test.
-        auto book_tree = [&](uint32_t cur_len, bool passes_cut, uint32_t cand_code) -> int64_t {
-          return ufb_book_tree(cur_len, passes_cut, cand_code, store_trees, topology_key);
-        };
-        if (pl.self_idx >= 0) {
-          const uint32_t self_len = asym ? out[(size_t)pl.self_idx] : randomMP;       // (:2285: mp of evaluateParsimony(p))
-          bool pass;
-          if (!ratchet) pass = !none_pass && self_len <= mp_max;
-          else {
-            pass = (store_trees || !u.gate_closed) && have_C && !none_pass && u.stale_len <= mp_max;
-            if (!pass) u.gate_closed = true;
-          }
-          u.cur_logl_now = -(int32_t)(ratchet ? u.stale_len : self_len);
-          const int64_t tree_index = book_tree(ratchet ? u.stale_len : self_len, pass, 0xFFFFFFFFu);
-          if (tree_index >= 0) {
-            if (host_self) replay_self(tree_index); else replay_events((uint32_t)pl.self_idx, tree_index, 0xFFFFFFFFu);
-            if (ratchet) u.stale_len = asym ? (uint32_t)lcol[(size_t)pl.self_idx] : u.rt_orig;
-          }
-        }
-        for (size_t c = 0; c < pl.cands.size(); c++) {
-          const uint32_t idx = pl.cands[c].out;
-          const uint32_t mp = out[idx];
-          bool pass;
-          if (!ratchet) pass = !none_pass && mp <= mp_max;
-          else {
-            pass = (store_trees || !u.gate_closed) && have_C && !none_pass && u.stale_len <= mp_max;
-            if (!pass) u.gate_closed = true;
-          }
-          u.cur_logl_now = -(int32_t)(ratchet ? u.stale_len : mp);
-          const int64_t tree_index = book_tree(ratchet ? u.stale_len : mp, pass, (uint32_t)c);
-          if (tree_index >= 0) {
-            replay_events(idx, tree_index, (uint32_t)c);
-            if (ratchet) u.stale_len = (uint32_t)lcol[(size_t)idx];
-          }
-          if (tie_mode_ == MPF_TIE_RANDOM) {
-            if (mp < best_) hits_ = 1;
-            else if (mp == best_) hits_++;
-            if (mp < best_ || (mp == best_ && tie_draw() <= 1.0 / (double)hits_)) { best_ = mp; sel = (long)c; }
-          } else if (mp < best_) {
-            best_ = mp; sel = (long)c;
-          }
-        }
-        if (sel >= 0) {
-          insert_rec_ = pl.cands[(size_t)sel].q;
-          remove_rec_ = sel < pl.n_p ? pl.rec : back_[pl.rec];
-        }
-        // topologies of the trees accepted during this prune node's scan that some sample still points to
-        for (const UfbState::Pending &pe : u.pending) {
-          if (u.refs[(size_t)pe.tree_index] <= 0) continue;
-          if (pe.cand == 0xFFFFFFFFu) {
-            if (!u.store.count(pe.tree_index)) { u.store.emplace(pe.tree_index, back_); u.stored++; }
-            continue;
-          }
-          ufb_store_tree(pe.tree_index, pe.cand < (uint32_t)pl.n_p ? pl.rec : back_[pl.rec], pl.cands[(size_t)pe.cand].q);
-        }
-        u.pending.clear();
-        bool accept;
-        if (tie_mode_ == MPF_TIE_RANDOM) {
-          if (best_ == randomMP) iter_hits++;
-          if (best_ < randomMP) iter_hits = 1;
-          accept = (best_ < randomMP || (best_ == randomMP && tie_draw() <= 1.0 / (double)iter_hits)) && remove_rec_ >= 0 && insert_rec_ >= 0;
-        } else {
-          accept = best_ < randomMP;
-        }
-        if (accept) {
-          if (sel < 0) { set_error("online UFBoot: accepted move without a candidate of this prune node"); return MPF_E_STATE; }
+        { int rc2 = ufb_replay_visit(plans[(size_t)(j - i)], V, randomMP, iter_hits); if (rc2) return rc2; }
+        if (V.accept) {
           moves_.push_back(Move{remove_rec_, insert_rec_, best_});
           apply_move(remove_rec_, insert_rec_);
           randomMP = best_;
@@ -311,12 +215,7 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
   } while (randomMP < startMP);
   climb_finished(total);
   u.rt_valid = false;
-  if (u.exchange) {
-    // closing handshake: a rank that took another path would be in the middle of a batch here
-    const mpf_ufb_event *all = nullptr;
-    uint32_t n_all_ev = 0;
-    if (u.exchange(u.exchange_arg, 0xFFFFFFFFu, nullptr, 0, &all, &n_all_ev) != 0) { set_error("online UFBoot: ranks out of step at the end of the climb"); return MPF_E_STATE; }
-  }
+  { int rc = ufb_close_exchange(); if (rc) return rc; }
   if (final_score) *final_score = randomMP;
   return MPF_OK;
 }
