@@ -2075,6 +2075,7 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "ufb_event_cap") *v = ufb_event_cap_;
   else if (key == "ufb_batches") *v = ufb_stat_batches_;
   else if (key == "ufb_early_batches") *v = ufb_stat_early_;
+  else if (key == "ufb_event_regrows") *v = ufb_stat_regrows_;
   else if (key == "force_big") *v = force_big_;
   else if (key == "sankoff_short") *v = snk16_opt_;
   else if (key == "sankoff_packed") *v = g_.snk16;       // the store holds two 16-bit costs per word (the guard of Engine::pack let sankoff_short through)

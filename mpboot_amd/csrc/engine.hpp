@@ -539,8 +539,35 @@ class Engine {
   struct UfbPartsVisit;
   template <class Loop> int ufb_replay_visit(const ScanPlan &pl, Loop &L, uint32_t randomMP, unsigned &iter_hits);
   // sample-sharded runs: the all-gather of a batch's events (events <- those of all ranks) and the handshake that closes a climb
-  int ufb_gather_events(std::vector<UfbEvent> &events, uint32_t tag);
-  int ufb_close_exchange();
+  int ufb_gather_events(std::vector<UfbEvent> &events, uint32_t tag, const char *who = "online UFBoot");
+  int ufb_close_exchange(uint32_t tag = 0xFFFFFFFFu, const char *msg = "online UFBoot: ranks out of step at the end of the climb");
+  // ---- the device half of a tracked batch, shared by every loop that books trees (host/ufboot.cpp)
+  // dst (+)= sum over the weight planes of 2^(7 plane + shift) * (rows_p mask rows, or the rows d_sel names) x weights; d_cut: the
+  // device word of a batch's certain end (launch_bitgemm's row_limit).  how: kUfbAccumulate = plane 0 adds to dst as well (a kernel
+  // has zeroed it, or a product stands there); kUfbUncounted = the rows do not go into the gemm_rows counter
+  enum UfbProduct : unsigned { kUfbOverwrite = 0, kUfbAccumulate = 1, kUfbUncounted = 2 };
+  int ufb_mask_product(const uint32_t *masks, int rows_p, int32_t *dst, unsigned how, const uint32_t *d_sel = nullptr, const uint32_t *d_cut = nullptr,
+                       int shift = 0);
+  // weighted engine, step one: the bit planes (UfbState::bitp) of `rows` rows of per-pattern lengths whose largest is vmax
+  struct UfbPlanes { int K = 1, rows_p = 0; };   // planes in use, padded rows per plane
+  int ufb_vals_planes(const uint16_t *vals, uint32_t rows, uint32_t vmax, UfbPlanes &P);
+  // ... step two: C = K x weight planes products of rows_p rows of them (or of the rows d_sel names), R_T = row rt_row of C;
+  // option timing: ev2_ / ev3_ around the product itself, where the SPR loop and the NNI step had them (the refine sweep, which
+  // had none, now records them too and reads nothing)
+  int ufb_weighted_product(const UfbPlanes &P, int rows_p, const uint32_t *d_sel, uint32_t rt_row);
+  // the (candidate, sample) events of a staged batch, synchronously: scratch and first buffers reserved, extraction, the count and
+  // the first events back in one round trip, grown and extracted again while they do not fit, the rest of the events; n_ev events
+  // are left in UfbState::h_ev.  published (or null): a publishing launch has extracted already -- n_ev is its count, *published of
+  // its events are in h_ev
+  struct UfbExtract {
+    const uint2 *info; const uint32_t *cost, *thr, *home, *crow, *best;
+    uint32_t *count;                             // device word, zero
+    uint32_t n_idx; int all_events;
+    bool eager = true;                           // the first 4096 events ride with the count (false: the count alone, then all events)
+  };
+  int ufb_extract_events(const UfbExtract &x, uint32_t &n_ev, const uint32_t *published = nullptr);
+  int ufb_reserve_events(uint32_t n_idx);        // its scratch and the first size of the event buffers
+  int64_t ufb_stat_regrows_ = 0;                 // read-only option ufb_event_regrows: extractions run again because the events did not fit
   int ufb_moot_ = 1;                             // option "ufb_moot"
   int ufb_memo_ = 1;                             // option "ufb_memo": no product for the batches of a topology known to be event-free (UfbState::quiet_topo)
   // the log of one batch against an explicit topology: touches nothing of the engine but n_ and the tracker's deferred state

@@ -415,30 +415,15 @@ int Engine::nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home
   if (sel_rows) std::memcpy(sm + o_sel, sel_rows->data(), sel_rows->size() * sizeof(uint32_t));
   UCHK(hipMemcpyAsync(u.thr.p, sm, (o_cnt + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
   if (!have_C) { int rc = product(rows_p, sel_rows ? u.thr.p + o_sel : nullptr); if (rc) return rc; }
-  const uint32_t nch = ufb_chunks(n_idx);
-  UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
-  UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
-  if (u.ev.cap == 0) { const size_t c0 = (size_t)std::min<int64_t>(ufb_event_cap_, 1 << 18); UCHK(u.ev.reserve(c0)); }
-  uint32_t *d_evcount = u.thr.p + o_cnt;
   uint32_t n_ev = 0;
   // the list rules and -storetrees see every (candidate, sample) at or below the sample's bound at the start of the step, not only the
   // strict improvements of a running minimum (as spr_sweeps_ufboot asks for them)
-  const int all_events = (u.topboot || u.distinct || u.store_trees) ? 1 : 0;
-  for (bool again = false;; again = true) {
-    if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
-    UCHK(launch_ufb_events(st_, reinterpret_cast<const uint2 *>(u.thr.p + o_info), u.thr.p + o_cost, u.thr.p, u.thr.p + o_home, u.thr.p + o_crow, u.C.p,
-                           u.Bp, u.Bl, u.rt.p, u.thr.p + o_best, n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, all_events));
-    UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-    UCHK(hipStreamSynchronize(st_));
-    n_ev = u.h_small.p[0];
-    if (n_ev <= u.ev.cap) break;
-    UCHK(u.ev.reserve((size_t)n_ev));              // more events than room: grow and extract again
-  }
+  const UfbExtract x{reinterpret_cast<const uint2 *>(u.thr.p + o_info), u.thr.p + o_cost, u.thr.p, u.thr.p + o_home, u.thr.p + o_crow, u.thr.p + o_best,
+                     u.thr.p + o_cnt, n_idx, (u.topboot || u.distinct || u.store_trees) ? 1 : 0,
+                     false};        // (no eager prefix: a step's events are fetched in one copy behind the count, as they always were here)
+  { int rc = ufb_extract_events(x, n_ev); if (rc) return rc; }
   events.clear();
   if (n_ev) {
-    UCHK(u.h_ev.reserve((size_t)n_ev));
-    UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_ev * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-    UCHK(hipStreamSynchronize(st_));
     events.assign(u.h_ev.p, u.h_ev.p + n_ev);
     for (UfbEvent &e : events) e.b = (uint32_t)u.ids[(size_t)e.b];
     if (!u.exchange) {                             // (a sample-sharded tracker orders the merged events: nni_exchange_events)
@@ -458,20 +443,12 @@ int Engine::nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home
 int Engine::nni_exchange_events(uint32_t n_idx, std::vector<UfbEvent> &events)
 {
   UfbState &u = *ufb_;
-  static_assert(sizeof(UfbEvent) == sizeof(mpf_ufb_event), "event layouts must match");
   for (int c2 = 0; c2 < u.Bl; c2++) events.push_back(UfbEvent{0u, (uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2]});
-  const mpf_ufb_event *all = nullptr;
-  uint32_t n_all_ev = 0;
-  const uint32_t tag = 0x40000000u | (u.nni_tag++ & 0x3FFFFFFFu);
-  if (u.exchange(u.exchange_arg, tag, reinterpret_cast<const mpf_ufb_event *>(events.data()), (uint32_t)events.size(), &all, &n_all_ev) != 0) {
-    set_error("tracked NNI climb: event exchange failed (ranks out of step?)");
-    return MPF_E_STATE;
-  }
-  const UfbEvent *pa = reinterpret_cast<const UfbEvent *>(all);
-  std::vector<UfbEvent> merged(pa, pa + n_all_ev), tmp;
+  int rc = ufb_gather_events(events, 0x40000000u | (u.nni_tag++ & 0x3FFFFFFFu), "tracked NNI climb");
+  if (rc) return rc;
+  std::vector<UfbEvent> tmp;
   std::vector<uint32_t> count;
-  sort_events(merged, tmp, count, n_idx, (uint32_t)u.B);
-  events.swap(merged);
+  sort_events(events, tmp, count, n_idx, (uint32_t)u.B);
   return MPF_OK;
 }
 
@@ -501,28 +478,21 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
   const size_t Wp = (size_t)g_.Wp;
   u.nni_booked += 1u + 2u * (uint64_t)nb;
   u.batches++;
-  const bool have_cut = u.logl_cutoff != 0.0;
-  const double lim = -u.logl_cutoff + 1e-4;        // iqtree.cpp:3343: booked iff  -len > logl_cutoff - 1e-4
-  const bool none_pass = have_cut && lim <= 0.0;
-  const uint32_t mp_max = have_cut ? (none_pass ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
+  const UfbCutoff cut = ufb_cutoff(u.logl_cutoff);     // iqtree.cpp:3343: booked iff  -len > logl_cutoff - 1e-4
   // -storetrees (iqtree.cpp:3302-3341): a topology met before is counted, and booked again when its length improved, whatever the
   // cut-off says -- no step is skipped, every row is multiplied, every candidate takes part in the extraction and the replay decides
   const bool store_trees = u.store_trees, sharded = u.exchange != nullptr;
-  if (none_pass && !store_trees) return MPF_OK;
+  if (cut.none_pass && !store_trees) return MPF_OK;
   const double t0 = now_ms();
   if (!u.rt_valid) { int rc = ufb_current_tree_reps(); if (rc) return rc; }       // (uses C: in front of the product)
   UCHK(u.h_rt.reserve((size_t)u.Bp));
   UCHK(hipMemcpyAsync(u.h_rt.p, u.rt.p, (size_t)(u.Bl + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
   const int mask_rows_p = round_up((int)(3u * nb), kUfbRowTile);
   const uint32_t *plane[2] = {d_nni_planes_.p, d_nni_planes_.p + (size_t)mask_rows_p * Wp};
-  auto product = [&](int rows_p, const uint32_t *d_sel) -> int {
+  auto product = [&](int rows_p, const uint32_t *d_sel) -> int {      // C = plane 0 x W + 2 * plane 1 x W, its rows counted once
     UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
-    bool first = true;
-    for (int pl = 0; pl < u.planes; pl++)
-      for (int bp = 0; bp < 2; bp++, first = false)
-        UCHK(launch_bitgemm(st_, plane[bp], rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, (1 << (7 * pl)) << bp, first ? 0 : 1, d_sel));
-    u.gemm_rows += (uint64_t)rows_p;
-    return MPF_OK;
+    int rc = ufb_mask_product(plane[0], rows_p, u.C.p, kUfbOverwrite, d_sel);
+    return rc ? rc : ufb_mask_product(plane[1], rows_p, u.C.p, kUfbAccumulate | kUfbUncounted, d_sel, nullptr, 1);
   };
   std::vector<uint32_t> blen(2 * (size_t)nb);      // the length each candidate is booked under
   bool have_C = false;
@@ -544,16 +514,16 @@ int Engine::nni_book_step(const std::vector<NniBranch> &br, const std::vector<ui
 
   // ---- the current tree: its own length (ratchet: its length on the original alignment), every sample from R_T
   const uint32_t self_len = ratchet ? u.rt_orig : cur;
-  const bool self_pass = !none_pass && self_len <= mp_max;
+  const bool self_pass = cut.passes(self_len);
   if (!sharded) replay.book_self(self_len, self_pass);
 
   // ---- the candidates that pass: product (unless a ratchet step has it), extraction
   std::vector<uint8_t> pass(2 * (size_t)nb), take(2 * (size_t)nb);       // pass: the cut-off test; take: part of the extraction
   uint32_t n_pass = 0;
-  for (size_t c = 0; c < pass.size(); c++) { pass[c] = !none_pass && blen[c] <= mp_max; take[c] = store_trees || pass[c]; n_pass += take[c]; }
+  for (size_t c = 0; c < pass.size(); c++) { pass[c] = cut.passes(blen[c]); take[c] = store_trees || pass[c]; n_pass += take[c]; }
   std::vector<UfbEvent> events;
   if (n_pass) {
-    const bool compact = have_cut && !ratchet && !store_trees;
+    const bool compact = cut.have_cut && !ratchet && !store_trees;
     std::vector<uint32_t> sel_rows, home(nb), part((size_t)n_idx, 0xFFFFFFFFu);
     std::vector<uint32_t> crow((size_t)n_idx, 0xFFFFFFFFu);
     for (uint32_t i = 0; i < nb; i++) {
@@ -602,48 +572,29 @@ int Engine::nni_book_step_snk(const std::vector<NniBranch> &br, const std::vecto
   const uint32_t nb = (uint32_t)br.size(), n_idx = 2u + 2u * nb, R = 2u * nb;       // R: the current tree's row of vals
   const bool ratchet = u.ratchet;
   const int oc = u.Bl;
-  const uint32_t npat = (uint32_t)g_.Wp;
   u.nni_booked += 1u + 2u * (uint64_t)nb;
   u.batches++;
-  const bool have_cut = u.logl_cutoff != 0.0;
-  const double lim = -u.logl_cutoff + 1e-4;        // iqtree.cpp:3343
-  const bool none_pass = have_cut && lim <= 0.0;
-  const uint32_t mp_max = have_cut ? (none_pass ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
+  const UfbCutoff cut = ufb_cutoff(u.logl_cutoff);     // iqtree.cpp:3343
   const bool store_trees = u.store_trees, sharded = u.exchange != nullptr;      // (-storetrees: as in nni_book_step)
-  if (none_pass && !store_trees) return MPF_OK;
+  if (cut.none_pass && !store_trees) return MPF_OK;
   std::vector<uint32_t> blen(len.begin(), len.begin() + 2 * (size_t)nb);
   std::vector<uint8_t> pass(2 * (size_t)nb), take(2 * (size_t)nb, 1);
   uint32_t n_pass = 0;
   if (!ratchet) {
-    for (size_t c = 0; c < pass.size(); c++) { pass[c] = !none_pass && blen[c] <= mp_max; n_pass += pass[c]; }
-    if (!store_trees && !n_pass && cur > mp_max) return MPF_OK;    // nothing of this step is booked: nothing to multiply
+    for (size_t c = 0; c < pass.size(); c++) { pass[c] = cut.passes(blen[c]); n_pass += pass[c]; }
+    if (!store_trees && !n_pass && !cut.passes(cur)) return MPF_OK;    // nothing of this step is booked: nothing to multiply
   }
   const double t0 = now_ms();
   // ---- K from vmax (nni_eval has waited for it), the bit planes of all 2 nb + 1 rows
-  int K = 1;
-  while (K < 16 && (h_nni_vmax_.p[0] >> K)) K++;
   const uint32_t rows = 2u * nb + 1u;
-  const int plane_rows_p = round_up((int)rows, kUfbRowTile);
-  const size_t plane_words = (size_t)plane_rows_p * (size_t)u.Wp_s;
-  UCHK(u.bitp.reserve((size_t)K * plane_words));
-  UCHK(hipMemsetAsync(u.bitp.p, 0, (size_t)K * plane_words * sizeof(uint32_t), st_));
-  for (uint32_t r0 = 0; r0 < rows; r0 += 32768u)                  // (grid.y limit)
-    UCHK(launch_vals_planes(st_, d_nni_vals_.p + (size_t)r0 * npat, std::min(32768u, rows - r0), npat, K, u.bitp.p + (size_t)r0 * u.Wp_s,
-                            (uint32_t)plane_rows_p, (uint32_t)u.Wp_s));
+  UfbPlanes P;
+  { int rc = ufb_vals_planes(d_nni_vals_.p, rows, h_nni_vmax_.p[0], P); if (rc) return rc; }
+  const int plane_rows_p = P.rows_p;
   uint32_t cur_row = R;                            // the current tree's row of C
   bool timed = false;
   auto product = [&](int rows_p, const uint32_t *d_sel) -> int {
-    UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
-    if (timing_) { UCHK(hipEventRecord(ev2_, st_)); timed = true; }
-    bool first = true;
-    for (int k = 0; k < K; k++)
-      for (int pl = 0; pl < u.planes; pl++, first = false)
-        UCHK(launch_bitgemm(st_, u.bitp.p + (size_t)k * plane_words, rows_p, u.Wp_s, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p,
-                            (1 << k) << (7 * pl), first ? 0 : 1, d_sel));
-    if (timing_) UCHK(hipEventRecord(ev3_, st_));
-    u.gemm_rows += (uint64_t)rows_p * (uint64_t)K;
-    UCHK(u.rt.reserve((size_t)u.Bp));
-    UCHK(launch_colsum(st_, u.C.p + (size_t)cur_row * u.Bp, 1, u.Bp, u.rt.p));       // R_T = the current tree's own row
+    timed = timing_;
+    { int rc = ufb_weighted_product(P, rows_p, d_sel, cur_row); if (rc) return rc; }       // (R_T = the current tree's own row; ev2_ .. ev3_)
     UCHK(u.h_rt.reserve((size_t)u.Bp));
     UCHK(hipMemcpyAsync(u.h_rt.p, u.rt.p, (size_t)(u.Bl + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
     return MPF_OK;
@@ -661,11 +612,11 @@ int Engine::nni_book_step_snk(const std::vector<NniBranch> &br, const std::vecto
     UCHK(hipMemcpyAsync(u.h_col.p, u.d_col.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
     UCHK(hipStreamSynchronize(st_));
     u.rt_orig = self_len = (uint32_t)u.h_col.p[R];
-    for (size_t c = 0; c < pass.size(); c++) { blen[c] = (uint32_t)u.h_col.p[c]; pass[c] = !none_pass && blen[c] <= mp_max; n_pass += pass[c]; }
+    for (size_t c = 0; c < pass.size(); c++) { blen[c] = (uint32_t)u.h_col.p[c]; pass[c] = cut.passes(blen[c]); n_pass += pass[c]; }
   }
   if (!store_trees) take = pass;
   // ---- product of the rows that are booked (unless a ratchet step has it), extraction
-  const bool compact = have_cut && !ratchet && !store_trees;
+  const bool compact = cut.have_cut && !ratchet && !store_trees;
   std::vector<uint32_t> sel_rows, home(1, 1u + 2u * nb), part((size_t)n_idx, 0xFFFFFFFFu), crow((size_t)n_idx, 0xFFFFFFFFu);
   for (uint32_t c = 0; c < 2 * nb; c++) {
     part[1 + c] = 0u;
@@ -686,7 +637,7 @@ int Engine::nni_book_step_snk(const std::vector<NniBranch> &br, const std::vecto
   u.t_dev += t1 - t0;
   // ---- host replay: the current tree (every sample from R_T), then the candidates
   NniReplay replay(*this, mv);
-  replay.book_self(self_len, !none_pass && self_len <= mp_max, sharded ? &events : nullptr);
+  replay.book_self(self_len, cut.passes(self_len), sharded ? &events : nullptr);
   replay.book_candidates(blen, pass, events);
   u.t_replay += now_ms() - t1;
   return MPF_OK;
@@ -713,12 +664,8 @@ int Engine::ufboot_optimize_nni(int root_taxon, bool speednni, int max_steps, ui
   ufb_->nni_tag = 0;
   const int rc = nni_climb(root_taxon, speednni, max_steps, tracked, score, nni_count, nni_steps);
   ufb_->rt_valid = false;
-  if (rc == MPF_OK && tracked && u.exchange) {
-    // closing handshake, as the SPR climb has one: a rank that took another path would be in the middle of a step here
-    const mpf_ufb_event *all = nullptr;
-    uint32_t n_all_ev = 0;
-    if (u.exchange(u.exchange_arg, 0xFFFFFFFEu, nullptr, 0, &all, &n_all_ev) != 0) { set_error("tracked NNI climb: ranks out of step at the end of the climb"); return MPF_E_STATE; }
-  }
+  // closing handshake, as the SPR climb has one: a rank that took another path would be in the middle of a step here
+  if (rc == MPF_OK && tracked) return ufb_close_exchange(0xFFFFFFFEu, "tracked NNI climb: ranks out of step at the end of the climb");
   return rc;
 }
 

@@ -427,11 +427,100 @@ int Engine::ufb_current_tree_reps()
   UCHK(hipMemcpyAsync(d_evops_.p, ops.data(), ops.size() * sizeof(EvOp), hipMemcpyHostToDevice, st_));
   UCHK(hipMemsetAsync(u.jmasks.p + (size_t)rows * g_.Wp, 0, (size_t)(rows_p - rows) * g_.Wp * sizeof(uint32_t), st_));
   UCHK(launch_join_masks(st_, g_, vec_rows(), d_evops_.p, rows, u.jmasks.p));
-  for (int pl = 0; pl < u.planes; pl++)
-    UCHK(launch_bitgemm(st_, u.jmasks.p, rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, 1 << (7 * pl), pl > 0));
+  { int rc = ufb_mask_product(u.jmasks.p, rows_p, u.C.p, kUfbUncounted); if (rc) return rc; }
   UCHK(launch_colsum(st_, u.C.p, rows, u.Bp, u.rt.p));
   UCHK(hipStreamSynchronize(st_));     // ops (host vector) must outlive the copy
   u.rt_valid = true;
+  return MPF_OK;
+}
+
+// ---- the device half of a tracked batch: what every loop that books trees runs between its staging upload and its replay ----
+int Engine::ufb_mask_product(const uint32_t *masks, int rows_p, int32_t *dst, unsigned how, const uint32_t *d_sel, const uint32_t *d_cut, int shift)
+{
+  UfbState &u = *ufb_;
+  for (int pl = 0; pl < u.planes; pl++)
+    UCHK(launch_bitgemm(st_, masks, rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, dst, (1 << (7 * pl)) << shift, ((how & kUfbAccumulate) || pl > 0) ? 1 : 0,
+                        d_sel, d_cut));
+  if (!(how & kUfbUncounted)) u.gemm_rows += (uint64_t)rows_p;
+  return MPF_OK;
+}
+
+int Engine::ufb_vals_planes(const uint16_t *vals, uint32_t rows, uint32_t vmax, UfbPlanes &P)
+{
+  UfbState &u = *ufb_;
+  const uint32_t npat = (uint32_t)g_.Wp;
+  P.K = 1;
+  while (P.K < 16 && (vmax >> P.K)) P.K++;
+  P.rows_p = round_up((int)rows, kUfbRowTile);
+  const size_t plane_words = (size_t)P.rows_p * (size_t)u.Wp_s;
+  UCHK(u.bitp.reserve((size_t)P.K * plane_words));
+  UCHK(hipMemsetAsync(u.bitp.p, 0, (size_t)P.K * plane_words * sizeof(uint32_t), st_));
+  for (uint32_t r0 = 0; r0 < rows; r0 += 32768u)                  // (grid.y limit)
+    UCHK(launch_vals_planes(st_, vals + (size_t)r0 * npat, std::min(32768u, rows - r0), npat, P.K, u.bitp.p + (size_t)r0 * u.Wp_s, (uint32_t)P.rows_p,
+                            (uint32_t)u.Wp_s));
+  return MPF_OK;
+}
+
+int Engine::ufb_weighted_product(const UfbPlanes &P, int rows_p, const uint32_t *d_sel, uint32_t rt_row)
+{
+  UfbState &u = *ufb_;
+  const size_t plane_words = (size_t)P.rows_p * (size_t)u.Wp_s;
+  UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
+  if (timing_) UCHK(hipEventRecord(ev2_, st_));       // (the product alone is timed: callers read ev2_ .. ev3_ behind their wait)
+  bool first = true;
+  for (int k = 0; k < P.K; k++)
+    for (int pl = 0; pl < u.planes; pl++, first = false)
+      UCHK(launch_bitgemm(st_, u.bitp.p + (size_t)k * plane_words, rows_p, u.Wp_s, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, (1 << k) << (7 * pl),
+                          first ? 0 : 1, d_sel));
+  if (timing_) UCHK(hipEventRecord(ev3_, st_));
+  u.gemm_rows += (uint64_t)rows_p * (uint64_t)P.K;
+  UCHK(u.rt.reserve((size_t)u.Bp));
+  UCHK(launch_colsum(st_, u.C.p + (size_t)rt_row * u.Bp, 1, u.Bp, u.rt.p));       // R_T = the current tree's own row
+  return MPF_OK;
+}
+
+// the extraction's scratch and the first size of the event buffers
+int Engine::ufb_reserve_events(uint32_t n_idx)
+{
+  UfbState &u = *ufb_;
+  const uint32_t nch = ufb_chunks(n_idx);
+  UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
+  UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
+  if (u.ev.cap == 0) { const size_t c0 = (size_t)std::min<int64_t>(ufb_event_cap_, 1 << 18); UCHK(u.ev.reserve(c0)); UCHK(u.h_ev.reserve(c0)); }
+  return MPF_OK;
+}
+
+int Engine::ufb_extract_events(const UfbExtract &x, uint32_t &n_ev, const uint32_t *published)
+{
+  UfbState &u = *ufb_;
+  if (!published) { int rc = ufb_reserve_events(x.n_idx); if (rc) return rc; }
+  uint32_t n_eager = published ? *published : 0u;
+  for (bool again = published != nullptr;; again = true) {
+    if (again) {
+      if (n_ev <= u.ev.cap) break;
+      UCHK(u.ev.reserve((size_t)n_ev));              // more events than room: grow and extract again (the product is still there)
+      UCHK(u.h_ev.reserve((size_t)n_ev));
+      UCHK(hipMemsetAsync(x.count, 0, sizeof(uint32_t), st_));
+      ufb_stat_regrows_++;
+    }
+    UCHK(launch_ufb_events(st_, x.info, x.cost, x.thr, x.home, x.crow, u.C.p, u.Bp, u.Bl, u.rt.p, x.best, x.n_idx, u.cmin.p, u.pre.p, u.ev.p,
+                           (uint32_t)u.ev.cap, x.count, x.all_events));
+    UCHK(hipMemcpyAsync(u.h_small.p, x.count, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+    // the first few thousand events ride along with their count: the batches of a climb need no second round trip
+    n_eager = x.eager ? (uint32_t)std::min<size_t>(u.ev.cap, 4096) : 0u;
+    if (n_eager) {
+      UCHK(u.h_ev.reserve((size_t)n_eager));
+      UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_eager * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
+    }
+    UCHK(hipStreamSynchronize(st_));
+    n_ev = u.h_small.p[0];
+  }
+  if (n_ev > n_eager) {
+    if (u.h_ev.cap < (size_t)n_ev) n_eager = 0;       // (a grown pinned buffer starts empty)
+    UCHK(u.h_ev.reserve((size_t)n_ev));
+    UCHK(hipMemcpyAsync(u.h_ev.p + n_eager, u.ev.p + n_eager, (size_t)(n_ev - n_eager) * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
+    UCHK(hipStreamSynchronize(st_));
+  }
   return MPF_OK;
 }
 
@@ -451,14 +540,14 @@ void Engine::ufb_flush_pending(const ScanPlan &pl)
 }
 
 // sample-sharded run: every rank replays the events of all ranks -- one all-gather per batch, events <- the ranks' lists in rank order
-int Engine::ufb_gather_events(std::vector<UfbEvent> &events, uint32_t tag)
+int Engine::ufb_gather_events(std::vector<UfbEvent> &events, uint32_t tag, const char *who)
 {
   static_assert(sizeof(UfbEvent) == sizeof(mpf_ufb_event), "event layouts must match");
   UfbState &u = *ufb_;
   const mpf_ufb_event *all = nullptr;
   uint32_t n_all_ev = 0;
   if (u.exchange(u.exchange_arg, tag, reinterpret_cast<const mpf_ufb_event *>(events.data()), (uint32_t)events.size(), &all, &n_all_ev) != 0) {
-    set_error("online UFBoot: event exchange failed (ranks out of step?)");
+    set_error(std::string(who) + ": event exchange failed (ranks out of step?)");
     return MPF_E_STATE;
   }
   const UfbEvent *pa = reinterpret_cast<const UfbEvent *>(all);
@@ -467,13 +556,13 @@ int Engine::ufb_gather_events(std::vector<UfbEvent> &events, uint32_t tag)
 }
 
 // ... and the closing handshake of a tracked climb: a rank that took another path would be in the middle of a batch here
-int Engine::ufb_close_exchange()
+int Engine::ufb_close_exchange(uint32_t tag, const char *msg)
 {
   UfbState &u = *ufb_;
   if (!u.exchange) return MPF_OK;
   const mpf_ufb_event *all = nullptr;
   uint32_t n_all_ev = 0;
-  if (u.exchange(u.exchange_arg, 0xFFFFFFFFu, nullptr, 0, &all, &n_all_ev) != 0) { set_error("online UFBoot: ranks out of step at the end of the climb"); return MPF_E_STATE; }
+  if (u.exchange(u.exchange_arg, tag, nullptr, 0, &all, &n_all_ev) != 0) { set_error(msg); return MPF_E_STATE; }
   return MPF_OK;
 }
 
@@ -676,9 +765,9 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
   // original alignment fails the cut-off, the first booking closes the gate and nothing of the climb is booked at all.
   int resume_i = 0;                                // > 0: the sweep under way continues at this visit (startMP, iter_hits as handed over)
   if (ufb_quiet_ && u.logl_cutoff != 0.0 && !u.store_trees && !u.snk) {
-    const double lim0 = -u.logl_cutoff + 1e-4;
-    const uint32_t mp_max0 = lim0 <= 0.0 ? 0u : (uint32_t)std::ceil(lim0) - 1u;
-    bool whole = lim0 <= 0.0;                      // nothing can pass
+    const UfbCutoff cut0 = ufb_cutoff(u.logl_cutoff);
+    const uint32_t mp_max0 = cut0.mp_max;
+    bool whole = cut0.none_pass;                   // nothing can pass
     if (u.ratchet && !whole) {
       if (!u.rt_valid) { int rc = ufb_current_tree_reps(); if (rc) return rc; }
       UCHK(u.h_col.reserve(4));
@@ -798,7 +887,8 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
       plans_cur ^= 1;
       std::vector<ScanPlan> &plans = plans_buf[plans_cur];
       // cut-off filter (reference iqtree.cpp:3343): a candidate is saved iff  -mp > logl_cutoff - 1e-4
-      const bool have_cut = u.logl_cutoff != 0.0;
+      const UfbCutoff cut = ufb_cutoff(u.logl_cutoff);
+      const bool have_cut = cut.have_cut;
       // one dispatch chain per batch: without a cut-off nothing the host would read from the scan decides what is
       // multiplied, so the product and the extraction are enqueued right behind the scan and the host waits ONCE
       scan_masks_ = true;
@@ -816,9 +906,8 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
       // ---- the first prune node with a strictly better candidate ends the batch for certain: nothing behind it
       //      needs REPS (a tie may end it earlier; then the tail of the product is simply not used)
       const int jstar = chained ? np - 1 : ufb_first_better(plans, np, out, randomMP);
-      const double lim = -u.logl_cutoff + 1e-4;
-      const uint32_t mp_max = have_cut ? (lim <= 0.0 ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
-      const bool none_pass = have_cut && lim <= 0.0;
+      const uint32_t mp_max = cut.mp_max;
+      const bool none_pass = cut.none_pass;
       // ---- device: REPS of every candidate of plans [0, jstar], then the (candidate, sample) events
       uint32_t n_idx = 0, n_parts = 0;
       self_list.clear();
@@ -905,10 +994,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
         const size_t o_self = o_sel + (compact ? (size_t)rows_p : 0);
         const size_t o_cnt = o_self + self_list.size();          // the event counter: a zero word of this upload (no memset dispatch)
         UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
-        const uint32_t nch = ufb_chunks(n_idx);
-        UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
-        UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
-        if (u.ev.cap == 0) { const size_t c0 = (size_t)std::min<int64_t>(ufb_event_cap_, 1 << 18); UCHK(u.ev.reserve(c0)); UCHK(u.h_ev.reserve(c0)); }
+        if (chained) { int rc2 = ufb_reserve_events(n_idx); if (rc2) return rc2; }      // (in front of the staging upload: nothing allocates inside the one-wait chain)
         const uint32_t *d_thr = nullptr, *d_home = nullptr, *d_best = nullptr, *d_crow = nullptr, *d_sel = nullptr, *d_self = nullptr;
         if (chained) {
           // the staging block normally went up with the refresh's own upload (Engine::scan_batch); a batch on valid views has none
@@ -928,7 +1014,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
           const ScanPlan &pl = plans[(size_t)j];
           for (int pi = 0; pi < pl.n_parts; pi++) {
             const uint32_t d = (uint32_t)pl.part_desc[pi];
-            small[d] = (!have_cut || ratchet || store_trees) ? UINT32_MAX : (mp_max >= pl.base ? mp_max - pl.base + 1u : 0u);   // max cost + 1
+            small[d] = (!have_cut || ratchet || store_trees) ? UINT32_MAX : cut.part_threshold(pl.base);   // max cost + 1
             small[n_parts + d] = pl.part_off[pi] + (uint32_t)pl.part_cnt[pi];
           }
         }
@@ -952,9 +1038,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
           UCHK(launch_ufb_prep(st_, u.C.p, (size_t)rows_p * (size_t)u.Bp, u.info.p, d_self, (uint32_t)self_list.size(),
                                (self_pass && !host_self) ? 0xFFFFFFFEu : 0xFFFFFFFFu, d_evcount));
           if (timing_) UCHK(hipEventRecord(ev2_, st_));
-          for (int pl = 0; pl < u.planes; pl++)
-            UCHK(launch_bitgemm(st_, u.masks.p, rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, 1 << (7 * pl), 1));
-          u.gemm_rows += (uint64_t)rows_p;
+          { int rc2 = ufb_mask_product(u.masks.p, rows_p, u.C.p, kUfbAccumulate); if (rc2) return rc2; }      // (the prep kernel has zeroed C)
           have_C = true;
           ran_events = true;
           if (timing_) UCHK(hipEventRecord(ev3_, st_));
@@ -995,20 +1079,9 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
             float ms = 0;
             if (hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) u.gemm_ms += ms;
           }
-          if (n_ev > u.ev.cap) {
-            // more events than room: grow and extract again (the product is still there)
-            UCHK(u.ev.reserve((size_t)n_ev));
-            UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
-            UCHK(launch_ufb_events(st_, u.info.p, d_out(), d_thr, d_home, nullptr, u.C.p, u.Bp, u.Bl, u.rt.p, d_best, n_idx, u.cmin.p, u.pre.p,
-                                   u.ev.p, (uint32_t)u.ev.cap, d_evcount, (u.topboot || u.distinct) ? 1 : 0));
-            n_eager = 0;
-          }
-          if (n_ev > n_eager) {
-            if (u.h_ev.cap < (size_t)n_ev) n_eager = 0;       // (a grown pinned buffer starts empty)
-            UCHK(u.h_ev.reserve((size_t)n_ev));
-            UCHK(hipMemcpyAsync(u.h_ev.p + n_eager, u.ev.p + n_eager, (size_t)(n_ev - n_eager) * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-            UCHK(hipStreamSynchronize(st_));
-          }
+          // (more events than room, or than the publishing launch brought along: extracted again / fetched)
+          const UfbExtract x{u.info.p, d_out(), d_thr, d_home, nullptr, d_best, d_evcount, n_idx, (u.topboot || u.distinct) ? 1 : 0};
+          { int rc2 = ufb_extract_events(x, n_ev, &n_eager); if (rc2) return rc2; }
         } else {
         UCHK(launch_ufb_self(st_, u.info.p, d_self, (uint32_t)self_list.size(), (self_pass && !host_self) ? 0xFFFFFFFEu : 0xFFFFFFFFu));
         if (host_self && self_pass) {                  // R_T for the host's own walk over the current tree's bookings
@@ -1017,9 +1090,8 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
         }
         if (timing_) UCHK(hipEventRecord(ev2_, st_));
         if (n_rows > 0) {
-          for (int pl = 0; pl < u.planes; pl++)
-            UCHK(launch_bitgemm(st_, u.masks.p, rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, 1 << (7 * pl), pl > 0, d_sel));
-          u.gemm_rows += (uint64_t)rows_p;
+          int rc2 = ufb_mask_product(u.masks.p, rows_p, u.C.p, kUfbOverwrite, d_sel);
+          if (rc2) return rc2;
           have_C = true;
         }
         if (timing_) UCHK(hipEventRecord(ev3_, st_));
@@ -1030,31 +1102,11 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
           UCHK(launch_ufb_column(st_, u.C.p, u.Bp, oc, n_rows, u.d_col.p));
           UCHK(hipMemcpyAsync(u.h_col.p, u.d_col.p, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, st_));   // synchronised with the event count below
         }
-        uint32_t *d_evcount = u.thr.p + o_cnt;
-        for (bool again = false;; again = true) {
-          if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
-          UCHK(launch_ufb_events(st_, u.info.p, d_out(), d_thr, d_home, d_crow, u.C.p, u.Bp, u.Bl, u.rt.p, d_best, n_idx, u.cmin.p, u.pre.p,
-                                 u.ev.p, (uint32_t)u.ev.cap, d_evcount, (u.topboot || u.distinct || store_trees) ? 1 : 0));
-          UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-          // the first few thousand events ride along with their count: the batches of a climb need no second round trip
-          n_eager = (uint32_t)std::min<size_t>(u.ev.cap, 4096);
-          UCHK(u.h_ev.reserve((size_t)n_eager));
-          UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_eager * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-          UCHK(hipStreamSynchronize(st_));
-          n_ev = u.h_small.p[0];
-          if (n_ev <= u.ev.cap) break;
-          UCHK(u.ev.reserve((size_t)n_ev));              // more events than room: grow and extract again
-          UCHK(u.h_ev.reserve((size_t)n_ev));
-        }
+        const UfbExtract x{u.info.p, d_out(), d_thr, d_home, d_crow, d_best, u.thr.p + o_cnt, n_idx, (u.topboot || u.distinct || store_trees) ? 1 : 0};
+        { int rc2 = ufb_extract_events(x, n_ev); if (rc2) return rc2; }
         if (timing_) {
           float ms = 0;
           if (hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) u.gemm_ms += ms;
-        }
-        if (n_ev > n_eager) {
-          if (u.h_ev.cap < (size_t)n_ev) n_eager = 0;       // (a grown pinned buffer starts empty)
-          UCHK(u.h_ev.reserve((size_t)n_ev));
-          UCHK(hipMemcpyAsync(u.h_ev.p + n_eager, u.ev.p + n_eager, (size_t)(n_ev - n_eager) * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-          UCHK(hipStreamSynchronize(st_));
         }
         }
         t1 = now_ms();
@@ -1132,7 +1184,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
       }
       // ---- host replay in the reference's order (ufb_replay_visit, host/ufboot_common.hpp)
       V.out = out; V.hinfo = hinfo; V.h_rt = u.h_rt.p; V.ep = 0;
-      V.none_pass = none_pass; V.mp_max = mp_max; V.skip_ahead = have_cut && !ratchet && !store_trees;
+      V.cut = cut; V.skip_ahead = have_cut && !ratchet && !store_trees;
       V.product_self = ran_events; V.product_cand = have_C;      // (have_C: a ratchet batch with candidates always has its product)
       V.moot = moot_on ? &moot : nullptr;
       bool moved = false;
@@ -1160,8 +1212,7 @@ int Engine::spr_sweeps_ufboot(int mintrav, int maxtrav, uint32_t randomMP, uint3
               for (int z = 0; z < kUfbRowTile; z++) u.h_small.p[z] = sel_home;
               u.h_small.p[0] = hinfo[sel_idx].x;
               UCHK(hipMemcpyAsync(u.sel2.p, u.h_small.p, (size_t)kUfbRowTile * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
-              for (int pl2 = 0; pl2 < u.planes; pl2++)
-                UCHK(launch_bitgemm(st_, u.masks.p, kUfbRowTile, g_.Wp, u.wt.p + (size_t)pl2 * u.plane_bytes, u.Bp, u.C2.p, 1 << (7 * pl2), pl2 > 0, u.sel2.p));
+              { int rc2 = ufb_mask_product(u.masks.p, kUfbRowTile, u.C2.p, kUfbUncounted, u.sel2.p); if (rc2) return rc2; }
               UCHK(launch_rt_update(st_, u.rt.p, u.C2.p, u.Bp, 0u, 1u));
               UCHK(hipStreamSynchronize(st_));       // h_small is reused by the next batch
             }

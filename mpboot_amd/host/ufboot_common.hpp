@@ -18,6 +18,7 @@
 #include "lcg_block.hpp"
 #include "simd_util.hpp"
 #include "spr_rule.hpp"
+#include "ufb_cutoff.hpp"
 
 namespace mpf {
 
@@ -230,9 +231,9 @@ struct Engine::UfbVisit {
   const uint32_t *out = nullptr;
   const std::vector<UfbEvent> *events = nullptr;
   size_t ep = 0;
-  // what is booked: the cut-off (none_pass, mp_max), the ratchet gate (product_*: the batch has the REPS it reads), -storetrees
-  bool ratchet = false, store_trees = false, none_pass = false, product_self = true, product_cand = true;
-  uint32_t mp_max = UINT32_MAX;
+  // what is booked: the cut-off (host/ufb_cutoff.hpp), the ratchet gate (product_*: the batch has the REPS it reads), -storetrees
+  bool ratchet = false, store_trees = false, product_self = true, product_cand = true;
+  UfbCutoff cut;
   // the update rule: deferred (acceptances go to the log) or in place; the current tree's bookings from R_T on the host (h_rt) or
   // from events; self_row: the current tree has a cost and a product row of its own at every visit (asymmetric cost matrix)
   bool defer = false, host_self = true, self_row = false;
@@ -270,7 +271,7 @@ struct Engine::UfbPartsVisit : Engine::UfbVisit {
     for (; at.pi < pl.n_parts; at.pi++, at.k = 0) {
       const int cnt = pl.part_cnt[at.pi];
       if (skip_ahead && at.k < cnt) {
-        const uint32_t lim_len = std::max(none_pass ? 0u : mp_max, e->best_);
+        const uint32_t lim_len = std::max(cut.none_pass ? 0u : cut.mp_max, e->best_);
         const int k2 = lim_len >= pl.base ? first_le(out + pl.part_off[at.pi], at.k, cnt, lim_len - pl.base) : cnt;
         at.c += (size_t)(k2 - at.k);
         at.k = k2;
@@ -327,13 +328,13 @@ int Engine::ufb_replay_visit(const ScanPlan &pl, Loop &L, uint32_t randomMP, uns
   // (iqtree.cpp:3283-3295 then :3343): a tree that fails leaves _pattern_pars as it is, so every later tree of the climb fails too
   // (-storetrees: unless a known topology gets in past the cut-off)
   // (copies: the bookings below write through pointers the compiler cannot tell from L's fields)
-  const bool ratchet = L.ratchet, store_trees = L.store_trees, none_pass = L.none_pass, grow_refs = !L.worker_books;
-  const uint32_t mp_max = L.mp_max;
+  const bool ratchet = L.ratchet, store_trees = L.store_trees, grow_refs = !L.worker_books;
+  const UfbCutoff cut = L.cut;
   auto book = [&](uint32_t len, bool product, uint32_t cand_code) -> int64_t {
     bool pass;
-    if (!ratchet) pass = !none_pass && len <= mp_max;
+    if (!ratchet) pass = cut.passes(len);
     else {
-      pass = (store_trees || !u.gate_closed) && product && !none_pass && u.stale_len <= mp_max;
+      pass = (store_trees || !u.gate_closed) && product && cut.passes(u.stale_len);
       if (!pass) u.gate_closed = true;
     }
     const uint32_t cur_len = ratchet ? u.stale_len : len;

@@ -189,9 +189,7 @@ int Engine::spr_sweeps_ufboot_pipe(int mintrav, int maxtrav, uint32_t randomMP, 
     __atomic_store_n(u.p_flag_s[B.par].p + 1, 0u, __ATOMIC_RELAXED);
     UCHK(launch_ufb_mid(st_, u.C.p, (size_t)rows_p * (size_t)u.Bp, u.info.p, d_self, B.n_self, host_self ? 0xFFFFFFFFu : 0xFFFFFFFEu, d_evcount, ps,
                         d_out(), d_home, d_pend, B.n_idx, d_cut));
-    for (int pl = 0; pl < u.planes; pl++)
-      UCHK(launch_bitgemm(st_, u.masks.p, rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, 1 << (7 * pl), 1, nullptr, small_batch ? d_cut : nullptr));
-    u.gemm_rows += (uint64_t)rows_p;
+    { int rc2 = ufb_mask_product(u.masks.p, rows_p, u.C.p, kUfbAccumulate, nullptr, small_batch ? d_cut : nullptr); if (rc2) return rc2; }    // (k_ufb_mid has zeroed C)
     B.n_eager = (uint32_t)std::min<size_t>(u.p_ev[B.par].cap, 0xFFFFFFFFu);
     UfbPublishArgs pe;                             // the bookkeeping's inputs
     pe.src[0] = reinterpret_cast<const uint32_t *>(u.rt.p);

@@ -77,6 +77,30 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
       if (first_move_visit) first_move_visit[b] = moved ? (int32_t)move_visit + 1 : 0;     // 1-based index into nodep[], 0 = none
     }
   };
+  // A chunk's extraction (the bound of sample b is R_T[b] itself, a running minimum from there on) and its events into `all`:
+  // output index -> (visit of the sweep, order inside the visit) -- the indices of one prune node rise in the reference's
+  // candidate order, ends[j] = the end (exclusive) of prune node j's index range
+  auto extract_chunk = [&](const std::vector<ScanPlan> &plans, int i, int np, uint32_t n_idx, uint32_t n_parts, uint32_t *d_count) -> int {
+    uint32_t n_ev = 0;
+    const UfbExtract x{u.info.p, d_out(), u.thr.p, u.thr.p + n_parts, nullptr, reinterpret_cast<const uint32_t *>(u.rt.p), d_count, n_idx, 0};
+    int rc = ufb_extract_events(x, n_ev);
+    if (rc || !n_ev) return rc;
+    std::vector<uint32_t> ends((size_t)np);
+    uint32_t run = 0;
+    for (int j = 0; j < np; j++) {
+      const ScanPlan &pl = plans[(size_t)j];
+      if (pl.self_idx >= 0) run = std::max(run, (uint32_t)pl.self_idx + 1u);
+      if (u.snk) for (const Candidate &cd : pl.cands) run = std::max(run, cd.out + 1u);                                     // (host-planned)
+      else for (int pi = 0; pi < pl.n_parts; pi++) run = std::max(run, pl.part_off[pi] + (uint32_t)pl.part_cnt[pi] + 1u);    // (device-walked)
+      ends[(size_t)j] = run;
+    }
+    for (uint32_t k = 0; k < n_ev; k++) {
+      const UfbEvent &e = u.h_ev.p[k];
+      const uint32_t j = (uint32_t)(std::upper_bound(ends.begin(), ends.end(), e.idx) - ends.begin());
+      all.push_back(Ev{e.b, (uint32_t)(i - 1) + j, e.idx, e.s});
+    }
+    return MPF_OK;
+  };
   if (u.snk) {
     // ---- the weighted (-cost) engine: the scans write every tentative tree's per-pattern lengths (k_snk_scan), bit planes of them
     // times the sample weights on the matrix cores = every sample's length of every tentative tree; the current tree's row is
@@ -106,27 +130,9 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
       else UCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(start_), slot(back_[start_]), u.vals.p + (size_t)R * npat, u.vmax.p));
       UCHK(hipMemcpyAsync(u.h_vmax.p, u.vmax.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
       UCHK(hipStreamSynchronize(st_));
-      int K = 1;
-      while (K < 16 && (u.h_vmax.p[0] >> K)) K++;
-      const uint32_t rows = n_idx + 1;
-      const int rows_p = round_up((int)rows, kUfbRowTile);
-      const size_t plane_words = (size_t)rows_p * (size_t)u.Wp_s;
-      UCHK(u.bitp.reserve((size_t)K * plane_words));
-      UCHK(hipMemsetAsync(u.bitp.p, 0, (size_t)K * plane_words * sizeof(uint32_t), st_));
-      for (uint32_t r0 = 0; r0 < rows; r0 += 32768u)
-        UCHK(launch_vals_planes(st_, u.vals.p + (size_t)r0 * npat, std::min(32768u, rows - r0), npat, K, u.bitp.p + (size_t)r0 * u.Wp_s, (uint32_t)rows_p,
-                                (uint32_t)u.Wp_s));
-      UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
-      bool first = true;
-      for (int k = 0; k < K; k++)
-        for (int pl = 0; pl < u.planes; pl++) {
-          UCHK(launch_bitgemm(st_, u.bitp.p + (size_t)k * plane_words, rows_p, u.Wp_s, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p,
-                              (1 << k) << (7 * pl), first ? 0 : 1));
-          first = false;
-        }
-      u.gemm_rows += (uint64_t)rows_p * (uint64_t)K;
-      UCHK(u.rt.reserve((size_t)u.Bp));
-      UCHK(launch_colsum(st_, u.C.p + (size_t)R * u.Bp, 1, u.Bp, u.rt.p));
+      UfbPlanes P;
+      { int rc2 = ufb_vals_planes(u.vals.p, n_idx + 1, u.h_vmax.p[0], P); if (rc2) return rc2; }
+      { int rc2 = ufb_weighted_product(P, P.rows_p, nullptr, R); if (rc2) return rc2; }
       if (!have_rt) {
         UCHK(u.h_rt.reserve((size_t)u.Bp));
         UCHK(hipMemcpyAsync(u.h_rt.p, u.rt.p, (size_t)u.Bl * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
@@ -137,14 +143,8 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
       if (n_idx == 0) continue;
       // per output index: (row, prune node of the chunk) for the candidates; the current tree's slots take no part
       hinfo.assign((size_t)n_idx, make_uint2(0u, 0xFFFFFFFFu));
-      std::vector<uint32_t> ends((size_t)np);
-      uint32_t run = 0;
-      for (int j = 0; j < np; j++) {
-        const ScanPlan &pl = plans[(size_t)j];
-        if (pl.self_idx >= 0) run = std::max(run, (uint32_t)pl.self_idx + 1u);
-        for (const Candidate &cd : pl.cands) { hinfo[cd.out] = make_uint2(cd.out, (uint32_t)j); run = std::max(run, cd.out + 1u); }
-        ends[(size_t)j] = run;
-      }
+      for (int j = 0; j < np; j++)
+        for (const Candidate &cd : plans[(size_t)j].cands) hinfo[cd.out] = make_uint2(cd.out, (uint32_t)j);
       const uint32_t n_parts = (uint32_t)np;
       const size_t o_cnt = (size_t)2 * n_parts;
       small.assign(o_cnt + 1, 0u);
@@ -153,35 +153,9 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
       std::memcpy(u.h_small.p, small.data(), small.size() * sizeof(uint32_t));
       UCHK(u.thr.reserve(small.size() + 4));
       UCHK(u.info.reserve((size_t)n_idx));
-      const uint32_t nch = ufb_chunks(n_idx);
-      UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
-      UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
-      if (u.ev.cap == 0) { UCHK(u.ev.reserve(1u << 18)); UCHK(u.h_ev.reserve(1u << 18)); }
       UCHK(hipMemcpyAsync(u.thr.p, u.h_small.p, small.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
       UCHK(hipMemcpyAsync(u.info.p, hinfo.data(), (size_t)n_idx * sizeof(uint2), hipMemcpyHostToDevice, st_));
-      uint32_t *d_evcount = u.thr.p + o_cnt;
-      uint32_t n_ev = 0;
-      for (bool again = false;; again = true) {
-        if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
-        UCHK(launch_ufb_events(st_, u.info.p, d_out(), u.thr.p, u.thr.p + n_parts, nullptr, u.C.p, u.Bp, u.Bl, u.rt.p,
-                               reinterpret_cast<const uint32_t *>(u.rt.p), n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, 0));
-        UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-        UCHK(hipStreamSynchronize(st_));
-        n_ev = u.h_small.p[0];
-        if (n_ev <= u.ev.cap) break;
-        UCHK(u.ev.reserve((size_t)n_ev));
-        UCHK(u.h_ev.reserve((size_t)n_ev));
-      }
-      if (n_ev) {
-        UCHK(u.h_ev.reserve((size_t)n_ev));
-        UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_ev * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-        UCHK(hipStreamSynchronize(st_));
-        for (uint32_t k = 0; k < n_ev; k++) {
-          const UfbEvent &e = u.h_ev.p[k];
-          const uint32_t j = (uint32_t)(std::upper_bound(ends.begin(), ends.end(), e.idx) - ends.begin());
-          all.push_back(Ev{e.b, (uint32_t)(i - 1) + j, e.idx, e.s});
-        }
-      }
+      { int rc2 = extract_chunk(plans, i, np, n_idx, n_parts, u.thr.p + o_cnt); if (rc2) return rc2; }
     }
     replay();
     u.rt_valid = false;
@@ -234,55 +208,16 @@ int Engine::ufboot_refine_sweep(int maxtrav, const int32_t *tie_seeds, uint32_t 
     std::memcpy(u.h_small.p, small.data(), small.size() * sizeof(uint32_t));
     UCHK(u.thr.reserve(small.size() + 4));
     UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
-    const uint32_t nch = ufb_chunks(n_idx);
-    UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
-    UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
-    if (u.ev.cap == 0) { UCHK(u.ev.reserve(1u << 18)); UCHK(u.h_ev.reserve(1u << 18)); }
     UCHK(hipMemcpyAsync(u.thr.p, u.h_small.p, small.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
     // (the current tree's own slots take no part: its length under sample b IS the bound)
     UCHK(launch_ufb_self(st_, u.info.p, u.thr.p + o_self, (uint32_t)self_list.size(), 0xFFFFFFFFu));
     if (timing_) UCHK(hipEventRecord(ev2_, st_));
-    for (int pl = 0; pl < u.planes; pl++)
-      UCHK(launch_bitgemm(st_, u.masks.p, rows_p, g_.Wp, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p, 1 << (7 * pl), pl > 0, nullptr));
-    u.gemm_rows += (uint64_t)rows_p;
+    { int rc2 = ufb_mask_product(u.masks.p, rows_p, u.C.p, kUfbOverwrite); if (rc2) return rc2; }
     if (timing_) UCHK(hipEventRecord(ev3_, st_));
-    uint32_t *d_evcount = u.thr.p + o_cnt;
-    uint32_t n_ev = 0;
-    for (bool again = false;; again = true) {
-      if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
-      // the bound of sample b: the current tree's length under its weights, R_T[b] -- a running minimum from there on
-      UCHK(launch_ufb_events(st_, u.info.p, d_out(), u.thr.p, u.thr.p + n_parts, nullptr, u.C.p, u.Bp, u.Bl, u.rt.p,
-                             reinterpret_cast<const uint32_t *>(u.rt.p), n_idx, u.cmin.p, u.pre.p, u.ev.p, (uint32_t)u.ev.cap, d_evcount, 0));
-      UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-      UCHK(hipStreamSynchronize(st_));
-      n_ev = u.h_small.p[0];
-      if (n_ev <= u.ev.cap) break;
-      UCHK(u.ev.reserve((size_t)n_ev));
-      UCHK(u.h_ev.reserve((size_t)n_ev));
-    }
+    { int rc2 = extract_chunk(plans, i, np, n_idx, n_parts, u.thr.p + o_cnt); if (rc2) return rc2; }
     if (timing_) {
       float ms = 0;
       if (hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) u.gemm_ms += ms;
-    }
-    if (n_ev) {
-      UCHK(u.h_ev.reserve((size_t)n_ev));
-      UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_ev * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-      UCHK(hipStreamSynchronize(st_));
-      // output index -> (visit of the sweep, order inside the visit): the indices of one prune node's parts rise in the
-      // reference's candidate order
-      std::vector<uint32_t> ends((size_t)np);            // end (exclusive) of prune node j's index range
-      uint32_t run = 0;
-      for (int j = 0; j < np; j++) {
-        const ScanPlan &pl = plans[(size_t)j];
-        if (pl.self_idx >= 0) run = std::max(run, (uint32_t)pl.self_idx + 1u);
-        for (int pi = 0; pi < pl.n_parts; pi++) run = std::max(run, pl.part_off[pi] + (uint32_t)pl.part_cnt[pi] + 1u);
-        ends[(size_t)j] = run;
-      }
-      for (uint32_t k = 0; k < n_ev; k++) {
-        const UfbEvent &e = u.h_ev.p[k];
-        const uint32_t j = (uint32_t)(std::upper_bound(ends.begin(), ends.end(), e.idx) - ends.begin());
-        all.push_back(Ev{e.b, (uint32_t)(i - 1) + j, e.idx, e.s});
-      }
     }
   }
   replay();

@@ -78,11 +78,8 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
         for (const Candidate &cd : pl.cands) m = std::min(m, out[cd.out]);
         if (m < randomMP) { jstar = j; break; }
       }
-      const bool have_cut = u.logl_cutoff != 0.0;
-      const double lim = -u.logl_cutoff + 1e-4;
-      const uint32_t mp_max = have_cut ? (lim <= 0.0 ? 0u : (uint32_t)std::ceil(lim) - 1u) : UINT32_MAX;
-      const bool none_pass = have_cut && lim <= 0.0;
-      const bool skip_product = store_trees ? false : ratchet ? (u.gate_closed || none_pass) : none_pass;
+      const UfbCutoff cut = ufb_cutoff(u.logl_cutoff);
+      const bool skip_product = store_trees ? false : ratchet ? (u.gate_closed || cut.none_pass) : cut.none_pass;
       bool have_C = false;
       events.clear();
       if (!skip_product) {
@@ -93,36 +90,18 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
         else UCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(start_), slot(back_[start_]), u.vals.p + (size_t)R * npat, u.vmax.p));
         UCHK(hipMemcpyAsync(u.h_vmax.p, u.vmax.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
         UCHK(hipStreamSynchronize(st_));
-        int K = 1;
-        while (K < 16 && (u.h_vmax.p[0] >> K)) K++;
         const uint32_t rows = n_idx + 1;
-        const int rows_p = round_up((int)rows, kUfbRowTile);
-        const size_t plane_words = (size_t)rows_p * (size_t)u.Wp_s;
-        UCHK(u.bitp.reserve((size_t)K * plane_words));
-        UCHK(hipMemsetAsync(u.bitp.p, 0, (size_t)K * plane_words * sizeof(uint32_t), st_));
-        for (uint32_t r0 = 0; r0 < rows; r0 += 32768u)                  // (grid.y limit)
-          UCHK(launch_vals_planes(st_, u.vals.p + (size_t)r0 * npat, std::min(32768u, rows - r0), npat, K, u.bitp.p + (size_t)r0 * u.Wp_s, (uint32_t)rows_p,
-                                  (uint32_t)u.Wp_s));
-        UCHK(u.C.reserve((size_t)rows_p * (size_t)u.Bp));
-        if (timing_) UCHK(hipEventRecord(ev2_, st_));
-        bool first = true;
-        for (int k = 0; k < K; k++)
-          for (int pl = 0; pl < u.planes; pl++) {
-            UCHK(launch_bitgemm(st_, u.bitp.p + (size_t)k * plane_words, rows_p, u.Wp_s, u.wt.p + (size_t)pl * u.plane_bytes, u.Bp, u.C.p,
-                                (1 << k) << (7 * pl), first ? 0 : 1));
-            first = false;
-          }
-        if (timing_) UCHK(hipEventRecord(ev3_, st_));
-        u.gemm_rows += (uint64_t)rows_p * (uint64_t)K;
-        UCHK(u.rt.reserve((size_t)u.Bp));
-        UCHK(launch_colsum(st_, u.C.p + (size_t)R * u.Bp, 1, u.Bp, u.rt.p));       // R_T = the current tree's own row
+        UfbPlanes P;
+        { int rc2 = ufb_vals_planes(u.vals.p, rows, u.h_vmax.p[0], P); if (rc2) return rc2; }
+        const int rows_p = P.rows_p;
+        { int rc2 = ufb_weighted_product(P, rows_p, nullptr, R); if (rc2) return rc2; }
         UCHK(u.h_rt.reserve((size_t)u.Bp));
         UCHK(hipMemcpyAsync(u.h_rt.p, u.rt.p, (size_t)u.Bl * sizeof(int32_t), hipMemcpyDeviceToHost, st_));    // synchronised below
         have_C = true;
         // ---- per output index: (row, part) for candidates of plans [0, jstar], the current tree's slots, everything else off
         uint32_t n_parts = 0;
         hinfo.assign((size_t)n_idx, make_uint2(0u, 0xFFFFFFFFu));
-        const bool self_pass = ratchet || store_trees || randomMP <= mp_max;
+        const bool self_pass = ratchet || store_trees || cut.passes(randomMP);
         for (int j = 0; j <= jstar; j++) {
           const ScanPlan &pl = plans[(size_t)j];
           // (asym: the visit's slot is a row of its own -- it takes part like a candidate, its cost the length at that edge)
@@ -135,7 +114,7 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
         const size_t o_cnt = (size_t)2 * n_parts + (size_t)u.Bp;   // the event counter: a zero word of this upload
         small.assign(o_cnt + 1, 0u);
         for (uint32_t d = 0; d < n_parts; d++) {
-          small[d] = (!have_cut || ratchet || store_trees) ? UINT32_MAX : mp_max + 1u;            // max cost + 1 (costs are full lengths here)
+          small[d] = (ratchet || store_trees) ? UINT32_MAX : cut.part_threshold(0u);            // max cost + 1 (costs are full lengths here)
           small[n_parts + d] = R;
         }
         for (int c2 = 0; c2 < u.Bl; c2++) small[(size_t)2 * n_parts + (size_t)c2] = ufb_event_bound((uint32_t)u.ids[(size_t)c2]);
@@ -143,11 +122,6 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
         std::memcpy(u.h_small.p, small.data(), small.size() * sizeof(uint32_t));
         UCHK(u.thr.reserve(small.size() + 4));
         UCHK(u.info.reserve((size_t)std::max<uint32_t>(n_idx, 1u)));
-        const uint32_t nch = ufb_chunks(std::max<uint32_t>(n_idx, 1u));
-        UCHK(u.cmin.reserve((size_t)nch * (size_t)u.Bp));
-        UCHK(u.pre.reserve((size_t)nch * (size_t)u.Bp));
-        UCHK(u.evcount.reserve(4));
-        if (u.ev.cap == 0) { UCHK(u.ev.reserve(1u << 18)); UCHK(u.h_ev.reserve(1u << 18)); }
         UCHK(hipMemcpyAsync(u.thr.p, u.h_small.p, small.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
         if (n_idx) UCHK(hipMemcpyAsync(u.info.p, hinfo.data(), (size_t)n_idx * sizeof(uint2), hipMemcpyHostToDevice, st_));
         const uint32_t *d_thr = u.thr.p, *d_home = u.thr.p + n_parts, *d_best = u.thr.p + 2 * n_parts;
@@ -157,32 +131,13 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
           UCHK(launch_ufb_column(st_, u.C.p, u.Bp, oc, rows, u.d_col.p));
           UCHK(hipMemcpyAsync(u.h_col.p, u.d_col.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
         }
-        uint32_t n_ev = 0, n_eager = 0;
-        uint32_t *d_evcount = u.thr.p + o_cnt;
-        for (bool again = false; n_idx; again = true) {
-          if (again) UCHK(hipMemsetAsync(d_evcount, 0, sizeof(uint32_t), st_));
-          UCHK(launch_ufb_events(st_, u.info.p, d_out(), d_thr, d_home, nullptr, u.C.p, u.Bp, u.Bl, u.rt.p, d_best, n_idx, u.cmin.p, u.pre.p,
-                                 u.ev.p, (uint32_t)u.ev.cap, d_evcount, (u.topboot || u.distinct || store_trees) ? 1 : 0));
-          UCHK(hipMemcpyAsync(u.h_small.p, d_evcount, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-          n_eager = (uint32_t)std::min<size_t>(u.ev.cap, 4096);     // (as in spr_sweeps_ufboot: one round trip for a small batch)
-          UCHK(u.h_ev.reserve((size_t)n_eager));
-          UCHK(hipMemcpyAsync(u.h_ev.p, u.ev.p, (size_t)n_eager * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-          UCHK(hipStreamSynchronize(st_));
-          n_ev = u.h_small.p[0];
-          if (n_ev <= u.ev.cap) break;
-          UCHK(u.ev.reserve((size_t)n_ev));
-          UCHK(u.h_ev.reserve((size_t)n_ev));
-        }
-        if (!n_idx) UCHK(hipStreamSynchronize(st_));
+        uint32_t n_ev = 0;
+        const UfbExtract x{u.info.p, d_out(), d_thr, d_home, nullptr, d_best, u.thr.p + o_cnt, n_idx, (u.topboot || u.distinct || store_trees) ? 1 : 0};
+        if (n_idx) { int rc2 = ufb_extract_events(x, n_ev); if (rc2) return rc2; }
+        else UCHK(hipStreamSynchronize(st_));
         if (timing_) {
           float ms = 0;
           if (hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) u.gemm_ms += ms;
-        }
-        if (n_ev > n_eager) {
-          if (u.h_ev.cap < (size_t)n_ev) n_eager = 0;
-          UCHK(u.h_ev.reserve((size_t)n_ev));
-          UCHK(hipMemcpyAsync(u.h_ev.p + n_eager, u.ev.p + n_eager, (size_t)(n_ev - n_eager) * sizeof(UfbEvent), hipMemcpyDeviceToHost, st_));
-          UCHK(hipStreamSynchronize(st_));
         }
         events.assign(u.h_ev.p, u.h_ev.p + n_ev);
         for (UfbEvent &ev : events) ev.b = (uint32_t)u.ids[(size_t)ev.b];
@@ -197,7 +152,7 @@ int Engine::spr_sweeps_ufboot_snk(int mintrav, int maxtrav, uint32_t randomMP, u
       }
       // ---- host replay in the reference's order
       V.out = out; V.h_rt = u.h_rt.p; V.ep = 0;
-      V.none_pass = none_pass; V.mp_max = mp_max; V.product_self = V.product_cand = have_C;
+      V.cut = cut; V.product_self = V.product_cand = have_C;
       bool moved = false;
       int j = i;
       for (; j <= hi && !moved; j++) {
