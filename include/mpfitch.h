@@ -446,6 +446,48 @@ int mpf_place_taxa(mpf_engine *e, int32_t n_inner, const int32_t *first, const i
    (record slot = list position) and call mpf_set_tree to climb from it. */
 int mpf_iq_parsimony_tree(mpf_engine *e, uint64_t *tie_state, int32_t *order, int32_t *first, int32_t *nbr,
                           uint32_t *length_per_step, uint32_t *score);
+/* Tree bisection and reconnection (TBR) on the engine's tree.  THERE IS NO REFERENCE FUNCTION: MPBoot 1.1.1 has SPR and NNI only.
+   A visit is a record rec, its edge (rec, q = back[rec]) and a radius maxtrav in 1 .. 255.  Cut the edge.  g_recs lists the
+   branches of rec's part and f_recs those of q's part, each as rearrangeParsimony's one side enumerates them with mintrav = 1
+   (addTraverseParsimony's order, sprparsimony.cpp:2208-2218; for q's part that is one level nearer than the 2 the SPR scan starts
+   from).  cost is the (1 + n_f) x (1 + n_g) matrix, row-major, of the length of the tree that joins the middle of f_recs[i - 1] to
+   the middle of g_recs[j - 1]; index 0 of either side means the part's own root.  So row 0 is testInsertParsimony
+   (sprparsimony.cpp:2106-2188) of rec on every g_recs[j - 1], the p side of mpf_spr_scan; column 0 is the q side where the lists
+   coincide (depth >= 2; rearrangeParsimony, sprparsimony.cpp:2259-2376); cost[0][0] is the current length.  The tree of an entry is
+   apply_spr(apply_spr(back, rec, g), q, f), a step whose record is "none" skipped.  All directional views are resident, so an
+   entry costs one popcount over two root sets: k_tbr_roots writes the root sets R(.) of both parts into a scratch store,
+   k_tbr_costs forms the matrix, cost = sc[rec] + sc[q] + #sites where R_q(f) and R_rec(g) share no state (tbr.hip).
+   Fitch engine only: a weighted (-cost) engine, and an engine with a UFBoot tracker attached (nothing would be booked), answer
+   MPF_E_UNSUPPORTED.  maxtrav outside 1 .. 255: MPF_E_INVALID.  Options: "tbr_tile" (0 = per visit from the padded outputs | 1 =
+   narrow, 4 x 16 per workgroup | 2 = wide, 64 x 64 for 4 state rows, 32 x 32 for 20 and 32), "tbr_chunk_vectors" (the most
+   root-set vectors a chunk of a sweep may hold, 0 = 256 MiB worth; a visit that needs more is a chunk of its own; results do not
+   depend on it), read-only "tbr_chunks" (chunks of the last sweep), "tbr_launches" and, under "timing", "tbr_kernel_ns".
+
+   mpf_tbr_scan: one visit's lists and matrix.  *n_f and *n_g are always set; the lists are filled if cap_f >= *n_f and
+   cap_g >= *n_g, and cost (may be NULL: the lists alone) only then, as mpf_spr_sweep_costs fills mp.  The tree does not change. */
+int mpf_tbr_scan(mpf_engine *e, int32_t rec, int32_t maxtrav, int32_t cap_f, int32_t cap_g, int32_t *f_recs, int32_t *g_recs,
+                 uint32_t *cost, int32_t *n_f, int32_t *n_g);
+/* No reference function (above).  The best of every visit of a sweep over the records of mpf_get_node_order, in that order (the SPR
+   sweep's order, sprparsimony.cpp:3298): the minimum over all entries of the visit's matrix except [0][0], ties to the lowest
+   row-major index (k_tbr_best); best_f / best_g = its records, -1 for "none" (row 0 / column 0: an SPR move of
+   sprparsimony.cpp:2106-2188, :2208-2218, :2259-2376).  A visit with a 1 x 1 matrix has best_cost 0xFFFFFFFF and records -1.  All
+   three arrays have 2 n - 2 entries; only these three words per visit leave the device.  *n_pairs (may be NULL) = matrix entries
+   scored.  The sweep runs in chunks of consecutive visits ("tbr_chunk_vectors").  The tree does not change. */
+int mpf_tbr_sweep_best(mpf_engine *e, int32_t maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs);
+/* No reference function (above; with f_rec = -1 or g_rec = -1 it is one removeNodeParsimony + insertParsimony, the move of
+   sprparsimony.cpp:2106-2188, :2208-2218, :2259-2376).  Edits the engine's tree to apply_spr(apply_spr(back, rec, g_rec), back[rec],
+   f_rec) and returns its length: equal in every observable to mpf_set_tree of the edited back[] followed by mpf_score_tree.  A pair
+   that is not in the visit's lists at radius 255: MPF_E_INVALID, tree unchanged. */
+int mpf_apply_tbr(mpf_engine *e, int32_t rec, int32_t f_rec, int32_t g_rec, uint32_t *score);
+/* No reference function (above; a climb that only ever finds its best in row 0 or column 0 makes the moves of
+   sprparsimony.cpp:2106-2188, :2208-2218, :2259-2376).  Steepest descent: take mpf_tbr_sweep_best's lowest cost (the lowest visit
+   index among equals) and apply it if it is strictly below the current length, otherwise stop.  max_moves <= 0: no limit.
+   Deterministic: draws nothing from the tie stream and leaves it untouched.  *score = final length, *n_moves = moves made; they are
+   read back with mpf_get_tbr_moves. */
+int mpf_optimize_tbr(mpf_engine *e, int32_t maxtrav, int32_t max_moves, uint32_t *score, int32_t *n_moves);
+/* moves of the last mpf_optimize_tbr: (rec, f_rec, g_rec, length after the move); protocol of mpf_get_moves */
+int mpf_get_tbr_moves(const mpf_engine *e, int32_t cap, int32_t *rec, int32_t *f_rec, int32_t *g_rec, uint32_t *score,
+                      int32_t *n_moves);
 /* The summary of a -bb run: split supports and the bootstrap consensus tree.  The reference weights the booked trees by the samples
    that point to them (IQTree::summarizeBootstrap, iqtree.cpp:4020-4165), turns every tree into Split objects through its Newick
    string and counts them in a hash map (MTreeSet::convertSplits, mtreeset.cpp:288-470), and builds the consensus from the counted

@@ -454,7 +454,62 @@ int mpf_insertion_costs(mpf_engine *e, int32_t n_inner, const int32_t *first, co
   return MPF_OK;
 }
 
-int mpf_place_taxa(mpf_engine *e, int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_query,
+// ---- TBR (host/tbr.cpp): no reference function
+int mpf_tbr_scan(mpf_engine *e, int32_t rec, int32_t maxtrav, int32_t cap_f, int32_t cap_g, int32_t *f_recs, int32_t *g_recs, uint32_t *cost,
+                 int32_t *n_f, int32_t *n_g)
+{
+  NEED(e);
+  if (!n_f || !n_g) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<int32_t> f, g;
+  std::vector<uint32_t> c;
+  // the lists first: the matrix is made only where it can be handed over
+  int rc = e->eng.tbr_scan(rec, maxtrav, f, g, nullptr);
+  if (rc) return rc;
+  *n_f = (int32_t)f.size();
+  *n_g = (int32_t)g.size();
+  if ((int64_t)cap_f < (int64_t)f.size() || (int64_t)cap_g < (int64_t)g.size()) return MPF_OK;
+  if ((!f.empty() && !f_recs) || (!g.empty() && !g_recs)) { set_error("null output"); return MPF_E_INVALID; }
+  if (cost) {
+    rc = e->eng.tbr_scan(rec, maxtrav, f, g, &c);
+    if (rc) return rc;
+    std::memcpy(cost, c.data(), c.size() * sizeof(uint32_t));
+  }
+  if (!f.empty()) std::memcpy(f_recs, f.data(), f.size() * sizeof(int32_t));
+  if (!g.empty()) std::memcpy(g_recs, g.data(), g.size() * sizeof(int32_t));
+  return MPF_OK;
+}
+
+int mpf_tbr_sweep_best(mpf_engine *e, int32_t maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs)
+{
+  NEED(e);
+  if (!best_cost || !best_f || !best_g) { set_error("null output"); return MPF_E_INVALID; }
+  return e->eng.tbr_sweep_best(maxtrav, best_cost, best_f, best_g, n_pairs);
+}
+
+int mpf_apply_tbr(mpf_engine *e, int32_t rec, int32_t f_rec, int32_t g_rec, uint32_t *score) { NEED(e); return e->eng.apply_tbr(rec, f_rec, g_rec, score); }
+
+int mpf_optimize_tbr(mpf_engine *e, int32_t maxtrav, int32_t max_moves, uint32_t *score, int32_t *n_moves)
+{
+  NEED(e);
+  return e->eng.optimize_tbr(maxtrav, max_moves, score, n_moves);
+}
+
+int mpf_get_tbr_moves(const mpf_engine *e, int32_t cap, int32_t *rec, int32_t *f_rec, int32_t *g_rec, uint32_t *score, int32_t *n_moves)
+{
+  NEED(e);
+  const auto &mv = e->eng.tbr_moves();
+  if (n_moves) *n_moves = (int32_t)mv.size();
+  const size_t k = std::min((size_t)std::max(cap, 0), mv.size());
+  for (size_t i = 0; i < k; i++) {
+    if (rec) rec[i] = mv[i].rec;
+    if (f_rec) f_rec[i] = mv[i].f_rec;
+    if (g_rec) g_rec[i] = mv[i].g_rec;
+    if (score) score[i] = mv[i].score;
+  }
+  return MPF_OK;
+}
+
+int mpf_place_taxa(mpf_engine *e,int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_query,
                    const int32_t *query_taxa, int32_t *best_branch, int32_t *best_node1, int32_t *best_node2, uint32_t *best_length,
                    uint32_t *tree_length)
 {

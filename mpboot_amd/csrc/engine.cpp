@@ -1904,6 +1904,8 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "grow_fault") { grow_fault_ = v; return MPF_OK; }
   if (key == "nni_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("nni_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } nni_vw_ = (int)v; return MPF_OK; }
   if (key == "brlen_tile") { if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4) { set_error("brlen_tile: -1 (from the geometry), 0 (word-major copy where current, else one word per lane), 1, 2 or 4"); return MPF_E_INVALID; } brlen_vw_ = (int)v; return MPF_OK; }
+  if (key == "tbr_tile") { if (v < 0 || v > 2) { set_error("tbr_tile: 0 (per visit, from the padded outputs), 1 (narrow: 4 x 16) or 2 (wide)"); return MPF_E_INVALID; } tbr_tile_ = (int)v; return MPF_OK; }
+  if (key == "tbr_chunk_vectors") { if (v < 0) { set_error("tbr_chunk_vectors: the most root-set vectors of a chunk, 0 = 256 MiB worth"); return MPF_E_INVALID; } tbr_chunk_vectors_ = v; return MPF_OK; }
   if (key == "place_tile") { if (v < 0 || v > 2) { set_error("place_tile: 0 (from the number of outputs), 1 (narrow: 4 queries x 16 branches) or 2 (wide)"); return MPF_E_INVALID; } place_tile_ = (int)v; return MPF_OK; }
   if (key == "place_weighted") { place_weighted_ = v ? 1 : 0; return MPF_OK; }   // taxon insertion under -cost (host/place.cpp); no effect on a Fitch engine
   if (key == "poly_tile") { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32) { set_error("poly_tile: 0 (from the row length), 4, 8, 16 or 32 words per workgroup"); return MPF_E_INVALID; } poly_tile_ = (int)v; return MPF_OK; }
@@ -2032,6 +2034,11 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "brlen_launches") *v = (int64_t)brlen_launches_;
   else if (key == "brlen_kernel_ns") *v = (int64_t)brlen_kernel_ns_;
   else if (key == "poly_tile") *v = poly_tile_;
+  else if (key == "tbr_tile") *v = tbr_tile_;
+  else if (key == "tbr_chunk_vectors") *v = tbr_chunk_vectors_;
+  else if (key == "tbr_chunks") *v = tbr_chunks_;
+  else if (key == "tbr_launches") *v = (int64_t)tbr_launches_;
+  else if (key == "tbr_kernel_ns") *v = (int64_t)tbr_kernel_ns_;
   else if (key == "place_tile") *v = place_tile_;
   else if (key == "place_weighted") *v = place_weighted_;
   else if (key == "place_shape") *v = place_shape_;

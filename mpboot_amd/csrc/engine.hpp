@@ -35,7 +35,11 @@
 #include "ufboot.hpp"
 #include "splits.hpp"
 
+namespace tbrplan { struct Visit; }                // host/tbr_plan.hpp (read by host/tbr.cpp alone)
+
 namespace mpf {
+
+struct TbrBuffers;                                 // host/tbr.cpp
 
 void set_error(const std::string &msg);
 const std::string &last_error();
@@ -385,6 +389,19 @@ class Engine {
   // PhyloTree::computeParsimonyTree (phylotree.cpp:1243-1320) over order[0 .. n) (1-based taxa): n - 3 exhaustive Q = 1 placements
   int parsimony_tree(const int32_t *order, std::vector<int32_t> &first, std::vector<int32_t> &nbr, uint32_t *length_per_step);
 
+  // ---- TBR neighbourhood (host/tbr.cpp, tbr.hip; the plan of a visit: host/tbr_plan.hpp).  No reference function: MPBoot has SPR
+  // and NNI only.  A visit cuts the edge (rec, back[rec]); f lists the branches of back[rec]'s part, g those of rec's part, both as
+  // one_side of plan_scan enumerates them with mintrav = 1; cost (null: the lists alone) [(1 + |f|) x (1 + |g|)], index 0 = the
+  // part's own root, so row 0 and column 0 are the SPR tests and cost[0][0] is the tree as it is.  Fitch engine without a tracker only
+  struct TbrMove { int32_t rec, f_rec, g_rec; uint32_t score; };
+  int tbr_scan(int rec, int maxtrav, std::vector<int32_t> &f, std::vector<int32_t> &g, std::vector<uint32_t> *cost);
+  // the best of every visit of a sweep in node_order(): the first minimum of its matrix in row-major order, [0][0] left out (cost
+  // 0xFFFFFFFF, records -1 where the matrix is 1 x 1); records -1 for index 0
+  int tbr_sweep_best(int maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs);
+  int apply_tbr(int rec, int f_rec, int g_rec, uint32_t *score);      // == set_tree(the edited back[]) + score_tree
+  int optimize_tbr(int maxtrav, int max_moves, uint32_t *score, int32_t *n_moves);      // steepest descent, no tie draw
+  const std::vector<TbrMove> &tbr_moves() const { return tbr_moves_; }
+
   // ---- the summary of a -bb run (host/splits.cpp, splits.hip; reference IQTree::summarizeBootstrap, MTreeSet::convertSplits,
   // computeConsensusTree): the splits of a weighted set of complete trees counted exactly on the device, the supports of a target
   // tree's branches, the consensus tree as neighbour lists.  Stateless towards the engine's own tree and its vectors
@@ -714,6 +731,18 @@ class Engine {
   uint64_t place_launches_ = 0, place_kernel_ns_ = 0;
   DevBuf<uint32_t> d_place_q_, d_place_out_;
   PinBuf<uint32_t> h_place_q_, h_place_out_;
+  // TBR (host/tbr.cpp): option "tbr_tile" (0 = per visit from the padded outputs, 1 = narrow, 2 = wide; host/tbr_plan.hpp),
+  // "tbr_chunk_vectors" (the most root-set vectors a chunk of a sweep may hold; 0 = 256 MiB worth), read-only "tbr_chunks" (chunks of
+  // the last sweep), "tbr_launches" (k_tbr_costs launches) and, under "timing", "tbr_kernel_ns" (HIP-event time of the three kernels)
+  int tbr_tile_ = 0, tbr_chunks_ = 0;
+  int64_t tbr_chunk_vectors_ = 0;
+  uint64_t tbr_launches_ = 0, tbr_kernel_ns_ = 0;
+  std::vector<TbrMove> tbr_moves_;
+  std::shared_ptr<TbrBuffers> tbr_buf_;          // (defined in host/tbr.cpp: this header does not read tbr.hpp)
+  struct TbrBest { uint32_t cost, row, col; };
+  int tbr_check(const char *what, int maxtrav);
+  int tbr_run(const int32_t *recs, size_t count, int maxtrav, std::vector<tbrplan::Visit> &vis, std::vector<uint32_t> *matrix,
+              std::vector<TbrBest> *best, uint64_t *n_pairs);
 
   int addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *insert_per_step);
   void apply_move(int remove_rec, int insert_rec);

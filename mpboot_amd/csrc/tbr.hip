@@ -1,0 +1,292 @@
+// tbr.hip -- the TBR neighbourhood on gfx950: root sets of both parts of a cut edge, and the pair product over them (host/tbr.cpp).
+//
+// No reference function: MPBoot has SPR and NNI only.  With every directional view resident, the tree that joins the middle of branch
+// f of q's part to the middle of branch g of p's part costs one popcount over two root sets (tbr.hpp); row 0 and column 0 of a
+// visit's matrix are the insertion tests of rearrangeParsimony (sprparsimony.cpp:2259-2376).
+//
+//   k_tbr_roots  one wave per (side, tile of 64 site words) walks the side's chain program; U per depth in LDS, beyond tbr_lds_levels
+//                in HBM scratch as k_scan_deep keeps its levels; every chain step stores fitch(U, vec[own]) into the scratch store
+//   k_tbr_costs  k_place_costs' skeleton (place.hip) over the and-or algebra of PlaceFitch, without the join: a workgroup owns a tile
+//                of F rows x G columns of ONE visit and walks the row of words in slices through LDS, the next slice's loads issued
+//                before this slice's arithmetic.  Index 0 of either side reads the resident vector, the rest the scratch store:
+//                absolute 64-bit row pointers.  The launch is a flat list of (visit, F tile, G tile) items.  One writer per output
+//   k_tbr_best   one wave per visit: the first minimum of its matrix, [0][0] left out
+// Padding bits are set in every state row of every resident vector, so they are in every U and every root set, and always match.
+#include "tbr.hpp"
+
+namespace mpf {
+
+namespace {
+
+// r = fitch(a, b) in place of a: the intersection where it is not empty, the union elsewhere
+template <int S>
+__device__ __forceinline__ void fitch_into(uint32_t (&a)[S], const uint32_t (&b)[S])
+{
+  uint32_t any = 0u;
+#pragma unroll
+  for (int s = 0; s < S; s++) any |= a[s] & b[s];
+#pragma unroll
+  for (int s = 0; s < S; s++) a[s] = (a[s] & b[s]) | (~any & (a[s] | b[s]));
+}
+
+template <int S, int LD>
+__global__ __launch_bounds__(64) void k_tbr_roots(const uint32_t *__restrict__ vec, const tbrplan::Op *__restrict__ ops,
+                                                  const TbrSide *__restrict__ sides, int tiles, int Wp, uint32_t *__restrict__ store,
+                                                  uint32_t *__restrict__ deep)
+{
+  __shared__ uint32_t su[LD * S * 64];               // [level][state row][lane]: a lane reads and writes its own column only, no barrier
+  const int lane = (int)threadIdx.x;
+  const size_t side = (size_t)blockIdx.x / (size_t)tiles, tile = (size_t)blockIdx.x % (size_t)tiles;
+  const size_t w = tile * 64 + (size_t)lane, row = (size_t)Wp, vsz = (size_t)S * row;
+  if (w >= row) return;                              // (Wp is a multiple of 32: the last tile may be half full)
+  const TbrSide sd = sides[side];
+  uint32_t *dl = deep + sd.deep_off + tile * (size_t)sd.deep_levels * (size_t)(S * 64) + (size_t)lane;
+  auto level = [&](int d) -> uint32_t * { return d < LD ? &su[d * S * 64 + lane] : dl + (size_t)(d - LD) * (size_t)(S * 64); };
+  for (uint32_t i = sd.op_begin; i < sd.op_end; i++) {
+    const tbrplan::Op o = ops[i];
+    const int d = (int)(o.meta & 255u);
+    uint32_t u[S], x[S];
+    if ((o.meta >> 16) == (uint32_t)tbrplan::OP_ROOT) {
+      const uint32_t *v = vec + (size_t)o.own * vsz + w;
+      uint32_t *l0 = level(0);
+#pragma unroll
+      for (int s = 0; s < S; s++) l0[s * 64] = v[(size_t)s * row];
+      continue;
+    }
+    const uint32_t *vs = vec + (size_t)o.sib * vsz + w, *vo = vec + (size_t)o.own * vsz + w;
+    const uint32_t *up = level(d - 1);
+#pragma unroll
+    for (int s = 0; s < S; s++) { u[s] = up[s * 64]; x[s] = vs[(size_t)s * row]; }
+    fitch_into<S>(u, x);
+#pragma unroll
+    for (int s = 0; s < S; s++) x[s] = vo[(size_t)s * row];
+    uint32_t *ud = level(d);
+#pragma unroll
+    for (int s = 0; s < S; s++) ud[s * 64] = u[s];
+    fitch_into<S>(u, x);
+    uint32_t *r = store + (size_t)o.out * vsz + w;
+#pragma unroll
+    for (int s = 0; s < S; s++) r[(size_t)s * row] = u[s];
+  }
+}
+
+// out[at + i ng + j] = base + 32 len - the sum over the row's words of popc(OR over the state rows of (row i of F & row j of G))
+template <int S, int TQ, int TB, int RQ, int RB, int KS, int KT>
+__global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ vec, const uint32_t *__restrict__ store,
+                                                   const TbrVisit *__restrict__ visits, const tbrplan::Item *__restrict__ items, int len_,
+                                                   uint32_t *__restrict__ out)
+{
+  constexpr int TBT = TB / RB, TQT = TQ / RQ;
+  static_assert(TBT * TQT * KT == 256 && TB % RB == 0 && TQ % RQ == 0 && KS % KT == 0, "lane mapping");
+  static_assert(KT == 1 || KT * TQ * TB <= KS * (S * TB + 64 / KS), "the partial sums reuse the column slice");
+  static_assert(64 % KS == 0 && (64 / KS) % 4 == 0, "padding keeps the 16-byte alignment");
+  constexpr int BI = (TB * KS + 255) / 256, QI = (TQ * KS + 255) / 256;      // staged (vector, word) items per lane
+  // [word of the slice][state row][column | row], 64 / KS words of padding behind every word of the slice (place.hip)
+  constexpr int XP = S * TB + 64 / KS, QP = S * TQ + 64 / KS;
+  __shared__ __attribute__((aligned(16))) uint32_t sx[KS * XP];
+  __shared__ __attribute__((aligned(16))) uint32_t sq[KS * QP];
+  const size_t len = (size_t)len_, vsz = (size_t)S * len;
+  const int tid = (int)threadIdx.x;
+  const int tb = tid % TBT, tq = (tid / TBT) % TQT, kt = tid / (TBT * TQT);
+  const tbrplan::Item it = items[blockIdx.x];
+  const TbrVisit vd = visits[it.visit];
+  const int nf = (int)vd.nf, ng = (int)vd.ng, f_lo = (int)it.ft * TQ, g_lo = (int)it.gt * TB;
+
+  const uint32_t *pg[BI], *pf[QI];
+#pragma unroll
+  for (int i = 0; i < BI; i++) {
+    const int idx = tid + 256 * i;
+    const int j = min(g_lo + min(idx / KS, TB - 1), ng - 1);               // (columns past the end repeat the last: loads stay inside)
+    pg[i] = (j == 0 ? vec + (size_t)vd.slot_p * vsz : store + ((size_t)vd.g0 + (size_t)(j - 1)) * vsz) + (size_t)(idx % KS);
+  }
+#pragma unroll
+  for (int i = 0; i < QI; i++) {
+    const int idx = tid + 256 * i;
+    const int f = min(f_lo + min(idx / KS, TQ - 1), nf - 1);
+    pf[i] = (f == 0 ? vec + (size_t)vd.slot_q * vsz : store + ((size_t)vd.f0 + (size_t)(f - 1)) * vsz) + (size_t)(idx % KS);
+  }
+  uint32_t rg[BI][S], rf[QI][S];
+  auto fetch = [&](size_t k0) {
+#pragma unroll
+    for (int i = 0; i < BI; i++)
+      if (tid + 256 * i < TB * KS) {
+#pragma unroll
+        for (int s = 0; s < S; s++) rg[i][s] = pg[i][(size_t)s * len + k0];
+      }
+#pragma unroll
+    for (int i = 0; i < QI; i++)
+      if (tid + 256 * i < TQ * KS) {
+#pragma unroll
+        for (int s = 0; s < S; s++) rf[i][s] = pf[i][(size_t)s * len + k0];
+      }
+  };
+  fetch(0);
+
+  uint32_t acc[RQ][RB];
+#pragma unroll
+  for (int i = 0; i < RQ; i++)
+#pragma unroll
+    for (int j = 0; j < RB; j++) acc[i][j] = 0u;
+
+  for (size_t k0 = 0; k0 < len; k0 += KS) {                  // (a row is whole slices: Wp is a multiple of 32)
+    __syncthreads();                                         // the last slice has been read by everybody
+#pragma unroll
+    for (int i = 0; i < BI; i++) {
+      const int idx = tid + 256 * i;
+      if (idx < TB * KS) {
+        uint32_t *d = &sx[(idx % KS) * XP + idx / KS];
+#pragma unroll
+        for (int s = 0; s < S; s++) d[s * TB] = rg[i][s];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < QI; i++) {
+      const int idx = tid + 256 * i;
+      if (idx < TQ * KS) {
+        uint32_t *d = &sq[(idx % KS) * QP + idx / KS];
+#pragma unroll
+        for (int s = 0; s < S; s++) d[s * TQ] = rf[i][s];
+      }
+    }
+    __syncthreads();
+    if (k0 + KS < len) fetch(k0 + KS);                       // the next slice is on its way while this one is summed
+#pragma unroll 2
+    for (int k = kt; k < KS; k += KT) {
+      uint32_t m[RQ][RB];
+#pragma unroll
+      for (int s = 0; s < S; s++) {
+        uint32_t xv[RB], qv[RQ];
+#pragma unroll
+        for (int j = 0; j < RB; j++) xv[j] = sx[k * XP + s * TB + tb * RB + j];
+#pragma unroll
+        for (int i = 0; i < RQ; i++) qv[i] = sq[k * QP + s * TQ + tq * RQ + i];
+#pragma unroll
+        for (int i = 0; i < RQ; i++)
+#pragma unroll
+          for (int j = 0; j < RB; j++) {
+            const uint32_t t = qv[i] & xv[j];
+            m[i][j] = s == 0 ? t : (m[i][j] | t);
+          }
+      }
+#pragma unroll
+      for (int i = 0; i < RQ; i++)
+#pragma unroll
+        for (int j = 0; j < RB; j++) acc[i][j] += (uint32_t)__popc(m[i][j]);
+    }
+  }
+
+  if constexpr (KT > 1) {
+    // the KT word classes of an output meet in LDS; class 0 adds them up in a fixed order
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < RQ; i++)
+#pragma unroll
+      for (int j = 0; j < RB; j++) sx[(kt * TQ + tq * RQ + i) * TB + tb * RB + j] = acc[i][j];
+    __syncthreads();
+    if (kt != 0) return;
+#pragma unroll
+    for (int i = 0; i < RQ; i++)
+#pragma unroll
+      for (int j = 0; j < RB; j++) {
+        uint32_t s = 0u;
+        for (int c = 0; c < KT; c++) s += sx[(c * TQ + tq * RQ + i) * TB + tb * RB + j];
+        acc[i][j] = s;
+      }
+  }
+  const uint32_t bits = 32u * (uint32_t)len_ + vd.base;      // (the sites of a row of words; the two parts' own lengths)
+#pragma unroll
+  for (int i = 0; i < RQ; i++)
+#pragma unroll
+    for (int j = 0; j < RB; j++) {
+      const int f = f_lo + tq * RQ + i, g = g_lo + tb * RB + j;
+      if (f < nf && g < ng) out[vd.at + (size_t)f * (size_t)ng + (size_t)g] = bits - acc[i][j];
+    }
+}
+
+// one wave per visit: the lowest entry of its matrix behind [0][0] and the lowest row-major index that has it
+__global__ __launch_bounds__(64) void k_tbr_best(const TbrVisit *__restrict__ visits, const uint32_t *__restrict__ out, uint32_t *__restrict__ best)
+{
+  const TbrVisit vd = visits[blockIdx.x];
+  const uint32_t *m = out + vd.at;
+  const size_t count = (size_t)vd.nf * (size_t)vd.ng;
+  uint32_t v = 0xFFFFFFFFu;
+  size_t at = (size_t)-1;
+  for (size_t e = 1 + (size_t)threadIdx.x; e < count; e += 64) {
+    const uint32_t x = m[e];
+    if (at == (size_t)-1 || x < v) { v = x; at = e; }      // (a lane's indices rise: the first of equal values stays)
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t ov = (uint32_t)__shfl_xor((int)v, off, 64);
+    const uint32_t alo = (uint32_t)__shfl_xor((int)(uint32_t)at, off, 64), ahi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)at >> 32), off, 64);
+    const size_t oat = (size_t)(((uint64_t)ahi << 32) | alo);
+    if (oat != (size_t)-1 && (at == (size_t)-1 || ov < v || (ov == v && oat < at))) { v = ov; at = oat; }
+  }
+  if (threadIdx.x == 0) {
+    uint32_t *b = best + 3 * (size_t)blockIdx.x;
+    if (at == (size_t)-1) { b[0] = b[1] = b[2] = 0xFFFFFFFFu; }
+    else { b[0] = v; b[1] = (uint32_t)(at / vd.ng); b[2] = (uint32_t)(at % vd.ng); }
+  }
+}
+
+template <int S, int SHAPE> struct CostShape;
+// (rows, columns, outputs per lane rows x columns, slice, word classes): place_shape's numbers, the unweighted ones
+template <int S> struct CostShape<S, tbrplan::TILE_NARROW> { static constexpr int rq = 4, rb = 1, ks = 16, kt = 16; };
+template <> struct CostShape<4, tbrplan::TILE_WIDE> { static constexpr int rq = 4, rb = 4, ks = 16, kt = 1; };
+template <int S> struct CostShape<S, tbrplan::TILE_WIDE> { static constexpr int rq = 2, rb = 2, ks = 4, kt = 1; };
+
+}  // namespace
+
+size_t tbr_deep_words(const Geometry &g, TbrSide *sides, size_t n_sides)
+{
+  const size_t tiles = ((size_t)g.Wp + 63) / 64;
+  size_t at = 0;
+  for (size_t i = 0; i < n_sides; i++) {
+    sides[i].deep_off = at;
+    at += tiles * (size_t)sides[i].deep_levels * (size_t)g.S * 64;
+  }
+  return at;
+}
+
+hipError_t launch_tbr_roots(hipStream_t st, const Geometry &g, const uint32_t *vec, const tbrplan::Op *ops, const TbrSide *sides, size_t n_sides,
+                            uint32_t *store, uint32_t *deep)
+{
+  if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
+  if (g.sankoff || g.Wp <= 0 || g.Wp % 32) return hipErrorInvalidValue;
+  if (!n_sides) return hipSuccess;
+  const size_t tiles = ((size_t)g.Wp + 63) / 64;
+  if (n_sides * tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  dispatch_states(g.S, [&](auto S) {
+    hipLaunchKernelGGL((k_tbr_roots<S, tbr_lds_levels(S)>), dim3((unsigned)(n_sides * tiles)), dim3(64), 0, st, vec, ops, sides, (int)tiles, g.Wp,
+                       store, deep);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_tbr_costs(hipStream_t st, const Geometry &g, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
+                            const tbrplan::Item *items, size_t n_items, int shape, uint32_t *out)
+{
+  if (!vec) return hipErrorInvalidValue;
+  if (g.sankoff || g.Wp <= 0 || g.Wp % 32 || (shape != tbrplan::TILE_NARROW && shape != tbrplan::TILE_WIDE)) return hipErrorInvalidValue;
+  if (!n_items) return hipSuccess;
+  if (n_items > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  dispatch_states(g.S, [&](auto S) {
+    dispatch_bool(shape == tbrplan::TILE_NARROW, [&](auto NARROW) {
+      constexpr int SH = NARROW ? tbrplan::TILE_NARROW : tbrplan::TILE_WIDE;
+      constexpr tbrplan::TileDims d = tbrplan::tile_dims(S, SH);
+      typedef CostShape<S, SH> C;
+      hipLaunchKernelGGL((k_tbr_costs<S, d.tf, d.tg, C::rq, C::rb, C::ks, C::kt>), dim3((unsigned)n_items), dim3(256), 0, st, vec, store, visits,
+                         items, g.Wp, out);
+    });
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_tbr_best(hipStream_t st, const TbrVisit *visits, size_t n_visits, const uint32_t *out, uint32_t *best)
+{
+  if (!n_visits) return hipSuccess;
+  hipLaunchKernelGGL(k_tbr_best, dim3((unsigned)n_visits), dim3(64), 0, st, visits, out, best);
+  return hipGetLastError();
+}
+
+}  // namespace mpf

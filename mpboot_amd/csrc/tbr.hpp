@@ -1,0 +1,35 @@
+// tbr.hpp -- launch interface of the TBR kernels (tbr.hip; host/tbr.cpp; the plan of a visit: host/tbr_plan.hpp).
+//
+// There is no reference function (MPBoot has SPR and NNI).  Cut the edge (p, q = back[p]).  The part on p's side, rooted on a branch
+// (g, back g) inside it, shows R_p(g) = fitch(U(g), vec[g]), U the chain of the SPR scan: U(child) = fitch(U(parent), vec[sibling]),
+// U(x1) = vec[x2], U(x2) = vec[x1] for p's children; rooted on its own merged edge it shows vec[p].  The same on q's side.  The tree
+// that joins the middle of f to the middle of g has length sc[p] + sc[q] + #sites where R_q(f) and R_p(g) share no state.
+#pragma once
+#include "kernels.hpp"
+#include "../host/tbr_plan.hpp"
+
+namespace mpf {
+
+// levels of U that k_tbr_roots keeps in LDS (a level is S rows x 64 words); deeper levels live in HBM scratch
+constexpr int tbr_lds_levels(int S) { return S == 4 ? 16 : 7; }      // 16 KiB | 35 KiB (20 rows) | 56 KiB (32 rows)
+
+// one side of a visit: its chain program ops[op_begin .. op_end) and where its levels beyond the LDS ones go: `deep_levels` levels
+// per site tile, `deep_off` words into the scratch area
+struct TbrSide { uint32_t op_begin, op_end, deep_levels, pad; uint64_t deep_off; };
+// one visit of the pair product: row i of its matrix reads vec slot_q (i = 0) or root set f0 + i - 1 of the scratch store, column j
+// vec slot_p or root set g0 + j - 1; cost[i][j] goes to out[at + i * ng + j] with base = sc[p] + sc[q] added
+struct TbrVisit { uint32_t slot_q, slot_p, f0, g0, nf, ng, base, pad; uint64_t at; };
+
+// the words of HBM scratch the deep levels of these sides take (sides[i].deep_off filled in)
+size_t tbr_deep_words(const Geometry &g, TbrSide *sides, size_t n_sides);
+// store[op.out] = the root set of every chain step, rows as in the engine's store (S rows x Wp words)
+hipError_t launch_tbr_roots(hipStream_t st, const Geometry &g, const uint32_t *vec, const tbrplan::Op *ops, const TbrSide *sides, size_t n_sides,
+                            uint32_t *store, uint32_t *deep);
+// the matrices of the visits, one workgroup per item; shape: tbrplan::TILE_NARROW | TILE_WIDE, the one the items were cut for
+hipError_t launch_tbr_costs(hipStream_t st, const Geometry &g, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
+                            const tbrplan::Item *items, size_t n_items, int shape, uint32_t *out);
+// best[3 v] = the first minimum of visit v's matrix in row-major order, [0][0] left out, best[3 v + 1], [3 v + 2] = its row and
+// column; 0xFFFFFFFF all three for a 1 x 1 matrix (one wave per visit)
+hipError_t launch_tbr_best(hipStream_t st, const TbrVisit *visits, size_t n_visits, const uint32_t *out, uint32_t *best);
+
+}  // namespace mpf

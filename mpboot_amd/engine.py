@@ -38,6 +38,7 @@ EXPORTS = [
     "mpf_branch_substitutions", "mpf_branch_lengths",
     "mpf_polytomy_parsimony", "mpf_polytomy_branch_substitutions", "mpf_polytomy_branch_lengths",
     "mpf_insertion_costs", "mpf_place_taxa", "mpf_iq_parsimony_tree",
+    "mpf_tbr_scan", "mpf_tbr_sweep_best", "mpf_apply_tbr", "mpf_optimize_tbr", "mpf_get_tbr_moves",
     "mpf_split_counts", "mpf_split_support", "mpf_consensus_tree", "mpf_ufboot_summarize", "mpf_ufboot_summary_trees",
     "mpf_rf_distances",
     "mpf_split_counts_set", "mpf_split_support_set", "mpf_consensus_tree_set", "mpf_rf_distances_set",
@@ -204,6 +205,11 @@ def load_library():
         L.mpf_insertion_costs.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_place_taxa.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.mpf_iq_parsimony_tree.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.mpf_tbr_scan.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+        L.mpf_tbr_sweep_best.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+        L.mpf_apply_tbr.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp]
+        L.mpf_optimize_tbr.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
+        L.mpf_get_tbr_moves.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_split_counts.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]
         L.mpf_split_support.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_consensus_tree.argtypes = [vp, C.c_int32, vp, vp, C.c_double, vp, vp, vp, vp, vp]
@@ -750,6 +756,62 @@ class FitchEngine:
         _chk(load_library().mpf_place_taxa(self.h, k, _p(f), _p(nb), root_taxon, Q, _p(q) if Q else None, _p(br), _p(a), _p(b), _p(ln),
                                            C.byref(tl)))
         return br[:Q], a[:Q], b[:Q], ln[:Q], int(tl.value)
+
+    # ---- TBR (host/tbr.cpp, tbr.hip): no reference function, MPBoot has SPR and NNI only.  Fitch engine without a tracker
+    def tbr_scan(self, rec: int, maxtrav: int = 6, cap=None):
+        """one visit: (f_recs, g_recs, cost[1 + len(f), 1 + len(g)]) -- cut the edge (rec, back[rec]); g_recs lists the branches of
+        rec's part, f_recs those of back[rec]'s part (the SPR scan's one side with mintrav = 1); cost[i][j] = the length of the tree
+        that joins the middle of f_recs[i - 1] to the middle of g_recs[j - 1], index 0 = the part's own root: row 0 and column 0
+        are SPR tests, cost[0][0] is the current length.  The tree of an entry is trees.apply_tbr(back, rec, f, g).
+        cap (tests): (cap_f, cap_g) handed to the C call; where one is too small only (n_f, n_g) comes back."""
+        L = load_library()
+        nf, ng = C.c_int32(), C.c_int32()
+        if cap is None:
+            _chk(L.mpf_tbr_scan(self.h, rec, maxtrav, -1, -1, None, None, None, C.byref(nf), C.byref(ng)))
+            cap = (nf.value, ng.value)
+        f = np.zeros(max(cap[0], 1), dtype=np.int32)
+        g = np.zeros(max(cap[1], 1), dtype=np.int32)
+        c = np.zeros((1 + max(cap[0], 0)) * (1 + max(cap[1], 0)), dtype=np.uint32)
+        _chk(L.mpf_tbr_scan(self.h, rec, maxtrav, cap[0], cap[1], _p(f), _p(g), _p(c), C.byref(nf), C.byref(ng)))
+        if nf.value > cap[0] or ng.value > cap[1]:
+            return nf.value, ng.value
+        return f[:nf.value].copy(), g[:ng.value].copy(), c[:(1 + nf.value) * (1 + ng.value)].reshape(1 + nf.value, 1 + ng.value).copy()
+
+    def tbr_sweep_best(self, maxtrav: int = 6):
+        """the best of every visit of a sweep over node_order(): (cost[2n - 2], f[2n - 2], g[2n - 2], n_pairs) -- the first minimum
+        of each visit's matrix in row-major order, [0][0] left out; records -1 for "none"; cost 0xFFFFFFFF where a visit has no
+        entry; n_pairs = matrix entries scored.  Found on the device: three words per visit come back."""
+        m = 2 * self.n - 2
+        c = np.zeros(m, dtype=np.uint32)
+        f = np.zeros(m, dtype=np.int32)
+        g = np.zeros(m, dtype=np.int32)
+        k = C.c_uint64()
+        _chk(load_library().mpf_tbr_sweep_best(self.h, maxtrav, _p(c), _p(f), _p(g), C.byref(k)))
+        return c, f, g, int(k.value)
+
+    def apply_tbr(self, rec: int, f_rec: int, g_rec: int) -> int:
+        """edit the engine's tree to trees.apply_tbr(back, rec, f_rec, g_rec) -> its length (as set_tree + score_tree)"""
+        s = C.c_uint32()
+        _chk(load_library().mpf_apply_tbr(self.h, rec, f_rec, g_rec, C.byref(s)))
+        return s.value
+
+    def optimize_tbr(self, maxtrav: int = 6, max_moves: int = 0):
+        """steepest descent over the TBR neighbourhood: the sweep's best is applied while it is strictly below the current length.
+        -> (length, n_moves); the moves are in tbr_moves().  Deterministic, the tie stream is not touched."""
+        s, k = C.c_uint32(), C.c_int32()
+        _chk(load_library().mpf_optimize_tbr(self.h, maxtrav, max_moves, C.byref(s), C.byref(k)))
+        return s.value, k.value
+
+    def tbr_moves(self):
+        """moves of the last optimize_tbr: (rec[k], f_rec[k], g_rec[k], length[k])"""
+        L = load_library()
+        k = C.c_int32()
+        _chk(L.mpf_get_tbr_moves(self.h, 0, None, None, None, None, C.byref(k)))
+        r, f, g = (np.zeros(k.value, dtype=np.int32) for _ in range(3))
+        s = np.zeros(k.value, dtype=np.uint32)
+        if k.value:
+            _chk(L.mpf_get_tbr_moves(self.h, k.value, _p(r), _p(f), _p(g), _p(s), C.byref(k)))
+        return r, f, g, s
 
     def iq_parsimony_tree(self, order=None, tie_state=None):
         """PhyloTree::computeParsimonyTree (-starttree PARS): stepwise addition with every branch tried at every step and the first

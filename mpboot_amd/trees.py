@@ -215,6 +215,19 @@ def apply_spr(back: np.ndarray, p: int, q: int) -> np.ndarray:
     return b
 
 
+def apply_tbr(back: np.ndarray, p: int, f: int, g: int) -> np.ndarray:
+    """Cut the edge (p, q = back[p]) and join the middle of branch (f, back[f]) of q's part to the middle of branch (g, back[g])
+    of p's part; -1 for either means that part's own root.  Two apply_spr steps on disjoint links (no reference function: MPBoot
+    has SPR and NNI only)."""
+    b = np.array(back, dtype=np.int32).copy()
+    q = int(b[p])
+    if g >= 0:
+        b = apply_spr(b, p, g)
+    if f >= 0:
+        b = apply_spr(b, q, f)
+    return b
+
+
 def random_spr_moves(engine_obj, back: np.ndarray, rng: np.random.Generator, k: int, maxtrav: int = 6) -> np.ndarray:
     """k random SPR moves within the given radius (a stand-in for the search's perturbation step): the prune node
     and the regraft branch are drawn uniformly from what rearrangeParsimony would test."""
