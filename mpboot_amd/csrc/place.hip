@@ -20,6 +20,7 @@
 //   PlaceMinPlus<S, PK, BIG> the weighted (-cost) engine: min-plus over the stored transforms, a weighted sum per element
 #include "place.hpp"
 #include "snk_elem.hpp"
+#include "wave_min.hpp"
 
 namespace mpf {
 
@@ -241,15 +242,11 @@ __global__ __launch_bounds__(64) void k_place_best(const uint32_t *__restrict__ 
     const uint32_t x = row[b];
     if (x < v) { v = x; at = (uint32_t)b; }                  // (a lane's indices rise: the first of equal values stays)
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t ov = (uint32_t)__shfl_xor((int)v, off, 64), oat = (uint32_t)__shfl_xor((int)at, off, 64);
-    if (ov < v || (ov == v && oat < at)) { v = ov; at = oat; }
-  }
-  if (threadIdx.x == 0) { best[2 * blockIdx.x] = v; best[2 * blockIdx.x + 1] = at; }
+  const MinAt<uint32_t> m = wave_first_min(v, at);
+  if (threadIdx.x == 0) { best[2 * blockIdx.x] = m.v; best[2 * blockIdx.x + 1] = m.at; }
 }
 
-// the algebra's kernel in the shape place_shape gives it for `narrow`
+// the algebra's kernel in the shape place_shape (host/pair_tile.hpp) gives it for `narrow`
 template <class A>
 void launch_shape(hipStream_t st, bool narrow, const uint32_t *base, const BranchDesc *desc, int n_br, const uint32_t *qslot, int n_query,
                   int len, const uint32_t *pwgt, uint32_t *out, int ld)

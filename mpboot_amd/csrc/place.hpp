@@ -5,24 +5,12 @@
 // that is non-empty, else A | B.  For Q queries and B branches that is a Q x B x row-words popcount product.
 #pragma once
 #include "kernels.hpp"
+#include "../host/pair_tile.hpp"
 
 namespace mpf {
 
-// Tile shapes of k_place_costs (compile-time).  A workgroup of 256 lanes owns TQ queries x TB branches and walks the
-// row in slices of KS elements (words of 32 sites; on the weighted engine patterns, or pairs of patterns in the 16-bit store); a lane
-// holds RQ x RB outputs and, in the narrow shape, one of KT interleaved element classes of a slice (summed through LDS at the end:
-// no atomics).
-//   wide   (many queries):  4 rows: 64 x 64, 4 x 4 per lane, KS 16;   32 rows: 32 x 32, 2 x 2 per lane, KS 4;
-//                           20 rows: the 32-row shape, on the weighted engine 64 x 64, 4 x 4 per lane, KS 4
-//   narrow (few outputs, every computeParsimonyTree step): 4 queries x 16 branches, 4 x 1 per lane, KT = KS = 16
-enum { PLACE_AUTO = 0, PLACE_NARROW = 1, PLACE_WIDE = 2 };
-struct PlaceShape { int tq, tb, rq, rb, ks, kt; };
-constexpr PlaceShape place_shape(int S, bool weighted, int tile)      // tile: PLACE_NARROW | PLACE_WIDE
-{
-  if (tile == PLACE_NARROW) return PlaceShape{4, 16, 4, 1, 16, 16};
-  if (S == 4) return PlaceShape{64, 64, 4, 4, 16, 1};
-  return S == 20 && weighted ? PlaceShape{64, 64, 4, 4, 4, 1} : PlaceShape{32, 32, 2, 2, 4, 1};
-}
+// The tile shapes of k_place_costs -- PlaceShape, place_shape(S, weighted, tile), PLACE_AUTO | PLACE_NARROW | PLACE_WIDE -- are in
+// host/pair_tile.hpp, the one table that the TBR pair product (tbr.hip, host/tbr_plan.hpp) reads too; DESIGN 5p.
 // PLACE_AUTO -> the narrow shape below `narrow_below` outputs (queries x branches), the wide one from there on
 int place_pick(int n_query, int n_br, int tile, long long narrow_below);
 long long place_narrow_below();                     // the Fitch engine's line: 2^18

@@ -13,6 +13,7 @@
 //   k_tbr_best   one wave per visit: the first minimum of its matrix, [0][0] left out
 // Padding bits are set in every state row of every resident vector, so they are in every U and every root set, and always match.
 #include "tbr.hpp"
+#include "wave_min.hpp"
 
 namespace mpf {
 
@@ -215,25 +216,13 @@ __global__ __launch_bounds__(64) void k_tbr_best(const TbrVisit *__restrict__ vi
     const uint32_t x = m[e];
     if (at == (size_t)-1 || x < v) { v = x; at = e; }      // (a lane's indices rise: the first of equal values stays)
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t ov = (uint32_t)__shfl_xor((int)v, off, 64);
-    const uint32_t alo = (uint32_t)__shfl_xor((int)(uint32_t)at, off, 64), ahi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)at >> 32), off, 64);
-    const size_t oat = (size_t)(((uint64_t)ahi << 32) | alo);
-    if (oat != (size_t)-1 && (at == (size_t)-1 || ov < v || (ov == v && oat < at))) { v = ov; at = oat; }
-  }
+  const MinAt<size_t> w = wave_first_min(v, at);      // (a lane without an entry has at = (size_t)-1 still: the helper's empty lane)
   if (threadIdx.x == 0) {
     uint32_t *b = best + 3 * (size_t)blockIdx.x;
-    if (at == (size_t)-1) { b[0] = b[1] = b[2] = 0xFFFFFFFFu; }
-    else { b[0] = v; b[1] = (uint32_t)(at / vd.ng); b[2] = (uint32_t)(at % vd.ng); }
+    if (w.at == (size_t)-1) { b[0] = b[1] = b[2] = 0xFFFFFFFFu; }
+    else { b[0] = w.v; b[1] = (uint32_t)(w.at / vd.ng); b[2] = (uint32_t)(w.at % vd.ng); }
   }
 }
-
-template <int S, int SHAPE> struct CostShape;
-// (rows, columns, outputs per lane rows x columns, slice, word classes): place_shape's numbers, the unweighted ones
-template <int S> struct CostShape<S, tbrplan::TILE_NARROW> { static constexpr int rq = 4, rb = 1, ks = 16, kt = 16; };
-template <> struct CostShape<4, tbrplan::TILE_WIDE> { static constexpr int rq = 4, rb = 4, ks = 16, kt = 1; };
-template <int S> struct CostShape<S, tbrplan::TILE_WIDE> { static constexpr int rq = 2, rb = 2, ks = 4, kt = 1; };
 
 }  // namespace
 
@@ -273,9 +262,9 @@ hipError_t launch_tbr_costs(hipStream_t st, const Geometry &g, const uint32_t *v
   dispatch_states(g.S, [&](auto S) {
     dispatch_bool(shape == tbrplan::TILE_NARROW, [&](auto NARROW) {
       constexpr int SH = NARROW ? tbrplan::TILE_NARROW : tbrplan::TILE_WIDE;
-      constexpr tbrplan::TileDims d = tbrplan::tile_dims(S, SH);
-      typedef CostShape<S, SH> C;
-      hipLaunchKernelGGL((k_tbr_costs<S, d.tf, d.tg, C::rq, C::rb, C::ks, C::kt>), dim3((unsigned)n_items), dim3(256), 0, st, vec, store, visits,
+      constexpr PlaceShape sh = place_shape(S, false, SH);      // the unweighted row of the one table (host/pair_tile.hpp)
+      static_assert(tbrplan::tile_dims(S, SH).tf == sh.tq && tbrplan::tile_dims(S, SH).tg == sh.tb, "the items were cut for another tile");
+      hipLaunchKernelGGL((k_tbr_costs<S, sh.tq, sh.tb, sh.rq, sh.rb, sh.ks, sh.kt>), dim3((unsigned)n_items), dim3(256), 0, st, vec, store, visits,
                          items, g.Wp, out);
     });
   });

@@ -14,6 +14,8 @@
 #include <utility>
 #include <vector>
 
+#include "pair_tile.hpp"
+
 namespace tbrplan {
 
 inline int nx(int r) { return 3 * (r / 3) + (r % 3 + 1) % 3; }
@@ -106,11 +108,11 @@ inline std::vector<std::pair<size_t, size_t>> chunks(const std::vector<size_t> &
   return out;
 }
 
-// ---- tiles of the pair product (csrc/tbr.hip).  A workgroup owns tf rows x tg columns of one visit's matrix.  Two shapes, as the
-// taxon-insertion product has them: narrow 4 x 16 with the row words split 16 ways, wide 64 x 64 (4 state rows) or 32 x 32.
-enum { TILE_AUTO = 0, TILE_NARROW = 1, TILE_WIDE = 2 };
+// ---- tiles of the pair product (csrc/tbr.hip).  A workgroup owns tf rows x tg columns of one visit's matrix, in one of the two
+// shapes of the taxon-insertion product: the unweighted rows of its table (pair_tile.hpp), which k_tbr_costs is instantiated from too.
+enum { TILE_AUTO = mpf::PLACE_AUTO, TILE_NARROW = mpf::PLACE_NARROW, TILE_WIDE = mpf::PLACE_WIDE };
 struct TileDims { int tf, tg; };
-constexpr TileDims tile_dims(int S, int shape) { return shape == TILE_NARROW ? TileDims{4, 16} : (S == 4 ? TileDims{64, 64} : TileDims{32, 32}); }
+constexpr TileDims tile_dims(int S, int shape) { return TileDims{mpf::place_shape(S, false, shape).tq, mpf::place_shape(S, false, shape).tb}; }
 constexpr size_t tiles_of(size_t rows, size_t cols, TileDims d) { return ((rows + (size_t)d.tf - 1) / (size_t)d.tf) * ((cols + (size_t)d.tg - 1) / (size_t)d.tg); }
 // TILE_AUTO: the shape whose tiles cover fewer outputs, padding included.  A wide lane holds 4 x 4 (2 x 2) outputs and reads each
 // staged word once for four (two) of them, a narrow lane holds 4 x 1: a narrow output is charged twice

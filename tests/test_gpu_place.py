@@ -20,7 +20,7 @@ SITES = (2047, 2048, 2049, 4096, 4097, 8193)              # site totals
 ALPHABETS = ("dna", "aa", "m32")
 DT = {"dna": 0, "aa": 1, "m32": 3}
 NARROW, WIDE = 1, 2
-# k_place_costs' instantiated shapes (place.hpp): (query tile, branch tile, words per K slice)
+# k_place_costs' instantiated shapes (host/pair_tile.hpp): (query tile, branch tile, words per K slice)
 SHAPES = {("dna", NARROW): (4, 16, 16), ("aa", NARROW): (4, 16, 16), ("m32", NARROW): (4, 16, 16),
           ("dna", WIDE): (64, 64, 16), ("aa", WIDE): (32, 32, 4), ("m32", WIDE): (32, 32, 4)}
 

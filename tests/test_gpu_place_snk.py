@@ -28,7 +28,7 @@ DT = {"dna": 0, "aa": 1, "m32": 3}
 STATES = {"dna": 4, "aa": 20, "m32": 32}
 KINDS = {"dna": ("tstv", "metric", "asym"), "aa": ("metric", "asym"), "m32": ("metric", "asym")}
 NARROW, WIDE = 1, 2
-# k_snk_place_costs' instantiated shapes (place.hpp): (query tile, branch tile, ELEMENTS per K slice; an element is one pattern in the
+# k_snk_place_costs' instantiated shapes (host/pair_tile.hpp): (query tile, branch tile, ELEMENTS per K slice; an element is one pattern in the
 # 32-bit store and two in the 16-bit store)
 SHAPES = {("dna", NARROW): (4, 16, 16), ("aa", NARROW): (4, 16, 16), ("m32", NARROW): (4, 16, 16),
           ("dna", WIDE): (64, 64, 16), ("aa", WIDE): (64, 64, 4), ("m32", WIDE): (32, 32, 4)}

@@ -23,7 +23,7 @@ ALPHABETS = ("dna", "aa", "m32")
 DT = {"dna": 0, "aa": 1, "m32": 3}
 RADII = (1, 2, 3, 255)
 NARROW, WIDE = 1, 2
-# k_tbr_costs' instantiated tiles (host/tbr_plan.hpp): (rows of F, columns of G)
+# k_tbr_costs' instantiated tiles (place_shape's unweighted rows, host/pair_tile.hpp): (rows of F, columns of G)
 SHAPES = {("dna", NARROW): (4, 16), ("aa", NARROW): (4, 16), ("m32", NARROW): (4, 16),
           ("dna", WIDE): (64, 64), ("aa", WIDE): (32, 32), ("m32", WIDE): (32, 32)}
 

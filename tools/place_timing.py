@@ -10,7 +10,7 @@ every one that opens the GPU under `timeout`, one GPU process at a time; a step 
             poly_view_ns per call.
          2. the same 2 n - 5 numbers by the only route there was before: mpf_score_trees over the completed trees (existing code).
          4. Q = 1, 16, 64, 256 queries on a backbone with min(256, n / 2) taxa held out (C2 has no 256 to hold out beside a
-            backbone): whole call and kernel time.
+            backbone): whole call and kernel time; mpf_place_taxa of the same queries, kernel time (k_place_costs + k_place_best).
          5. for the kernel at the largest Q the (query, branch, word) operations per second it achieved -- tiles x tile area x
             padded words -- next to the VALU issue bound, computed as tools/rf_timing.py computes its own: 256 CUs x 4 SIMDs x 32
             lanes per cycle x 2.4 GHz / 5 instructions per operation (four v_and / v_and_or and one v_bcnt for 4 state rows).
@@ -120,6 +120,7 @@ def step_gpu(shape, reps, workdir):
             r["place_kernels_" + name] = timed(eng, lambda: eng.insertion_costs(f2, n2, drop[:Q]), reps)["place_kernels"]
         eng.set_option("place_tile", 0)
         at, _, _, ln, _ = eng.place_taxa(f2, n2, drop[:Q])
+        r["place_taxa_kernels"] = timed(eng, lambda: eng.place_taxa(f2, n2, drop[:Q]), reps)["place_kernels"]      # (k_place_best rides in it)
         full = eng.insertion_costs(f2, n2, drop[:Q])[2]
         r["place_taxa_is_the_first_minimum"] = bool((at == full.argmin(axis=1)).all() and (ln == full.min(axis=1)).all())
         sweep["queries"][str(Q)] = r
