@@ -457,9 +457,19 @@ int mpf_iq_parsimony_tree(mpf_engine *e, uint64_t *tie_state, int32_t *order, in
    apply_spr(apply_spr(back, rec, g), q, f), a step whose record is "none" skipped.  All directional views are resident, so an
    entry costs one popcount over two root sets: k_tbr_roots writes the root sets R(.) of both parts into a scratch store,
    k_tbr_costs forms the matrix, cost = sc[rec] + sc[q] + #sites where R_q(f) and R_rec(g) share no state (tbr.hip).
-   Fitch engine only: a weighted (-cost) engine, and an engine with a UFBoot tracker attached (nothing would be booked), answer
-   MPF_E_UNSUPPORTED.  maxtrav outside 1 .. 255: MPF_E_INVALID.  Options: "tbr_tile" (0 = per visit from the padded outputs | 1 =
-   narrow, 4 x 16 per workgroup | 2 = wide, 64 x 64 for 4 state rows, 32 x 32 for 20 and 32), "tbr_chunk_vectors" (the most
+   The weighted engine (mpf_engine_create_sankoff; -cost m).  Option "tbr_weighted" (mpf_set_option; default 0, no effect on a
+   Fitch engine): with 0 a weighted engine answers MPF_E_UNSUPPORTED as before.  With 1 it serves all five entries below over the
+   min-plus algebra, m(v)[z] = min_x(v[x] + cost[z][x]) the stored transform with the viewer as the parent: k_tbr_snk_roots forms
+   MU[0] = m(vec[own]), U = MU[d - 1] + m(vec[sib]), MU[d] = m(U) and the root set R = MU[d] + m(vec[own]) -- a root set of rec's part
+   is stored as m(R) --, k_tbr_costs forms cost[i][j] = sum over the patterns of weight x min_x(R_q(f)[x] + m(R_rec(g))[x]): the FULL
+   weighted length of the joined tree, nothing added; cost[0][0] is the current length, row 0 and column 0 are the weighted
+   mpf_spr_scan's tests.  Both stores ("sankoff_short").  Symmetric cost matrices only: with a matrix that is not symmetric the
+   length depends on the edge it is evaluated at and TBR has no reference function that would fix one -- MPF_E_UNSUPPORTED, the
+   message says "not symmetric".
+   An engine with a UFBoot tracker attached (nothing would be booked) answers MPF_E_UNSUPPORTED on either engine.
+   maxtrav outside 1 .. 255: MPF_E_INVALID.  Options: "tbr_tile" (0 = per visit from the padded outputs | 1 =
+   narrow, 4 x 16 per workgroup | 2 = wide, 64 x 64 for 4 state rows, 32 x 32 for 20 and 32; on the weighted engine 64 x 64 for 4 and
+   20 state rows, 32 x 32 for 32), "tbr_weighted" (above), "tbr_chunk_vectors" (the most
    root-set vectors a chunk of a sweep may hold, 0 = 256 MiB worth; a visit that needs more is a chunk of its own; results do not
    depend on it), read-only "tbr_chunks" (chunks of the last sweep), "tbr_launches" and, under "timing", "tbr_kernel_ns".
 

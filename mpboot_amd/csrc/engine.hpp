@@ -734,7 +734,9 @@ class Engine {
   // TBR (host/tbr.cpp): option "tbr_tile" (0 = per visit from the padded outputs, 1 = narrow, 2 = wide; host/tbr_plan.hpp),
   // "tbr_chunk_vectors" (the most root-set vectors a chunk of a sweep may hold; 0 = 256 MiB worth), read-only "tbr_chunks" (chunks of
   // the last sweep), "tbr_launches" (k_tbr_costs launches) and, under "timing", "tbr_kernel_ns" (HIP-event time of the three kernels)
-  int tbr_tile_ = 0, tbr_chunks_ = 0;
+  // option "tbr_weighted": the weighted engine serves the TBR entries (k_tbr_snk_roots, k_tbr_costs<PlaceMinPlus>, tbr.hip; symmetric
+  // cost matrices only); 0: refused as before.  No effect on a Fitch engine
+  int tbr_tile_ = 0, tbr_chunks_ = 0, tbr_weighted_ = 0;
   int64_t tbr_chunk_vectors_ = 0;
   uint64_t tbr_launches_ = 0, tbr_kernel_ns_ = 0;
   std::vector<TbrMove> tbr_moves_;

@@ -12,7 +12,16 @@
 //                absolute 64-bit row pointers.  The launch is a flat list of (visit, F tile, G tile) items.  One writer per output
 //   k_tbr_best   one wave per visit: the first minimum of its matrix, [0][0] left out
 // Padding bits are set in every state row of every resident vector, so they are in every U and every root set, and always match.
+//
+// On the weighted (-cost) engine (option "tbr_weighted", symmetric cost matrices) the same plan runs over the min-plus algebra, m()
+// the stored transform with the viewer as the parent:
+//   k_tbr_snk_roots  the chain of k_snk_scan: MU[0] = m(vec[own]) as stored, U = MU[d - 1] + m(vec[sib]), MU[d] = m(U), root set
+//                    R = MU[d] + m(vec[own]); MU per depth where k_tbr_roots keeps U.  A side of F stores R, a side of G stores m(R),
+//                    so the S x S transform is paid once per root set and not once per pair
+//   k_tbr_costs      over PlaceMinPlus: cost[i][j] = sum_ptn w * min_x(RF_i[x] + m(RG_j)[x]), the FULL length, no additive base;
+//                    row 0 reads vec[slot_q] as it is, column 0 the stored transform of slot_p
 #include "tbr.hpp"
+#include "pair_algebra.hpp"
 #include "wave_min.hpp"
 
 namespace mpf {
@@ -71,13 +80,73 @@ __global__ __launch_bounds__(64) void k_tbr_roots(const uint32_t *__restrict__ v
   }
 }
 
-// out[at + i ng + j] = base + 32 len - the sum over the row's words of popc(OR over the state rows of (row i of F & row j of G))
-template <int S, int TQ, int TB, int RQ, int RB, int KS, int KT>
+// The weighted root sets.  One wave per (side, tile of 64 elements of the row: patterns, or pairs of patterns in the 16-bit store); a
+// lane owns its element for the whole program.  MU[d] = m(U[d]) per depth, in LDS and beyond tbr_lds_levels in HBM scratch exactly
+// as k_tbr_roots keeps U; every operand read from the engine's store is a STORED transform (the `moff` half), so a chain step costs
+// one transform, m(U), and a side of G (TbrSide::pad bit 0) one more, m(R): the costs product then adds and takes minima only.
+// 16-bit store: U[d] = MU[d - 1] + m(vec[sib]) and R = MU[d] + m(vec[own]) are sums of transforms over disjoint parts of ONE side
+// of the cut edge.  A tip's vector is 0 or highest_cost, a view the sum of its children's transforms, and m(v)[z] <= v[z] + cost[z][z]
+// = v[z], so a part of t tips stays within t highest_cost: U and R within the side's tips, the costs product's RF_i[x] + m(RG_j)[x]
+// within n highest_cost, and inside a transform v[x] + cost[z][x] within (n + 1) highest_cost -- all below what Engine::pack guards,
+// 3 n highest_cost < 65536.  No 32-bit fall-back is needed.
+template <int S, bool PK, int LD>
+__global__ __launch_bounds__(64) void k_tbr_snk_roots(const uint32_t *__restrict__ mvec, const tbrplan::Op *__restrict__ ops,
+                                                      const TbrSide *__restrict__ sides, int tiles, int We,
+                                                      const uint32_t *__restrict__ cost, uint32_t *__restrict__ store,
+                                                      uint32_t *__restrict__ deep)
+{
+  typedef SnkT<PK> T;
+  typedef typename T::E E;
+  __shared__ uint32_t su[LD * S * 64];               // [level][state row][lane]: a lane reads and writes its own column only, no barrier
+  const int lane = (int)threadIdx.x;
+  const size_t side = (size_t)blockIdx.x / (size_t)tiles, tile = (size_t)blockIdx.x % (size_t)tiles;
+  const size_t e = tile * 64 + (size_t)lane, row = (size_t)We, vsz = (size_t)S * row;
+  if (e >= row) return;                              // (We is a multiple of 16: the last tile may be partly full; no lane waits on another)
+  const TbrSide sd = sides[side];
+  const bool transformed = (sd.pad & 1u) != 0u;      // a side of G: the root sets are stored as m(R)
+  uint32_t *dl = deep + sd.deep_off + tile * (size_t)sd.deep_levels * (size_t)(S * 64) + (size_t)lane;
+  auto level = [&](int d) -> uint32_t * { return d < LD ? &su[d * S * 64 + lane] : dl + (size_t)(d - LD) * (size_t)(S * 64); };
+  for (uint32_t i = sd.op_begin; i < sd.op_end; i++) {
+    const tbrplan::Op o = ops[i];
+    const int d = (int)(o.meta & 255u);
+    Costs<S, PK> u, x, mu;
+    if ((o.meta >> 16) == (uint32_t)tbrplan::OP_ROOT) {
+      load_costs<S, PK>(x, mvec, o.own, We, (int)e);
+      uint32_t *l0 = level(0);
+#pragma unroll
+      for (int s = 0; s < S; s++) l0[s * 64] = __builtin_bit_cast(uint32_t, x.v[s]);
+      continue;
+    }
+    load_costs<S, PK>(x, mvec, o.sib, We, (int)e);
+    const uint32_t *up = level(d - 1);
+#pragma unroll
+    for (int s = 0; s < S; s++) u.v[s] = T::add(__builtin_bit_cast(E, up[s * 64]), x.v[s]);      // U[d]
+    mplus_fast<S, PK>(mu, u, cost);
+    load_costs<S, PK>(x, mvec, o.own, We, (int)e);
+    uint32_t *ud = level(d);
+#pragma unroll
+    for (int s = 0; s < S; s++) ud[s * 64] = __builtin_bit_cast(uint32_t, mu.v[s]);
+#pragma unroll
+    for (int s = 0; s < S; s++) u.v[s] = T::add(mu.v[s], x.v[s]);                               // R
+    if (transformed) { mplus_fast<S, PK>(mu, u, cost); u = mu; }
+    uint32_t *r = store + (size_t)o.out * vsz + e;
+#pragma unroll
+    for (int s = 0; s < S; s++) r[(size_t)s * row] = __builtin_bit_cast(uint32_t, u.v[s]);
+  }
+}
+
+// out[at + i ng + j] = A::finish of the sum over the row's `len` elements of A::weigh(the sum over the state rows of A::mul(row i of F,
+// row j of G)).  PlaceFitch: base + 32 len - the sum over the row's words of popc(OR over the state rows of (row i of F & row j of
+// G)).  PlaceMinPlus: the weighted sum of min_x(F_i[x] + G_j[x]) over the patterns; column 0 is read `moff` words behind vec (the
+// stored transform of slot_p), pwgt holds the pattern weights (0 on padding)
+template <class A, int TQ, int TB, int RQ, int RB, int KS, int KT>
 __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ vec, const uint32_t *__restrict__ store,
                                                    const TbrVisit *__restrict__ visits, const tbrplan::Item *__restrict__ items, int len_,
-                                                   uint32_t *__restrict__ out)
+                                                   uint32_t *__restrict__ out, size_t moff, const uint32_t *__restrict__ pwgt)
 {
-  constexpr int TBT = TB / RB, TQT = TQ / RQ;
+  typedef typename A::E E;
+  constexpr int S = A::S, NW = KS * A::NP, TBT = TB / RB, TQT = TQ / RQ;
+  static_assert(A::template slice_ok<KS>, "the algebra's slice");
   static_assert(TBT * TQT * KT == 256 && TB % RB == 0 && TQ % RQ == 0 && KS % KT == 0, "lane mapping");
   static_assert(KT == 1 || KT * TQ * TB <= KS * (S * TB + 64 / KS), "the partial sums reuse the column slice");
   static_assert(64 % KS == 0 && (64 / KS) % 4 == 0, "padding keeps the 16-byte alignment");
@@ -86,6 +155,7 @@ __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ 
   constexpr int XP = S * TB + 64 / KS, QP = S * TQ + 64 / KS;
   __shared__ __attribute__((aligned(16))) uint32_t sx[KS * XP];
   __shared__ __attribute__((aligned(16))) uint32_t sq[KS * QP];
+  __shared__ uint32_t sw[NW ? NW : 1];                       // (NW == 0: never touched, takes no LDS)
   const size_t len = (size_t)len_, vsz = (size_t)S * len;
   const int tid = (int)threadIdx.x;
   const int tb = tid % TBT, tq = (tid / TBT) % TQT, kt = tid / (TBT * TQT);
@@ -98,7 +168,7 @@ __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ 
   for (int i = 0; i < BI; i++) {
     const int idx = tid + 256 * i;
     const int j = min(g_lo + min(idx / KS, TB - 1), ng - 1);               // (columns past the end repeat the last: loads stay inside)
-    pg[i] = (j == 0 ? vec + (size_t)vd.slot_p * vsz : store + ((size_t)vd.g0 + (size_t)(j - 1)) * vsz) + (size_t)(idx % KS);
+    pg[i] = (j == 0 ? vec + (NW ? moff : (size_t)0) + (size_t)vd.slot_p * vsz : store + ((size_t)vd.g0 + (size_t)(j - 1)) * vsz) + (size_t)(idx % KS);
   }
 #pragma unroll
   for (int i = 0; i < QI; i++) {
@@ -106,7 +176,7 @@ __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ 
     const int f = min(f_lo + min(idx / KS, TQ - 1), nf - 1);
     pf[i] = (f == 0 ? vec + (size_t)vd.slot_q * vsz : store + ((size_t)vd.f0 + (size_t)(f - 1)) * vsz) + (size_t)(idx % KS);
   }
-  uint32_t rg[BI][S], rf[QI][S];
+  uint32_t rg[BI][S], rf[QI][S], rw = 0u;
   auto fetch = [&](size_t k0) {
 #pragma unroll
     for (int i = 0; i < BI; i++)
@@ -120,6 +190,8 @@ __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ 
 #pragma unroll
         for (int s = 0; s < S; s++) rf[i][s] = pf[i][(size_t)s * len + k0];
       }
+    if constexpr (NW > 0)
+      if (tid < NW) rw = pwgt[k0 * A::NP + (size_t)tid];
   };
   fetch(0);
 
@@ -129,7 +201,7 @@ __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ 
 #pragma unroll
     for (int j = 0; j < RB; j++) acc[i][j] = 0u;
 
-  for (size_t k0 = 0; k0 < len; k0 += KS) {                  // (a row is whole slices: Wp is a multiple of 32)
+  for (size_t k0 = 0; k0 < len; k0 += KS) {                  // (a row is whole slices: Wp is a multiple of 32, We of 16)
     __syncthreads();                                         // the last slice has been read by everybody
 #pragma unroll
     for (int i = 0; i < BI; i++) {
@@ -149,30 +221,32 @@ __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ 
         for (int s = 0; s < S; s++) d[s * TQ] = rf[i][s];
       }
     }
+    if constexpr (NW > 0)
+      if (tid < NW) sw[tid] = rw;
     __syncthreads();
     if (k0 + KS < len) fetch(k0 + KS);                       // the next slice is on its way while this one is summed
 #pragma unroll 2
     for (int k = kt; k < KS; k += KT) {
-      uint32_t m[RQ][RB];
+      E m[RQ][RB];
 #pragma unroll
       for (int s = 0; s < S; s++) {
-        uint32_t xv[RB], qv[RQ];
+        E xv[RB], qv[RQ];
 #pragma unroll
-        for (int j = 0; j < RB; j++) xv[j] = sx[k * XP + s * TB + tb * RB + j];
+        for (int j = 0; j < RB; j++) xv[j] = __builtin_bit_cast(E, sx[k * XP + s * TB + tb * RB + j]);
 #pragma unroll
-        for (int i = 0; i < RQ; i++) qv[i] = sq[k * QP + s * TQ + tq * RQ + i];
+        for (int i = 0; i < RQ; i++) qv[i] = __builtin_bit_cast(E, sq[k * QP + s * TQ + tq * RQ + i]);
 #pragma unroll
         for (int i = 0; i < RQ; i++)
 #pragma unroll
           for (int j = 0; j < RB; j++) {
-            const uint32_t t = qv[i] & xv[j];
-            m[i][j] = s == 0 ? t : (m[i][j] | t);
+            const E t = A::mul(qv[i], xv[j]);
+            m[i][j] = s == 0 ? t : A::add(m[i][j], t);
           }
       }
 #pragma unroll
       for (int i = 0; i < RQ; i++)
 #pragma unroll
-        for (int j = 0; j < RB; j++) acc[i][j] += (uint32_t)__popc(m[i][j]);
+        for (int j = 0; j < RB; j++) acc[i][j] += A::weigh(m[i][j], sw, k);
     }
   }
 
@@ -200,7 +274,7 @@ __global__ __launch_bounds__(256) void k_tbr_costs(const uint32_t *__restrict__ 
 #pragma unroll
     for (int j = 0; j < RB; j++) {
       const int f = f_lo + tq * RQ + i, g = g_lo + tb * RB + j;
-      if (f < nf && g < ng) out[vd.at + (size_t)f * (size_t)ng + (size_t)g] = bits - acc[i][j];
+      if (f < nf && g < ng) out[vd.at + (size_t)f * (size_t)ng + (size_t)g] = A::finish(acc[i][j], bits);
     }
 }
 
@@ -228,7 +302,7 @@ __global__ __launch_bounds__(64) void k_tbr_best(const TbrVisit *__restrict__ vi
 
 size_t tbr_deep_words(const Geometry &g, TbrSide *sides, size_t n_sides)
 {
-  const size_t tiles = ((size_t)g.Wp + 63) / 64;
+  const size_t tiles = ((size_t)tbr_row_words(g) + 63) / 64;
   size_t at = 0;
   for (size_t i = 0; i < n_sides; i++) {
     sides[i].deep_off = at;
@@ -241,10 +315,18 @@ hipError_t launch_tbr_roots(hipStream_t st, const Geometry &g, const uint32_t *v
                             uint32_t *store, uint32_t *deep)
 {
   if (!vec) return hipErrorInvalidValue;            // (Engine::vec_rows: the rows could not be brought up to date)
-  if (g.sankoff || g.Wp <= 0 || g.Wp % 32) return hipErrorInvalidValue;
+  if (g.Wp <= 0 || g.Wp % 32 || (g.sankoff && (!g.moff || !g.cost || g.costT))) return hipErrorInvalidValue;
   if (!n_sides) return hipSuccess;
-  const size_t tiles = ((size_t)g.Wp + 63) / 64;
+  const int We = tbr_row_words(g);
+  const size_t tiles = ((size_t)We + 63) / 64;
   if (n_sides * tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  if (g.sankoff) {
+    dispatch_snk(g, [&](auto S, auto PK) {
+      hipLaunchKernelGGL((k_tbr_snk_roots<S, PK, tbr_lds_levels(S)>), dim3((unsigned)(n_sides * tiles)), dim3(64), 0, st, vec + g.moff, ops, sides,
+                         (int)tiles, We, g.cost, store, deep);
+    });
+    return hipGetLastError();
+  }
   dispatch_states(g.S, [&](auto S) {
     hipLaunchKernelGGL((k_tbr_roots<S, tbr_lds_levels(S)>), dim3((unsigned)(n_sides * tiles)), dim3(64), 0, st, vec, ops, sides, (int)tiles, g.Wp,
                        store, deep);
@@ -256,18 +338,24 @@ hipError_t launch_tbr_costs(hipStream_t st, const Geometry &g, const uint32_t *v
                             const tbrplan::Item *items, size_t n_items, int shape, uint32_t *out)
 {
   if (!vec) return hipErrorInvalidValue;
-  if (g.sankoff || g.Wp <= 0 || g.Wp % 32 || (shape != tbrplan::TILE_NARROW && shape != tbrplan::TILE_WIDE)) return hipErrorInvalidValue;
+  if (g.Wp <= 0 || g.Wp % 32 || (shape != tbrplan::TILE_NARROW && shape != tbrplan::TILE_WIDE)) return hipErrorInvalidValue;
+  if (g.sankoff && (!g.moff || !g.pwgt || g.costT)) return hipErrorInvalidValue;
   if (!n_items) return hipSuccess;
   if (n_items > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  dispatch_states(g.S, [&](auto S) {
+  // the algebra's kernel in the shape its row of the one table (host/pair_tile.hpp) gives it
+  auto launch = [&](auto a, auto WEIGHTED) {
+    typedef decltype(a) A;
     dispatch_bool(shape == tbrplan::TILE_NARROW, [&](auto NARROW) {
       constexpr int SH = NARROW ? tbrplan::TILE_NARROW : tbrplan::TILE_WIDE;
-      constexpr PlaceShape sh = place_shape(S, false, SH);      // the unweighted row of the one table (host/pair_tile.hpp)
-      static_assert(tbrplan::tile_dims(S, SH).tf == sh.tq && tbrplan::tile_dims(S, SH).tg == sh.tb, "the items were cut for another tile");
-      hipLaunchKernelGGL((k_tbr_costs<S, sh.tq, sh.tb, sh.rq, sh.rb, sh.ks, sh.kt>), dim3((unsigned)n_items), dim3(256), 0, st, vec, store, visits,
-                         items, g.Wp, out);
+      constexpr PlaceShape sh = place_shape(A::S, WEIGHTED, SH);
+      static_assert(tbrplan::tile_dims(A::S, SH, WEIGHTED).tf == sh.tq && tbrplan::tile_dims(A::S, SH, WEIGHTED).tg == sh.tb,
+                    "the items were cut for another tile");
+      hipLaunchKernelGGL((k_tbr_costs<A, sh.tq, sh.tb, sh.rq, sh.rb, sh.ks, sh.kt>), dim3((unsigned)n_items), dim3(256), 0, st, vec, store, visits,
+                         items, tbr_row_words(g), out, g.moff, g.pwgt);
     });
-  });
+  };
+  if (g.sankoff) dispatch_snk(g, [&](auto S, auto PK) { launch(PlaceMinPlus<S, PK, true>(), bool_c<true>()); });
+  else dispatch_states(g.S, [&](auto S) { launch(PlaceFitch<S>(), bool_c<false>()); });
   return hipGetLastError();
 }
 

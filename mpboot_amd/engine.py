@@ -757,12 +757,17 @@ class FitchEngine:
                                            C.byref(tl)))
         return br[:Q], a[:Q], b[:Q], ln[:Q], int(tl.value)
 
-    # ---- TBR (host/tbr.cpp, tbr.hip): no reference function, MPBoot has SPR and NNI only.  Fitch engine without a tracker
+    # ---- TBR (host/tbr.cpp, tbr.hip): no reference function, MPBoot has SPR and NNI only.  An engine without a tracker; a weighted
+    # engine (cost=...) after set_option("tbr_weighted", 1) only, and only with a symmetric cost matrix
     def tbr_scan(self, rec: int, maxtrav: int = 6, cap=None):
         """one visit: (f_recs, g_recs, cost[1 + len(f), 1 + len(g)]) -- cut the edge (rec, back[rec]); g_recs lists the branches of
         rec's part, f_recs those of back[rec]'s part (the SPR scan's one side with mintrav = 1); cost[i][j] = the length of the tree
         that joins the middle of f_recs[i - 1] to the middle of g_recs[j - 1], index 0 = the part's own root: row 0 and column 0
         are SPR tests, cost[0][0] is the current length.  The tree of an entry is trees.apply_tbr(back, rec, f, g).
+        A weighted engine (cost=...) serves this, tbr_sweep_best, apply_tbr and optimize_tbr after set_option("tbr_weighted", 1) only
+        (default 0: MpfError -6 as before): an entry is then the FULL weighted length of the joined tree, in either store
+        ("sankoff_short"); a cost matrix that is not symmetric is refused (-6, "not symmetric": the length would depend on the edge it
+        is evaluated at).
         cap (tests): (cap_f, cap_g) handed to the C call; where one is too small only (n_f, n_g) comes back."""
         L = load_library()
         nf, ng = C.c_int32(), C.c_int32()

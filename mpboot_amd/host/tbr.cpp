@@ -10,8 +10,13 @@
 // scratch store, k_tbr_costs forms every visit's matrix from a flat tile list, k_tbr_best leaves three words per visit.  A sweep's
 // root sets run to several GB at full size, so it goes chunk by chunk; the result does not depend on the chunking.
 //
-// Not served: the weighted (-cost) engine (its cost is a min-plus product rooted at the new edge), an engine with a UFBoot tracker
-// attached (nothing would be booked), random ties, a device-resident climb.
+// The weighted (-cost) engine, under the option "tbr_weighted" (default 0: refused as before): the same lists, chunks and tiles; the
+// root sets are sums of stored min-plus transforms (k_tbr_snk_roots), an entry is the FULL length of the joined tree (no base), a
+// vector is S rows of We elements (patterns, or pairs of patterns in the 16-bit store).  Symmetric cost matrices only: with any
+// other the length depends on the evaluation edge, and TBR has no reference function that would fix one.
+//
+// Not served: a cost matrix that is not symmetric, an engine with a UFBoot tracker attached (nothing would be booked), random ties,
+// a device-resident climb.
 #include <string>
 
 #include "../csrc/engine.hpp"
@@ -34,8 +39,12 @@ struct TbrBuffers {
 
 int Engine::tbr_check(const char *what, int maxtrav)
 {
-  if (sankoff_) {
+  if (sankoff_ && !tbr_weighted_) {
     set_error(std::string(what) + ": TBR is not served on the weighted (-cost) engine (its cost is a min-plus product rooted at the new edge)");
+    return MPF_E_UNSUPPORTED;
+  }
+  if (sankoff_ && g_.costT) {
+    set_error(std::string(what) + ": TBR is not served with a cost matrix that is not symmetric (the length depends on the evaluation edge)");
     return MPF_E_UNSUPPORTED;
   }
   if (ufb_) {
@@ -69,7 +78,8 @@ int Engine::tbr_run(const int32_t *recs, size_t count, int maxtrav, std::vector<
   }
   if (n_pairs) *n_pairs = pairs;
   if (best) best->assign(count, TbrBest{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu});
-  const size_t vec_words = (size_t)S * (size_t)g_.Wp;
+  const bool weighted = sankoff_ != 0;
+  const size_t vec_words = (size_t)S * (size_t)tbr_row_words(g_);      // (weighted: S rows of We elements)
   const size_t cap = tbr_chunk_vectors_ > 0 ? (size_t)tbr_chunk_vectors_ : std::max<size_t>(1, ((size_t)256 << 20) / (vec_words * sizeof(uint32_t)));
   const auto chunks = tbrplan::chunks(need, cap, entries);
   tbr_chunks_ = (int)chunks.size();
@@ -91,14 +101,16 @@ int Engine::tbr_run(const int32_t *recs, size_t count, int maxtrav, std::vector<
         tbrplan::side(n, back, xs[side], maxtrav, scratch_side, &b.v_ops, (uint32_t)nvec);
         nvec += scratch_side.rec.size();
         if (b.v_ops.size() > op_begin)
-          b.v_sides.push_back(TbrSide{op_begin, (uint32_t)b.v_ops.size(), (uint32_t)std::max(0, scratch_side.max_depth + 1 - LD), 0u, 0ull});
+          b.v_sides.push_back(TbrSide{op_begin, (uint32_t)b.v_ops.size(), (uint32_t)std::max(0, scratch_side.max_depth + 1 - LD),
+                                      weighted && side == 1 ? 1u : 0u /* a side of G is stored transformed */, 0ull});
       }
       if (nvec != g0 + v.G.rec.size()) { set_error("TBR: inconsistent plan"); return MPF_E_STATE; }
-      const uint32_t base = (tip(v.p) ? 0u : sc_[v.p]) + (tip(v.q) ? 0u : sc_[v.q]);
+      // (weighted: an entry is the full length of the joined tree, nothing to add)
+      const uint32_t base = weighted ? 0u : (tip(v.p) ? 0u : sc_[v.p]) + (tip(v.q) ? 0u : sc_[v.q]);
       b.v_visits.push_back(TbrVisit{slot(v.q), slot(v.p), (uint32_t)f0, (uint32_t)g0, (uint32_t)v.rows(), (uint32_t)v.cols(), base, 0u, (uint64_t)at});
       at += v.rows() * v.cols();
-      const int shape = tbrplan::pick(S, v.rows(), v.cols(), tbr_tile_);
-      tbrplan::tiles((uint32_t)k, v.rows(), v.cols(), tbrplan::tile_dims(S, shape), b.v_items[shape == tbrplan::TILE_NARROW ? 0 : 1]);
+      const int shape = tbrplan::pick(S, v.rows(), v.cols(), tbr_tile_, weighted);
+      tbrplan::tiles((uint32_t)k, v.rows(), v.cols(), tbrplan::tile_dims(S, shape, weighted), b.v_items[shape == tbrplan::TILE_NARROW ? 0 : 1]);
     }
     if (nvec > 0xFFFFFFFFull) { set_error("TBR: a chunk of more than 2^32 root sets"); return MPF_E_UNSUPPORTED; }
     const size_t deep_words = tbr_deep_words(g_, b.v_sides.data(), b.v_sides.size());
@@ -141,7 +153,8 @@ int Engine::tbr_run(const int32_t *recs, size_t count, int maxtrav, std::vector<
     if (matrix) {
       if (at > 1) matrix->assign(b.h_out.p, b.h_out.p + at);
       else {
-        // the tree as it is: both parts' own lengths plus the sites the two views of the edge do not share
+        // the tree as it is: both parts' own lengths plus the sites the two views of the edge do not share (weighted: the length at the
+        // start edge, which with a symmetric matrix is the length at any edge)
         uint32_t len = 0;
         int rc = tree_length(&len);
         if (rc) return rc;

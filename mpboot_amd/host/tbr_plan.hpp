@@ -109,17 +109,29 @@ inline std::vector<std::pair<size_t, size_t>> chunks(const std::vector<size_t> &
 }
 
 // ---- tiles of the pair product (csrc/tbr.hip).  A workgroup owns tf rows x tg columns of one visit's matrix, in one of the two
-// shapes of the taxon-insertion product: the unweighted rows of its table (pair_tile.hpp), which k_tbr_costs is instantiated from too.
+// shapes of the taxon-insertion product: the rows of its table (pair_tile.hpp) for the engine kind, which k_tbr_costs is instantiated
+// from too.  weighted: the weighted (-cost) engine, where 20 state rows take the 64 x 64 wide tile
 enum { TILE_AUTO = mpf::PLACE_AUTO, TILE_NARROW = mpf::PLACE_NARROW, TILE_WIDE = mpf::PLACE_WIDE };
 struct TileDims { int tf, tg; };
-constexpr TileDims tile_dims(int S, int shape) { return TileDims{mpf::place_shape(S, false, shape).tq, mpf::place_shape(S, false, shape).tb}; }
+constexpr TileDims tile_dims(int S, int shape, bool weighted = false)
+{
+  return TileDims{mpf::place_shape(S, weighted, shape).tq, mpf::place_shape(S, weighted, shape).tb};
+}
 constexpr size_t tiles_of(size_t rows, size_t cols, TileDims d) { return ((rows + (size_t)d.tf - 1) / (size_t)d.tf) * ((cols + (size_t)d.tg - 1) / (size_t)d.tg); }
 // TILE_AUTO: the shape whose tiles cover fewer outputs, padding included.  A wide lane holds 4 x 4 (2 x 2) outputs and reads each
 // staged word once for four (two) of them, a narrow lane holds 4 x 1: a narrow output is charged twice
-inline int pick(int S, size_t rows, size_t cols, int tile)
+// On the weighted engine that rule lost: a wide workgroup walks the whole row alone (a weighted row is 16 to 32 times as long as the
+// Fitch row of the same alignment), so a wide launch takes that long however few tiles it has, while the narrow shape's time grows
+// with the outputs.  Measured on whole sweeps (profiles/tbr/timing_weighted.json): the forced narrow shape took a third
+// of the rule's time at radius 6 and was never slower, the forced wide shape 6 to 17 times the narrow one's.  TILE_AUTO there is
+// narrow below kWeightedWideFrom entries of the visit's own matrix -- near where taxon insertion's two weighted shapes cross
+// (2.45e5 to 3.5e5 outputs; no TBR visit of that size has been timed) -- and wide from there on
+constexpr size_t kWeightedWideFrom = (size_t)1 << 18;
+inline int pick(int S, size_t rows, size_t cols, int tile, bool weighted = false)
 {
   if (tile == TILE_NARROW || tile == TILE_WIDE) return tile;
-  const TileDims a = tile_dims(S, TILE_NARROW), w = tile_dims(S, TILE_WIDE);
+  if (weighted) return rows * cols < kWeightedWideFrom ? TILE_NARROW : TILE_WIDE;
+  const TileDims a = tile_dims(S, TILE_NARROW, weighted), w = tile_dims(S, TILE_WIDE, weighted);
   const size_t narrow = 2 * tiles_of(rows, cols, a) * (size_t)(a.tf * a.tg), wide = tiles_of(rows, cols, w) * (size_t)(w.tf * w.tg);
   return narrow < wide ? TILE_NARROW : TILE_WIDE;
 }
