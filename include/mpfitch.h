@@ -466,7 +466,8 @@ int mpf_iq_parsimony_tree(mpf_engine *e, uint64_t *tie_state, int32_t *order, in
    mpf_spr_scan's tests.  Both stores ("sankoff_short").  Symmetric cost matrices only: with a matrix that is not symmetric the
    length depends on the edge it is evaluated at and TBR has no reference function that would fix one -- MPF_E_UNSUPPORTED, the
    message says "not symmetric".
-   An engine with a UFBoot tracker attached (nothing would be booked) answers MPF_E_UNSUPPORTED on either engine.
+   An engine with a UFBoot tracker attached answers MPF_E_UNSUPPORTED to these five entries on either engine (nothing would be
+   booked): under -bb the sweep and the climb are mpf_ufboot_tbr_sweep and mpf_ufboot_optimize_tbr, below.
    maxtrav outside 1 .. 255: MPF_E_INVALID.  Options: "tbr_tile" (0 = per visit from the padded outputs | 1 =
    narrow, 4 x 16 per workgroup | 2 = wide, 64 x 64 for 4 state rows, 32 x 32 for 20 and 32; on the weighted engine 64 x 64 for 4 and
    20 state rows, 32 x 32 for 32), "tbr_weighted" (above), "tbr_chunk_vectors" (the most
@@ -498,6 +499,35 @@ int mpf_optimize_tbr(mpf_engine *e, int32_t maxtrav, int32_t max_moves, uint32_t
 /* moves of the last mpf_optimize_tbr: (rec, f_rec, g_rec, length after the move); protocol of mpf_get_moves */
 int mpf_get_tbr_moves(const mpf_engine *e, int32_t cap, int32_t *rec, int32_t *f_rec, int32_t *g_rec, uint32_t *score,
                       int32_t *n_moves);
+/* TBR under -bb (a UFBoot tracker attached; host/tbr.cpp, k_tbr_masks in tbr.hip).  No reference function, so this is the
+   definition.  A tracked sweep hands EVERY entry of every visit's matrix to IQTree::saveCurrentTree's rule (iqtree.cpp:3271-3731):
+   the visits in the order of mpf_get_node_order, a visit's entries in row-major order from [0][0].  [0][0] is the current tree under
+   its own length (as rearrangeParsimony opens every prune node with a booking of the current tree, sprparsimony.cpp:2285-2289),
+   every other entry the joined tree under cost[i][j]; a visit with a 1 x 1 matrix books the current tree only.  A booking is the
+   cut-off filter, a new entry of treels_logl, then the per-sample update rule, whose tie draws come from the engine's one stream in
+   that order.  Duplicated topologies are booked as often as they occur (row 0 and column 0 repeat SPR tests).
+   Per site, pattern_pars(T_ij) = pattern_pars(T) - M[0][0] + M[i][j] with M[i][j] the 1-bit-per-site word "R_q(F_i) and R_rec(G_j)
+   share no state" whose popcount k_tbr_costs takes: k_tbr_masks writes that word for every entry that passes the cut-off and for each
+   visit's [0][0], and the tracker's product, extraction and replay run on those rows as they do on the SPR scan's and the NNI step's.
+   The entries are booked in batches of at most "tbr_book_rows" consecutive entries (option; 0 = the mask rows and the product of a
+   batch each stay within 256 MiB); books and draws do not depend on it, nor on "tbr_chunk_vectors".  Read-only options "tbr_booked"
+   (trees handed over since the attach), "tbr_book_batches" and, under "timing", "tbr_masks_ns", "tbr_product_ns", "tbr_extract_ns".
+   Served: the default update rule, -mulhits, a logl_cutoff, -cutoff_from_btrees.  On a suspended tracker (mpf_set_weights left an
+   attach-time pattern without a site, or re-weighted patterns with ratchet booking off) both run as their plain counterparts and
+   book nothing.  MPF_E_STATE without a tracker or a tree.  MPF_E_UNSUPPORTED, the message naming the case: the weighted engine,
+   -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, re-weighted (ratchet) patterns with ratchet
+   booking on.
+   mpf_ufboot_tbr_sweep: mpf_tbr_sweep_best (same outputs) with every entry booked.  The tree does not change. */
+int mpf_ufboot_tbr_sweep(mpf_engine *e, int32_t maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs);
+/* mpf_optimize_tbr's steepest descent with every sweep booked as above, the last sweep, which finds nothing, included (a climb that
+   stops at max_moves runs no sweep behind its last move).  The climb itself draws nothing.  Moves: mpf_get_tbr_moves. */
+int mpf_ufboot_optimize_tbr(mpf_engine *e, int32_t maxtrav, int32_t max_moves, uint32_t *score, int32_t *n_moves);
+/* DIAGNOSTIC, with the standing of mpf_nni_pattern_terms: the rows k_tbr_masks writes for ONE visit (every entry, [0][0] included),
+   read back per original pattern: terms[(i * (1 + *n_g) + j) * n_patterns + p] = the bit of M[i][j] at pattern p's first site, 0 for
+   a pattern the engine drops, so that pattern_pars(T_ij) = pattern_pars(T) - terms[0][0] + terms[i][j].  *n_f and *n_g (the lists'
+   sizes, as mpf_tbr_scan gives them) are always set; terms is filled if cap_entries >= (1 + *n_f) * (1 + *n_g).  Works with or
+   without a tracker and books nothing; Fitch engines only. */
+int mpf_tbr_pattern_terms(mpf_engine *e, int32_t rec, int32_t maxtrav, int64_t cap_entries, uint8_t *terms, int32_t *n_f, int32_t *n_g);
 /* The summary of a -bb run: split supports and the bootstrap consensus tree.  The reference weights the booked trees by the samples
    that point to them (IQTree::summarizeBootstrap, iqtree.cpp:4020-4165), turns every tree into Split objects through its Newick
    string and counts them in a hash map (MTreeSet::convertSplits, mtreeset.cpp:288-470), and builds the consensus from the counted

@@ -509,6 +509,39 @@ int mpf_get_tbr_moves(const mpf_engine *e, int32_t cap, int32_t *rec, int32_t *f
   return MPF_OK;
 }
 
+// ... under -bb: every entry of every visit booked through the tracker (host/tbr.cpp, "under -bb")
+int mpf_ufboot_tbr_sweep(mpf_engine *e, int32_t maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs)
+{
+  NEED(e);
+  if (!best_cost || !best_f || !best_g) { set_error("null output"); return MPF_E_INVALID; }
+  return e->eng.ufboot_tbr_sweep(maxtrav, best_cost, best_f, best_g, n_pairs);
+}
+
+int mpf_ufboot_optimize_tbr(mpf_engine *e, int32_t maxtrav, int32_t max_moves, uint32_t *score, int32_t *n_moves)
+{
+  NEED(e);
+  return e->eng.ufboot_optimize_tbr(maxtrav, max_moves, score, n_moves);
+}
+
+int mpf_tbr_pattern_terms(mpf_engine *e, int32_t rec, int32_t maxtrav, int64_t cap_entries, uint8_t *terms, int32_t *n_f, int32_t *n_g)
+{
+  NEED(e);
+  if (!n_f || !n_g) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<int32_t> f, g;
+  std::vector<uint8_t> t;
+  // the lists first: the rows are made only where they can be handed over
+  int rc = e->eng.tbr_pattern_terms(rec, maxtrav, f, g, nullptr);
+  if (rc) return rc;
+  *n_f = (int32_t)f.size();
+  *n_g = (int32_t)g.size();
+  if (cap_entries < (int64_t)(1 + f.size()) * (int64_t)(1 + g.size())) return MPF_OK;
+  if (!terms) { set_error("null output"); return MPF_E_INVALID; }
+  rc = e->eng.tbr_pattern_terms(rec, maxtrav, f, g, &t);
+  if (rc) return rc;
+  std::memcpy(terms, t.data(), t.size());
+  return MPF_OK;
+}
+
 int mpf_place_taxa(mpf_engine *e,int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_query,
                    const int32_t *query_taxa, int32_t *best_branch, int32_t *best_node1, int32_t *best_node2, uint32_t *best_length,
                    uint32_t *tree_length)

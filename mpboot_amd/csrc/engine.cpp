@@ -1907,6 +1907,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "tbr_tile") { if (v < 0 || v > 2) { set_error("tbr_tile: 0 (per visit, from the padded outputs), 1 (narrow: 4 x 16) or 2 (wide)"); return MPF_E_INVALID; } tbr_tile_ = (int)v; return MPF_OK; }
   if (key == "tbr_chunk_vectors") { if (v < 0) { set_error("tbr_chunk_vectors: the most root-set vectors of a chunk, 0 = 256 MiB worth"); return MPF_E_INVALID; } tbr_chunk_vectors_ = v; return MPF_OK; }
   if (key == "place_tile") { if (v < 0 || v > 2) { set_error("place_tile: 0 (from the number of outputs), 1 (narrow: 4 queries x 16 branches) or 2 (wide)"); return MPF_E_INVALID; } place_tile_ = (int)v; return MPF_OK; }
+  if (key == "tbr_book_rows") { if (v < 0) { set_error("tbr_book_rows: the most entries of a booking batch of a tracked TBR sweep, 0 = 256 MiB worth"); return MPF_E_INVALID; } tbr_book_rows_ = v; return MPF_OK; }
   if (key == "tbr_weighted") { tbr_weighted_ = v ? 1 : 0; return MPF_OK; }       // TBR under -cost (host/tbr.cpp); no effect on a Fitch engine
   if (key == "place_weighted") { place_weighted_ = v ? 1 : 0; return MPF_OK; }   // taxon insertion under -cost (host/place.cpp); no effect on a Fitch engine
   if (key == "poly_tile") { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32) { set_error("poly_tile: 0 (from the row length), 4, 8, 16 or 32 words per workgroup"); return MPF_E_INVALID; } poly_tile_ = (int)v; return MPF_OK; }
@@ -2043,6 +2044,12 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "place_tile") *v = place_tile_;
   else if (key == "place_weighted") *v = place_weighted_;
   else if (key == "tbr_weighted") *v = tbr_weighted_;
+  else if (key == "tbr_book_rows") *v = tbr_book_rows_;
+  else if (key == "tbr_booked") *v = ufb_ ? (int64_t)ufb_->tbr_booked : 0;
+  else if (key == "tbr_book_batches") *v = ufb_ ? (int64_t)ufb_->tbr_book_batches : 0;
+  else if (key == "tbr_masks_ns") *v = (int64_t)tbr_masks_ns_;
+  else if (key == "tbr_product_ns") *v = (int64_t)tbr_product_ns_;
+  else if (key == "tbr_extract_ns") *v = (int64_t)tbr_extract_ns_;
   else if (key == "place_shape") *v = place_shape_;
   // what launch_scan dispatched for the last weighted batch (0 before the first): rows through 64-bit pointers (BUF off) / k_snk_scan_deep;
   // and, since creation, the batches k_snk_scan_deep served and the launches they were cut into

@@ -179,6 +179,7 @@ struct UfbState : books::Deferred {      // (boot_trees, store, refs, topo_index
   const std::vector<ScanPlan> *log_plans = nullptr;
   uint64_t draws = 0, events = 0, gemm_rows = 0, batches = 0, stored = 0;
   uint64_t nni_booked = 0;                       // trees NNI climbs have handed to saveCurrentTree (read-only option "nni_booked")
+  uint64_t tbr_booked = 0, tbr_book_batches = 0; // ... tracked TBR sweeps have (read-only options "tbr_booked", "tbr_book_batches")
   uint32_t nni_tag = 0;                          // sample-sharded tracker: scoring steps of the NNI climb under way that exchanged their events
   double gemm_ms = 0.0;
   double t_lookup = 0;                           // ... of t_replay: canonical forms for the topology map
@@ -401,6 +402,18 @@ class Engine {
   int apply_tbr(int rec, int f_rec, int g_rec, uint32_t *score);      // == set_tree(the edited back[]) + score_tree
   int optimize_tbr(int maxtrav, int max_moves, uint32_t *score, int32_t *n_moves);      // steepest descent, no tie draw
   const std::vector<TbrMove> &tbr_moves() const { return tbr_moves_; }
+  // ---- ... under -bb (a UFBoot tracker attached).  No reference function either, so this is the definition: a tracked sweep hands
+  // EVERY entry of every visit's matrix to saveCurrentTree's rule -- the visits in node_order(), a visit's entries in row-major order
+  // from [0][0]; [0][0] is the current tree under its own length (as rearrangeParsimony opens every prune node with a booking of the
+  // current tree), every other entry the joined tree under cost[i][j]; a 1 x 1 visit books the current tree only.  Duplicated
+  // topologies are booked as often as they occur (row 0 and column 0 repeat SPR tests).  Served: the default rule, -mulhits, a
+  // cut-off, -cutoff_from_btrees.  A suspended tracker books nothing.  ufboot_tbr_sweep = tbr_sweep_best with every entry booked
+  // (the tree stays); ufboot_optimize_tbr = optimize_tbr with every sweep booked, the last one, which finds nothing, included
+  int ufboot_tbr_sweep(int maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs);
+  int ufboot_optimize_tbr(int maxtrav, int max_moves, uint32_t *score, int32_t *n_moves);
+  // DIAGNOSTIC (no tracker needed, Fitch engine): the mask rows k_tbr_masks writes for one visit, read back per original pattern:
+  // terms[(i * (1 + |g|) + j) * P + p] = the bit of M[i][j] at the first site of pattern p, 0 for a pattern the engine drops
+  int tbr_pattern_terms(int rec, int maxtrav, std::vector<int32_t> &f, std::vector<int32_t> &g, std::vector<uint8_t> *terms);
 
   // ---- the summary of a -bb run (host/splits.cpp, splits.hip; reference IQTree::summarizeBootstrap, MTreeSet::convertSplits,
   // computeConsensusTree): the splits of a weighted set of complete trees counted exactly on the device, the supports of a target
@@ -742,9 +755,20 @@ class Engine {
   std::vector<TbrMove> tbr_moves_;
   std::shared_ptr<TbrBuffers> tbr_buf_;          // (defined in host/tbr.cpp: this header does not read tbr.hpp)
   struct TbrBest { uint32_t cost, row, col; };
-  int tbr_check(const char *what, int maxtrav);
+  int tbr_check(const char *what, int maxtrav, bool tracked = false);
+  // option "tbr_book_rows": the most entries of one booking batch of a tracked sweep (0 = the mask rows and the product each stay
+  // within 256 MiB); under "timing": "tbr_masks_ns", "tbr_product_ns" (HIP events), "tbr_extract_ns" (the rest of the device half)
+  int64_t tbr_book_rows_ = 0;
+  uint64_t tbr_masks_ns_ = 0, tbr_product_ns_ = 0, tbr_extract_ns_ = 0;
+  int tbr_tracked_check(const char *what, int maxtrav);
+  int tbr_edit(int rec, int f_rec, int g_rec, uint32_t *score);       // apply_tbr behind its checks
+  int tbr_climb(int maxtrav, int max_moves, bool tracked, uint32_t *score, int32_t *n_moves);
+  // what a chunk of tbr_run is handed to while its root sets and cost matrices stand: (first visit, visits, cost matrices on the host)
+  using TbrChunkFn = std::function<int(size_t, size_t, const uint32_t *)>;
+  struct TbrReplay;
+  int tbr_book_chunk(const tbrplan::Visit *vis, size_t nv, const uint32_t *cost, uint32_t cur_len);
   int tbr_run(const int32_t *recs, size_t count, int maxtrav, std::vector<tbrplan::Visit> &vis, std::vector<uint32_t> *matrix,
-              std::vector<TbrBest> *best, uint64_t *n_pairs);
+              std::vector<TbrBest> *best, uint64_t *n_pairs, const TbrChunkFn *chunk_fn = nullptr);
 
   int addition_phase(int64_t seed, uint32_t *best_per_step, int32_t *insert_per_step);
   void apply_move(int remove_rec, int insert_rec);

@@ -11,6 +11,7 @@
 //                before this slice's arithmetic.  Index 0 of either side reads the resident vector, the rest the scratch store:
 //                absolute 64-bit row pointers.  The launch is a flat list of (visit, F tile, G tile) items.  One writer per output
 //   k_tbr_best   one wave per visit: the first minimum of its matrix, [0][0] left out
+//   k_tbr_masks  under a UFBoot tracker: the "no common state" word itself, one mask row per listed entry (host/tbr.cpp)
 // Padding bits are set in every state row of every resident vector, so they are in every U and every root set, and always match.
 //
 // On the weighted (-cost) engine (option "tbr_weighted", symmetric cost matrices) the same plan runs over the min-plus algebra, m()
@@ -298,7 +299,51 @@ __global__ __launch_bounds__(64) void k_tbr_best(const TbrVisit *__restrict__ vi
   }
 }
 
+// The mask rows a UFBoot tracker needs of a visit's matrix (host/tbr.cpp): masks[out][w] = ~OR over the state rows of (row i of F
+// & column j of G), the very word whose popcount k_tbr_costs takes, laid out as k_join_masks lays a row (Wp words, bit b of word w =
+// site 32 w + b; padding bits are set in every state row of both operands and so come out 0).  One wave per (run, tile of 64 site
+// words): a run is one row i of one visit with a list of its columns; the lane keeps its word of RF_i's S state rows in registers,
+// walks the run's columns and stores one coalesced 256-byte stretch per column.  Index 0 of either side reads the resident vector.
+// One writer per word, no LDS, no atomics; the run and column records are wave-uniform
+template <int S>
+__global__ __launch_bounds__(64) void k_tbr_masks(const uint32_t *__restrict__ vec, const uint32_t *__restrict__ store,
+                                                  const TbrVisit *__restrict__ visits, const tbrplan::MaskRun *__restrict__ runs,
+                                                  const tbrplan::MaskCol *__restrict__ cols, int tiles, int Wp, uint32_t *__restrict__ masks)
+{
+  const size_t run = (size_t)blockIdx.x / (size_t)tiles, tile = (size_t)blockIdx.x % (size_t)tiles;
+  const size_t w = tile * 64 + (size_t)threadIdx.x, row = (size_t)Wp, vsz = (size_t)S * row;
+  if (w >= row) return;                              // (Wp is a multiple of 32: the last tile may be half full)
+  const tbrplan::MaskRun r = runs[run];
+  const TbrVisit vd = visits[r.visit];
+  const uint32_t *pf = (r.row == 0 ? vec + (size_t)vd.slot_q * vsz : store + ((size_t)vd.f0 + (size_t)(r.row - 1)) * vsz) + w;
+  uint32_t rf[S];
+#pragma unroll
+  for (int s = 0; s < S; s++) rf[s] = pf[(size_t)s * row];
+  for (uint32_t c = r.begin; c < r.end; c++) {
+    const tbrplan::MaskCol cj = cols[c];
+    const uint32_t *pg = (cj.col == 0 ? vec + (size_t)vd.slot_p * vsz : store + ((size_t)vd.g0 + (size_t)(cj.col - 1)) * vsz) + w;
+    uint32_t any = 0u;
+#pragma unroll
+    for (int s = 0; s < S; s++) any |= rf[s] & pg[(size_t)s * row];
+    masks[(size_t)cj.out * row + w] = ~any;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_tbr_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
+                            const tbrplan::MaskRun *runs, size_t n_runs, const tbrplan::MaskCol *cols, uint32_t *masks)
+{
+  if (!vec) return hipErrorInvalidValue;
+  if (g.sankoff || g.Wp <= 0 || g.Wp % 32) return hipErrorInvalidValue;      // (a mask row is a Fitch join)
+  if (!n_runs) return hipSuccess;
+  const size_t tiles = ((size_t)g.Wp + 63) / 64;
+  if (n_runs * tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  dispatch_states(g.S, [&](auto S) {
+    hipLaunchKernelGGL((k_tbr_masks<S>), dim3((unsigned)(n_runs * tiles)), dim3(64), 0, st, vec, store, visits, runs, cols, (int)tiles, g.Wp, masks);
+  });
+  return hipGetLastError();
+}
 
 size_t tbr_deep_words(const Geometry &g, TbrSide *sides, size_t n_sides)
 {

@@ -41,5 +41,11 @@ hipError_t launch_tbr_costs(hipStream_t st, const Geometry &g, const uint32_t *v
 // best[3 v] = the first minimum of visit v's matrix in row-major order, [0][0] left out, best[3 v + 1], [3 v + 2] = its row and
 // column; 0xFFFFFFFF all three for a 1 x 1 matrix (one wave per visit)
 hipError_t launch_tbr_best(hipStream_t st, const TbrVisit *visits, size_t n_visits, const uint32_t *out, uint32_t *best);
+// Under a UFBoot tracker (k_tbr_masks; Fitch engine).  Per site, pattern_pars(T_ij) = pattern_pars(T) - M[0][0] + M[i][j] with M[i][j]
+// the 1-bit-per-site word "R_q(F_i) and R_p(G_j) share no state" (each part's own per-site length does not depend on where it is
+// rooted).  masks[col.out][0 .. Wp) = M[run.row][col.col] of visit run.visit for every column cols[run.begin .. run.end) of every run:
+// rows in the form of launch_join_masks, ready for the REPS product.  Every `out` must lie inside masks; one entry, one writer
+hipError_t launch_tbr_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
+                            const tbrplan::MaskRun *runs, size_t n_runs, const tbrplan::MaskCol *cols, uint32_t *masks);
 
 }  // namespace mpf

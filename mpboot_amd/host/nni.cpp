@@ -385,56 +385,7 @@ struct Engine::NniReplay {
   }
 };
 
-// One step's event extraction.  Output indices: 0 = the current tree (offered on the host), 1 + c = candidate c, behind them the
-// home slots; part[idx] = the part of a candidate (0xFFFFFFFF: no candidate), home[part] = its home slot, crow[idx] = the row of C
-// an index reads (0xFFFFFFFF: none), pass[c]: candidate c takes part (under -storetrees every one does: the replay decides).  sel_rows (or nullptr): the mask rows a compact product
-// multiplies, handed to product(rows_p, device copy) -- which runs here unless the caller has C already.  events: in replay order.
-// staging: thr[n_parts] | home[n_parts] | best[Bp] | crow[n_idx] | cost[n_idx] | (even) info[n_idx] as pairs | sel[rows_p] | event counter
-template <class Product>
-int Engine::nni_extract_events(uint32_t n_idx, const std::vector<uint32_t> &home, const std::vector<uint32_t> &part, const std::vector<uint32_t> &crow,
-                               const std::vector<uint8_t> &pass, const std::vector<uint32_t> *sel_rows, int rows_p, bool have_C, Product product,
-                               std::vector<UfbEvent> &events)
-{
-  UfbState &u = *ufb_;
-  const size_t n_parts = home.size();
-  const size_t o_home = n_parts, o_best = 2 * n_parts, o_crow = o_best + (size_t)u.Bp, o_cost = o_crow + n_idx;
-  const size_t o_info = (o_cost + n_idx + 1) & ~(size_t)1, o_sel = o_info + 2 * (size_t)n_idx, o_cnt = o_sel + (sel_rows ? (size_t)rows_p : 0);
-  UCHK(u.h_small.reserve(o_cnt + 4));
-  UCHK(u.thr.reserve(o_cnt + 4));
-  uint32_t *sm = u.h_small.p;
-  std::memset(sm, 0, (o_cnt + 1) * sizeof(uint32_t));           // (padding columns of best: 0 -> never an event; padding rows multiply mask row 0)
-  for (size_t i = 0; i < n_parts; i++) { sm[i] = 1u; sm[o_home + i] = home[i]; }            // a candidate takes part iff cost < 1
-  for (int c2 = 0; c2 < u.Bl; c2++) sm[o_best + (size_t)c2] = ufb_event_bound((uint32_t)u.ids[(size_t)c2]);
-  std::memcpy(sm + o_crow, crow.data(), (size_t)n_idx * sizeof(uint32_t));
-  for (uint32_t idx = 0; idx < n_idx; idx++) { sm[o_info + 2 * idx] = 0u; sm[o_info + 2 * idx + 1] = 0xFFFFFFFFu; }      // the current tree, the home slots
-  for (uint32_t c = 0; c < (uint32_t)pass.size(); c++) {
-    sm[o_cost + 1 + c] = pass[c] ? 0u : 1u;
-    sm[o_info + 2 * (1 + c)] = crow[1 + c];
-    sm[o_info + 2 * (1 + c) + 1] = part[1 + c];
-  }
-  if (sel_rows) std::memcpy(sm + o_sel, sel_rows->data(), sel_rows->size() * sizeof(uint32_t));
-  UCHK(hipMemcpyAsync(u.thr.p, sm, (o_cnt + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
-  if (!have_C) { int rc = product(rows_p, sel_rows ? u.thr.p + o_sel : nullptr); if (rc) return rc; }
-  uint32_t n_ev = 0;
-  // the list rules and -storetrees see every (candidate, sample) at or below the sample's bound at the start of the step, not only the
-  // strict improvements of a running minimum (as spr_sweeps_ufboot asks for them)
-  const UfbExtract x{reinterpret_cast<const uint2 *>(u.thr.p + o_info), u.thr.p + o_cost, u.thr.p, u.thr.p + o_home, u.thr.p + o_crow, u.thr.p + o_best,
-                     u.thr.p + o_cnt, n_idx, (u.topboot || u.distinct || u.store_trees) ? 1 : 0,
-                     false};        // (no eager prefix: a step's events are fetched in one copy behind the count, as they always were here)
-  { int rc = ufb_extract_events(x, n_ev); if (rc) return rc; }
-  events.clear();
-  if (n_ev) {
-    events.assign(u.h_ev.p, u.h_ev.p + n_ev);
-    for (UfbEvent &e : events) e.b = (uint32_t)u.ids[(size_t)e.b];
-    if (!u.exchange) {                             // (a sample-sharded tracker orders the merged events: nni_exchange_events)
-      std::vector<UfbEvent> tmp;
-      std::vector<uint32_t> count;
-      sort_events(events, tmp, count, n_idx, (uint32_t)u.B);
-    }
-  }
-  u.events += n_ev;
-  return MPF_OK;
-}
+// (One step's event extraction, nni_extract_events, is in ufboot_common.hpp: the tracked TBR sweep, host/tbr.cpp, runs it too.)
 
 // A sample-sharded tracker: the product and the extraction ran over this rank's columns, R_T (u.h_rt) holds its samples only.  ONE
 // exchange per scoring step: the step's local events and, as index 0, the current tree's score under every local sample; every rank

@@ -1,5 +1,5 @@
 // tbr_plan.hpp -- what a TBR (tree bisection and reconnection) visit is, as far as it follows from back[] alone.  Device-free: no HIP
-// header, no engine; host/tbr.cpp and the stand-alone program tests/tbr_plan_main.cpp both read it.
+// header, no engine; host/tbr.cpp and the stand-alone programs tests/tbr_plan_main.cpp and tests/tbr_book_main.cpp read it.
 //
 // There is no reference function: MPBoot has SPR and NNI only.  A visit is a record p, its edge (p, q = back[p]) and a radius.  Cut
 // the edge; G lists the branches of p's part, F those of q's part, both as one_side of Engine::plan_scan enumerates them with
@@ -141,6 +141,66 @@ inline void tiles(uint32_t visit, size_t rows, size_t cols, TileDims d, std::vec
   if (rows * cols <= 1) return;                      // (a 1 x 1 matrix: the tree as it is, nothing to score)
   for (size_t ft = 0; ft * (size_t)d.tf < rows; ft++)
     for (size_t gt = 0; gt * (size_t)d.tg < cols; gt++) out.push_back(Item{visit, (uint32_t)ft, (uint32_t)gt, 0u});
+}
+
+// ---- a sweep under a UFBoot tracker (host/tbr.cpp).  Every entry of every visit's matrix is handed to the tracker: the visits in
+// sweep order, a visit's entries in row-major order from [0][0] (the tree as it is).  A batch is a stretch of that sequence of at
+// most `cap` entries; the part of one visit that falls into a batch is a run.  A visit larger than what is left of a batch goes on in
+// the next one, so a large visit is booked in consecutive blocks of its matrix, wherever in a row a block may end.
+struct BookRun { uint32_t visit, pad; uint64_t begin, end; };      // entries [begin, end) of the visit's matrix, row-major
+// entries[v] = rows x columns of visit v  ->  runs, and off: batch b is runs[off[b] .. off[b + 1])
+inline void book_batches(const std::vector<size_t> &entries, size_t cap, std::vector<BookRun> &runs, std::vector<size_t> &off)
+{
+  runs.clear();
+  off.assign(1, 0);
+  if (cap < 1) cap = 1;
+  size_t room = cap;
+  for (size_t v = 0; v < entries.size(); v++)
+    for (size_t at = 0; at < entries[v];) {
+      if (!room) { off.push_back(runs.size()); room = cap; }
+      const size_t take = std::min(room, entries[v] - at);
+      runs.push_back(BookRun{(uint32_t)v, 0u, (uint64_t)at, (uint64_t)(at + take)});
+      at += take;
+      room -= take;
+    }
+  if (!runs.empty()) off.push_back(runs.size());
+}
+
+// The mask rows one batch needs (k_tbr_masks, csrc/tbr.hip): one per entry that takes part, and per run with such an entry the
+// visit's home row M[0][0] in front of them -- also where the run begins behind [0][0].  Entry [0][0] itself never takes a row of its
+// own (it is the current tree).  A MaskRun is one matrix row of one visit with at most kMaskRunCols listed columns: one wave's work.
+// take[c]: entry c of the batch, counted through its runs, takes part.  -> rows used; crow[c] = the row of entry c, home[r] = the home
+// row of run r, kNoRow where there is none
+constexpr uint32_t kNoRow = 0xFFFFFFFFu, kMaskRunCols = 32;
+struct MaskRun { uint32_t visit, row, begin, end; };      // columns cols[begin .. end)
+struct MaskCol { uint32_t col, out; };                    // column of the matrix, output row
+inline uint32_t mask_rows(const BookRun *runs, size_t n_runs, const uint32_t *ncols /* by visit */, const uint8_t *take,
+                          std::vector<MaskRun> &mr, std::vector<MaskCol> &mc, std::vector<uint32_t> &crow, std::vector<uint32_t> &home)
+{
+  mr.clear();
+  mc.clear();
+  crow.clear();
+  home.assign(n_runs, kNoRow);
+  uint32_t rows = 0;
+  size_t c = 0;
+  auto add = [&](uint32_t visit, uint32_t row, uint32_t col, uint32_t out) {
+    if (mr.empty() || mr.back().visit != visit || mr.back().row != row || mr.back().end - mr.back().begin >= kMaskRunCols)
+      mr.push_back(MaskRun{visit, row, (uint32_t)mc.size(), (uint32_t)mc.size()});
+    mc.push_back(MaskCol{col, out});
+    mr.back().end = (uint32_t)mc.size();
+  };
+  for (size_t r = 0; r < n_runs; r++) {
+    const BookRun &run = runs[r];
+    const uint64_t ng = ncols[run.visit];
+    for (uint64_t e = run.begin; e < run.end; e++, c++) {
+      crow.push_back(kNoRow);
+      if (e == 0 || !take[c]) continue;
+      if (home[r] == kNoRow) { home[r] = rows; add(run.visit, 0u, 0u, rows++); }
+      crow.back() = rows;
+      add(run.visit, (uint32_t)(e / ng), (uint32_t)(e % ng), rows++);
+    }
+  }
+  return rows;
 }
 
 // ---- the edit.  removeNodeParsimony + insertParsimony (sprparsimony.cpp:2245-2257, :1942-1952) on back[]: the node of record p leaves
