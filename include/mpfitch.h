@@ -514,8 +514,8 @@ int mpf_get_tbr_moves(const mpf_engine *e, int32_t cap, int32_t *rec, int32_t *f
    (trees handed over since the attach), "tbr_book_batches" and, under "timing", "tbr_masks_ns", "tbr_product_ns", "tbr_extract_ns".
    Served: the default update rule, -mulhits, a logl_cutoff, -cutoff_from_btrees.  On a suspended tracker (mpf_set_weights left an
    attach-time pattern without a site, or re-weighted patterns with ratchet booking off) both run as their plain counterparts and
-   book nothing.  MPF_E_STATE without a tracker or a tree.  MPF_E_UNSUPPORTED, the message naming the case: the weighted engine,
-   -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, re-weighted (ratchet) patterns with ratchet
+   book nothing.  MPF_E_STATE without a tracker or a tree.  MPF_E_UNSUPPORTED, the message naming the case: the weighted engine
+   (unless its options "tbr_weighted" and "tbr_weighted_tracked" are both 1: see mpf_tbr_pattern_lengths below), -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, re-weighted (ratchet) patterns with ratchet
    booking on.
    mpf_ufboot_tbr_sweep: mpf_tbr_sweep_best (same outputs) with every entry booked.  The tree does not change. */
 int mpf_ufboot_tbr_sweep(mpf_engine *e, int32_t maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs);
@@ -528,6 +528,27 @@ int mpf_ufboot_optimize_tbr(mpf_engine *e, int32_t maxtrav, int32_t max_moves, u
    sizes, as mpf_tbr_scan gives them) are always set; terms is filled if cap_entries >= (1 + *n_f) * (1 + *n_g).  Works with or
    without a tracker and books nothing; Fitch engines only. */
 int mpf_tbr_pattern_terms(mpf_engine *e, int32_t rec, int32_t maxtrav, int64_t cap_entries, uint8_t *terms, int32_t *n_f, int32_t *n_g);
+/* TBR under -bb on the weighted engine (-cost m -bb; host/tbr.cpp, k_tbr_snk_vals in tbr.hip).  Option "tbr_weighted_tracked"
+   (mpf_set_option; default 0, no effect on a Fitch engine): with 0, or with "tbr_weighted" 0, a weighted engine answers
+   MPF_E_UNSUPPORTED to mpf_ufboot_tbr_sweep and mpf_ufboot_optimize_tbr with the message it had.  With both options 1 the two
+   entries are served under the definition above, unchanged: every entry of every visit's matrix, visits in sweep order, entries
+   row-major from [0][0], [0][0] the current tree under its own length, duplicates booked as often as they occur.  On this engine
+   an entry's length is cost[i][j], the full weighted length mpf_tbr_scan returns; its _pattern_pars row is, per pattern,
+   min_x(R_q(F_i)[x] + m(R_rec(G_j))[x]), the terms whose weighted sum cost[i][j] is (k_tbr_snk_vals writes them as 16-bit values for
+   the entries that pass the cut-off and one home row per visit; k_vals_planes and K runs of k_bitgemm form the product, as for the
+   weighted tracked NNI climb); a tree's score under sample b is its OWN product row.  Symmetric cost matrices only ("tbr_weighted"'s
+   condition): the current tree's row is then the same at every cut edge.  Served and refused as above -- default rule, -mulhits, a
+   cut-off, -cutoff_from_btrees; a suspended tracker runs the plain weighted sweep or climb and books nothing; MPF_E_UNSUPPORTED by
+   name for a matrix that is not symmetric, -storetrees, -mulhits -topboot, -distinct_iter_top_boot, a sample-sharded tracker, a
+   ratchet state -- and, in the 32-bit store ("sankoff_short" 0 or costs too large for the 16-bit store), for an engine with
+   n_taxa x (largest cost + 1) >= 65536, whose per-pattern lengths might not fit their 16-bit rows (nothing is ever truncated).
+   "tbr_book_rows" 0 on this engine: the 16-bit rows, the bit planes and the product of a batch each stay within 256 MiB.
+   mpf_tbr_pattern_lengths: DIAGNOSTIC, the counterpart of mpf_nni_pattern_lengths with the calling shape and standing of
+   mpf_tbr_pattern_terms: the rows k_tbr_snk_vals writes for ONE visit (every entry, [0][0] included), read back per original
+   pattern: rows[(i * (1 + *n_g) + j) * n_patterns + p] = the per-pattern length of the tree of entry [i][j] at pattern p, 0 for a
+   pattern the engine drops; the weighted sum of a row is cost[i][j].  Works with or without a tracker and books nothing; weighted
+   engines with both options only (a Fitch engine: MPF_E_UNSUPPORTED, it has mpf_tbr_pattern_terms, which stays Fitch only). */
+int mpf_tbr_pattern_lengths(mpf_engine *e, int32_t rec, int32_t maxtrav, int64_t cap_entries, uint16_t *rows, int32_t *n_f, int32_t *n_g);
 /* The summary of a -bb run: split supports and the bootstrap consensus tree.  The reference weights the booked trees by the samples
    that point to them (IQTree::summarizeBootstrap, iqtree.cpp:4020-4165), turns every tree into Split objects through its Newick
    string and counts them in a hash map (MTreeSet::convertSplits, mtreeset.cpp:288-470), and builds the consensus from the counted

@@ -542,6 +542,25 @@ int mpf_tbr_pattern_terms(mpf_engine *e, int32_t rec, int32_t maxtrav, int64_t c
   return MPF_OK;
 }
 
+int mpf_tbr_pattern_lengths(mpf_engine *e, int32_t rec, int32_t maxtrav, int64_t cap_entries, uint16_t *rows, int32_t *n_f, int32_t *n_g)
+{
+  NEED(e);
+  if (!n_f || !n_g) { set_error("null output"); return MPF_E_INVALID; }
+  std::vector<int32_t> f, g;
+  std::vector<uint16_t> t;
+  // the lists first: the rows are made only where they can be handed over
+  int rc = e->eng.tbr_pattern_lengths(rec, maxtrav, f, g, nullptr);
+  if (rc) return rc;
+  *n_f = (int32_t)f.size();
+  *n_g = (int32_t)g.size();
+  if (cap_entries < (int64_t)(1 + f.size()) * (int64_t)(1 + g.size())) return MPF_OK;
+  if (!rows) { set_error("null output"); return MPF_E_INVALID; }
+  rc = e->eng.tbr_pattern_lengths(rec, maxtrav, f, g, &t);
+  if (rc) return rc;
+  std::memcpy(rows, t.data(), t.size() * sizeof(uint16_t));
+  return MPF_OK;
+}
+
 int mpf_place_taxa(mpf_engine *e,int32_t n_inner, const int32_t *first, const int32_t *nbr, int32_t root_taxon, int32_t n_query,
                    const int32_t *query_taxa, int32_t *best_branch, int32_t *best_node1, int32_t *best_node2, uint32_t *best_length,
                    uint32_t *tree_length)

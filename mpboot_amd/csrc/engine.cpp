@@ -1909,6 +1909,7 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "place_tile") { if (v < 0 || v > 2) { set_error("place_tile: 0 (from the number of outputs), 1 (narrow: 4 queries x 16 branches) or 2 (wide)"); return MPF_E_INVALID; } place_tile_ = (int)v; return MPF_OK; }
   if (key == "tbr_book_rows") { if (v < 0) { set_error("tbr_book_rows: the most entries of a booking batch of a tracked TBR sweep, 0 = 256 MiB worth"); return MPF_E_INVALID; } tbr_book_rows_ = v; return MPF_OK; }
   if (key == "tbr_weighted") { tbr_weighted_ = v ? 1 : 0; return MPF_OK; }       // TBR under -cost (host/tbr.cpp); no effect on a Fitch engine
+  if (key == "tbr_weighted_tracked") { tbr_weighted_tracked_ = v ? 1 : 0; return MPF_OK; }   // ... under -bb; no effect on a Fitch engine
   if (key == "place_weighted") { place_weighted_ = v ? 1 : 0; return MPF_OK; }   // taxon insertion under -cost (host/place.cpp); no effect on a Fitch engine
   if (key == "poly_tile") { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32) { set_error("poly_tile: 0 (from the row length), 4, 8, 16 or 32 words per workgroup"); return MPF_E_INVALID; } poly_tile_ = (int)v; return MPF_OK; }
   if (key == "split_key_bits") { if (v < 1 || v > 64) { set_error("split_key_bits: 1 .. 64"); return MPF_E_INVALID; } split_key_bits_ = (int)v; return MPF_OK; }
@@ -2044,6 +2045,7 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "place_tile") *v = place_tile_;
   else if (key == "place_weighted") *v = place_weighted_;
   else if (key == "tbr_weighted") *v = tbr_weighted_;
+  else if (key == "tbr_weighted_tracked") *v = tbr_weighted_tracked_;
   else if (key == "tbr_book_rows") *v = tbr_book_rows_;
   else if (key == "tbr_booked") *v = ufb_ ? (int64_t)ufb_->tbr_booked : 0;
   else if (key == "tbr_book_batches") *v = ufb_ ? (int64_t)ufb_->tbr_book_batches : 0;

@@ -414,6 +414,9 @@ class Engine {
   // DIAGNOSTIC (no tracker needed, Fitch engine): the mask rows k_tbr_masks writes for one visit, read back per original pattern:
   // terms[(i * (1 + |g|) + j) * P + p] = the bit of M[i][j] at the first site of pattern p, 0 for a pattern the engine drops
   int tbr_pattern_terms(int rec, int maxtrav, std::vector<int32_t> &f, std::vector<int32_t> &g, std::vector<uint8_t> *terms);
+  // the weighted counterpart (k_tbr_snk_vals; options "tbr_weighted" and "tbr_weighted_tracked"; a Fitch engine is refused):
+  // rows[(i * (1 + |g|) + j) * P + p] = min_x(RF_i[x] + m(RG_j)[x]) of pattern p, the per-pattern length of the tree of entry [i][j]
+  int tbr_pattern_lengths(int rec, int maxtrav, std::vector<int32_t> &f, std::vector<int32_t> &g, std::vector<uint16_t> *rows);
 
   // ---- the summary of a -bb run (host/splits.cpp, splits.hip; reference IQTree::summarizeBootstrap, MTreeSet::convertSplits,
   // computeConsensusTree): the splits of a weighted set of complete trees counted exactly on the device, the supports of a target
@@ -767,6 +770,11 @@ class Engine {
   using TbrChunkFn = std::function<int(size_t, size_t, const uint32_t *)>;
   struct TbrReplay;
   int tbr_book_chunk(const tbrplan::Visit *vis, size_t nv, const uint32_t *cost, uint32_t cur_len);
+  // option "tbr_weighted_tracked" (with "tbr_weighted"): mpf_ufboot_tbr_sweep, mpf_ufboot_optimize_tbr and mpf_tbr_pattern_lengths are
+  // served on the weighted engine (k_tbr_snk_vals, tbr_book_chunk_snk); 0: refused as before.  No effect on a Fitch engine
+  int tbr_weighted_tracked_ = 0;
+  int tbr_snk_vals_check(const std::string &what);                    // every per-pattern length fits its 16-bit row
+  int tbr_book_chunk_snk(const tbrplan::Visit *vis, size_t nv, const uint32_t *cost, uint32_t cur_len);
   int tbr_run(const int32_t *recs, size_t count, int maxtrav, std::vector<tbrplan::Visit> &vis, std::vector<uint32_t> *matrix,
               std::vector<TbrBest> *best, uint64_t *n_pairs, const TbrChunkFn *chunk_fn = nullptr);
 

@@ -21,6 +21,8 @@
 //                    so the S x S transform is paid once per root set and not once per pair
 //   k_tbr_costs      over PlaceMinPlus: cost[i][j] = sum_ptn w * min_x(RF_i[x] + m(RG_j)[x]), the FULL length, no additive base;
 //                    row 0 reads vec[slot_q] as it is, column 0 the stored transform of slot_p
+//   k_tbr_snk_vals   under a UFBoot tracker (option "tbr_weighted_tracked"): the per-pattern terms min_x(RF_i[x] + m(RG_j)[x]) themselves,
+//                    one 16-bit row per listed entry
 #include "tbr.hpp"
 #include "pair_algebra.hpp"
 #include "wave_min.hpp"
@@ -329,7 +331,86 @@ __global__ __launch_bounds__(64) void k_tbr_masks(const uint32_t *__restrict__ v
   }
 }
 
+// The rows a UFBoot tracker needs of a visit's matrix on the weighted engine (host/tbr.cpp): vals[out][p] = min_x(RF_i[x] +
+// m(RG_j)[x]) of pattern p, the very terms whose weighted sum k_tbr_costs<PlaceMinPlus> returns as cost[i][j] -- the _pattern_pars
+// row of the joined tree.  The shape is k_tbr_masks's, the algebra k_snk_branch_eval's: one wave per (run, tile of 64 elements of a
+// row of We elements), a run one row i of one visit with a list of its columns.  The lane keeps its element of RF_i's S state rows
+// in registers (row 0: vec at slot_q), walks the run's columns (wave-uniform records), loads its element of m(RG_j)'s S rows -- the
+// chunk's G sets are stored transformed, column 0 is the STORED transform of vec at slot_p: nothing is transformed here -- and stores
+// the minimum into vals[out][npat] in the layout k_snk_nni_eval_vals writes and k_vals_planes reads: a us2 per lane in the 16-bit
+// store (patterns 2 e, 2 e + 1), one uint16_t in the 32-bit store.  One writer per element, no LDS, one atomicMax per wave into vmax.
+// Lanes at and beyond We are clamped onto the last element (lane_word's rule): they load real data, store nothing and add nothing to
+// the maximum; padding patterns inside a row are stored as they come, as k_snk_nni_eval_vals stores them (their sample weights are 0).
+// 16 bits: RF_i and RG_j are sums of transforms over disjoint parts holding the n tips between them, a tip's vector is 0 or
+// highest_cost and m(v)[z] <= v[z], so RF_i[x] + m(RG_j)[x] <= n highest_cost (k_tbr_snk_roots above, DESIGN 5q "16-bit store").  The
+// 16-bit store exists under 3 n highest_cost < 65536 only (Engine::pack).  The 32-bit store has no such guard of its own -- the
+// rows k_snk_scan writes there rest on the lengths of real data being small -- so the launcher serves it only where the same bound,
+// n highest_cost < 65536, holds, and refuses it otherwise: no value is ever truncated.
+template <int S, bool PK>
+__global__ __launch_bounds__(64) void k_tbr_snk_vals(const uint32_t *__restrict__ vec, const uint32_t *__restrict__ mvec,
+                                                     const uint32_t *__restrict__ store, const TbrVisit *__restrict__ visits,
+                                                     const tbrplan::MaskRun *__restrict__ runs, const tbrplan::MaskCol *__restrict__ cols,
+                                                     int tiles, int We, uint16_t *__restrict__ vals, uint32_t npat, uint32_t *__restrict__ vmax)
+{
+  typedef SnkT<PK> T;
+  typedef typename T::E E;
+  const size_t run = (size_t)blockIdx.x / (size_t)tiles, tile = (size_t)blockIdx.x % (size_t)tiles;
+  const int lane = (int)threadIdx.x;
+  const bool valid = tile * 64 + (size_t)lane < (size_t)We;
+  const int e0 = valid ? (int)(tile * 64) + lane : We - 1;
+  const tbrplan::MaskRun r = runs[run];
+  const TbrVisit vd = visits[r.visit];
+  Costs<S, PK> rf;
+  if (r.row == 0) load_costs<S, PK>(rf, vec, vd.slot_q, We, e0);
+  else load_costs<S, PK>(rf, store, vd.f0 + (r.row - 1), We, e0);
+  uint32_t m = 0;
+  for (uint32_t c = r.begin; c < r.end; c++) {
+    const tbrplan::MaskCol cj = cols[c];
+    Costs<S, PK> mg;
+    if (cj.col == 0) load_costs<S, PK>(mg, mvec, vd.slot_p, We, e0);
+    else load_costs<S, PK>(mg, store, vd.g0 + (cj.col - 1), We, e0);
+    E best = T::inf();
+#pragma unroll
+    for (int x = 0; x < S; x++) best = T::mn(best, T::add(rf.v[x], mg.v[x]));
+    if (valid) {
+      uint16_t *row = vals + (size_t)cj.out * npat;
+      if constexpr (PK) {
+        *reinterpret_cast<us2 *>(row + 2 * e0) = best;
+        m = max(m, max((uint32_t)best.x, (uint32_t)best.y));
+      } else {
+        row[e0] = (uint16_t)best;
+        m = max(m, (uint32_t)best);
+      }
+    }
+  }
+#pragma unroll
+  for (int sh = 32; sh >= 1; sh >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, sh, 64));
+  if (lane == 0 && m) atomicMax(vmax, m);
+}
+
 }  // namespace
+
+bool tbr_snk_vals_fit(const Geometry &g, int n_taxa)
+{
+  return g.sankoff && (uint64_t)n_taxa * (uint64_t)g.highest_cost < 65536ull;
+}
+
+hipError_t launch_tbr_snk_vals(hipStream_t st, const Geometry &g, int n_taxa, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
+                               const tbrplan::MaskRun *runs, size_t n_runs, const tbrplan::MaskCol *cols, uint16_t *vals, uint32_t *vmax)
+{
+  if (!vec) return hipErrorInvalidValue;
+  if (!g.sankoff || !g.moff || g.costT || g.Wp <= 0 || g.Wp % 32) return hipErrorInvalidValue;      // (a vals row is a min-plus join)
+  if (!tbr_snk_vals_fit(g, n_taxa) || !vals || !vmax) return hipErrorInvalidValue;
+  if (!n_runs) return hipSuccess;
+  const int We = tbr_row_words(g);
+  const size_t tiles = ((size_t)We + 63) / 64;
+  if (n_runs * tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  dispatch_snk(g, [&](auto S, auto PK) {
+    hipLaunchKernelGGL((k_tbr_snk_vals<S, PK>), dim3((unsigned)(n_runs * tiles)), dim3(64), 0, st, vec, vec + g.moff, store, visits, runs, cols,
+                       (int)tiles, We, vals, (uint32_t)g.Wp, vmax);
+  });
+  return hipGetLastError();
+}
 
 hipError_t launch_tbr_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
                             const tbrplan::MaskRun *runs, size_t n_runs, const tbrplan::MaskCol *cols, uint32_t *masks)

@@ -47,5 +47,14 @@ hipError_t launch_tbr_best(hipStream_t st, const TbrVisit *visits, size_t n_visi
 // rows in the form of launch_join_masks, ready for the REPS product.  Every `out` must lie inside masks; one entry, one writer
 hipError_t launch_tbr_masks(hipStream_t st, const Geometry &g, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
                             const tbrplan::MaskRun *runs, size_t n_runs, const tbrplan::MaskCol *cols, uint32_t *masks);
+// ... on the weighted engine (k_tbr_snk_vals; a Fitch geometry is refused as launch_tbr_masks refuses a weighted one).  A joined tree's
+// _pattern_pars row is, per pattern, min_x(R_q(F_i)[x] + m(R_p(G_j))[x]): the terms whose weighted sum cost[i][j] is.
+// vals[col.out][0 .. g.Wp) = that row as 16-bit values for every listed column of every run, in the layout of launch_snk_nni_eval's
+// vals (launch_vals_planes reads it); *vmax takes the largest value written (atomic max: the caller zeroes it).  The same lists as
+// launch_tbr_masks.  tbr_snk_vals_fit: every value fits 16 bits, n_taxa x highest_cost < 65536 -- implied by the 16-bit store's own
+// condition, required of the 32-bit store (the launcher refuses a geometry that does not fit; nothing is truncated)
+bool tbr_snk_vals_fit(const Geometry &g, int n_taxa);
+hipError_t launch_tbr_snk_vals(hipStream_t st, const Geometry &g, int n_taxa, const uint32_t *vec, const uint32_t *store, const TbrVisit *visits,
+                               const tbrplan::MaskRun *runs, size_t n_runs, const tbrplan::MaskCol *cols, uint16_t *vals, uint32_t *vmax);
 
 }  // namespace mpf

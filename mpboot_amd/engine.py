@@ -39,7 +39,7 @@ EXPORTS = [
     "mpf_polytomy_parsimony", "mpf_polytomy_branch_substitutions", "mpf_polytomy_branch_lengths",
     "mpf_insertion_costs", "mpf_place_taxa", "mpf_iq_parsimony_tree",
     "mpf_tbr_scan", "mpf_tbr_sweep_best", "mpf_apply_tbr", "mpf_optimize_tbr", "mpf_get_tbr_moves",
-    "mpf_ufboot_tbr_sweep", "mpf_ufboot_optimize_tbr", "mpf_tbr_pattern_terms",
+    "mpf_ufboot_tbr_sweep", "mpf_ufboot_optimize_tbr", "mpf_tbr_pattern_terms", "mpf_tbr_pattern_lengths",
     "mpf_split_counts", "mpf_split_support", "mpf_consensus_tree", "mpf_ufboot_summarize", "mpf_ufboot_summary_trees",
     "mpf_rf_distances",
     "mpf_split_counts_set", "mpf_split_support_set", "mpf_consensus_tree_set", "mpf_rf_distances_set",
@@ -214,6 +214,7 @@ def load_library():
         L.mpf_ufboot_tbr_sweep.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
         L.mpf_ufboot_optimize_tbr.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
         L.mpf_tbr_pattern_terms.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp]
+        L.mpf_tbr_pattern_lengths.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp]
         L.mpf_split_counts.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]
         L.mpf_split_support.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.mpf_consensus_tree.argtypes = [vp, C.c_int32, vp, vp, C.c_double, vp, vp, vp, vp, vp]
@@ -825,6 +826,7 @@ class FitchEngine:
     # ---- ... under -bb (a tracker attached): every entry of every visit's matrix goes to saveCurrentTree's rule -- the visits in
     # node_order(), a visit's entries in row-major order from [0][0] (the current tree under its own length), every other entry the
     # joined tree under cost[i][j].  Default rule, -mulhits, a cut-off, -cutoff_from_btrees; the rest is refused (-6)
+    # A weighted engine (cost=...) serves both after set_option("tbr_weighted", 1) and set_option("tbr_weighted_tracked", 1) only
     def ufboot_tbr_sweep(self, maxtrav: int = 6):
         """tbr_sweep_best with every entry booked through the tracker -> (cost, f, g, n_pairs); the tree does not change.
         get_option("tbr_booked") counts the trees handed over since the attach; set_option("tbr_book_rows", k) caps the entries of
@@ -855,6 +857,24 @@ class FitchEngine:
             cap = (1 + nf.value) * (1 + ng.value)
         t = np.zeros(max(cap, 1) * self.P, dtype=np.uint8)
         _chk(L.mpf_tbr_pattern_terms(self.h, rec, maxtrav, cap, _p(t), C.byref(nf), C.byref(ng)))
+        k = (1 + nf.value) * (1 + ng.value)
+        if k > cap:
+            return nf.value, ng.value
+        return nf.value, ng.value, t[:k * self.P].reshape(1 + nf.value, 1 + ng.value, self.P).copy()
+
+    def tbr_pattern_lengths(self, rec: int, maxtrav: int = 6, cap=None):
+        """DIAGNOSTIC, weighted engines after set_option("tbr_weighted", 1) and set_option("tbr_weighted_tracked", 1) (refused on a
+        Fitch engine): the rows of one visit as the weighted tracked sweep's kernel writes them -> (n_f, n_g,
+        rows[1 + n_f][1 + n_g][n_patterns] uint16): per pattern the length of the tree of entry [i][j], 0 for a pattern the engine
+        drops; a row's weighted sum is the entry's cost.  cap (tests): cap_entries handed to the C call; too small, only (n_f, n_g)
+        comes back."""
+        L = load_library()
+        nf, ng = C.c_int32(), C.c_int32()
+        if cap is None:
+            _chk(L.mpf_tbr_pattern_lengths(self.h, rec, maxtrav, 0, None, C.byref(nf), C.byref(ng)))
+            cap = (1 + nf.value) * (1 + ng.value)
+        t = np.zeros(max(cap, 1) * self.P, dtype=np.uint16)
+        _chk(L.mpf_tbr_pattern_lengths(self.h, rec, maxtrav, cap, _p(t), C.byref(nf), C.byref(ng)))
         k = (1 + nf.value) * (1 + ng.value)
         if k > cap:
             return nf.value, ng.value

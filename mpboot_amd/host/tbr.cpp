@@ -16,10 +16,12 @@
 // other the length depends on the evaluation edge, and TBR has no reference function that would fix one.
 //
 // Under -bb (a UFBoot tracker attached): ufboot_tbr_sweep / ufboot_optimize_tbr book every entry of every visit through the tracker
-// (tbr_book_chunk, k_tbr_masks; "under -bb" below).  Fitch engine; the default rule, -mulhits, a cut-off, -cutoff_from_btrees.
+// (tbr_book_chunk, k_tbr_masks; "under -bb" below); the default rule, -mulhits, a cut-off, -cutoff_from_btrees.  The weighted
+// engine serves them under the option "tbr_weighted_tracked" (with "tbr_weighted"; default 0: refused as before) through
+// tbr_book_chunk_snk and k_tbr_snk_vals ("... on the weighted engine" below).
 //
 // Not served: a cost matrix that is not symmetric, the plain entries with a UFBoot tracker attached (nothing would be booked), the
-// tracked ones on the weighted engine, under -storetrees, -mulhits -topboot, -distinct_iter_top_boot, on a sample-sharded tracker or
+// tracked ones on the weighted engine without its option, under -storetrees, -mulhits -topboot, -distinct_iter_top_boot, on a sample-sharded tracker or
 // in a ratchet state; random ties, a device-resident climb.
 #include <functional>
 #include <string>
@@ -40,6 +42,10 @@ struct TbrBuffers {
   DevBuf<uint32_t> masks;
   DevBuf<tbrplan::MaskRun> mruns;
   DevBuf<tbrplan::MaskCol> mcols;
+  // ... on the weighted engine (tbr_book_chunk_snk, tbr_pattern_lengths): the 16-bit rows of a batch and their largest value
+  DevBuf<uint16_t> vals;
+  DevBuf<uint32_t> vmax;
+  PinBuf<uint32_t> h_vmax;
   std::vector<tbrplan::Op> v_ops;
   std::vector<TbrSide> v_sides;
   std::vector<TbrVisit> v_visits;
@@ -389,6 +395,7 @@ struct Engine::TbrReplay {
 
 int Engine::tbr_book_chunk(const tbrplan::Visit *vis, size_t nv, const uint32_t *cost, uint32_t cur_len)
 {
+  if (sankoff_) return tbr_book_chunk_snk(vis, nv, cost, cur_len);
   UfbState &u = *ufb_;
   TbrBuffers &b = *tbr_buf_;
   const size_t Wp = (size_t)g_.Wp;
@@ -506,20 +513,177 @@ int Engine::tbr_book_chunk(const tbrplan::Visit *vis, size_t nv, const uint32_t 
   return MPF_OK;
 }
 
+// ---------------------------------------------------------------- ... on the weighted engine (-cost m -bb)
+//
+// The same entries in the same order under the same lengths: cost[i][j] is the full weighted length k_tbr_costs<PlaceMinPlus> returns.
+// _pattern_pars of the tree of entry [i][j] is, per pattern, min_x(RF_i[x] + m(RG_j)[x]) -- the terms whose weighted sum cost[i][j]
+// is --, which k_tbr_snk_vals writes as a 16-bit row per listed entry.  The chain is nni_book_step_snk's: K = bits of the largest
+// value, k_vals_planes, K runs of k_bitgemm per weight plane.  A tree's score under sample b is its OWN product row: the home row of
+// a run is its visit's [0][0] row, which under a symmetric matrix is the current tree's row at every cut edge, so that R_T - C[home]
+// + C[c] = C[c].  No ufb_current_tree_reps pass, no join mask.  R_T itself is the product of the current tree's own row
+// (launch_sankoff_pattern in tree_length's operand order), made once per sweep in front of the first batch: the current tree's
+// bookings are offered from it on the host even where no candidate of a batch passes the cut-off.  Batches, pass flags, index space,
+// extraction and replay are tbr_book_chunk's; the automatic batch cap is tbrplan::book_cap.
+int Engine::tbr_snk_vals_check(const std::string &what)
+{
+  if (tbr_snk_vals_fit(g_, n_)) return MPF_OK;
+  set_error(what + ": not served in the 32-bit store where a per-pattern length may exceed 16 bits (taxa x highest cost >= 65536)");
+  return MPF_E_UNSUPPORTED;
+}
+
+int Engine::tbr_book_chunk_snk(const tbrplan::Visit *vis, size_t nv, const uint32_t *cost, uint32_t cur_len)
+{
+  UfbState &u = *ufb_;
+  TbrBuffers &b = *tbr_buf_;
+  const size_t npat = (size_t)g_.Wp;                 // (weighted: g_.Wp counts patterns)
+  std::vector<size_t> entries(nv), at(nv);
+  std::vector<uint32_t> ncols(nv);
+  size_t total = 0;
+  for (size_t k = 0; k < nv; k++) {
+    at[k] = total;
+    entries[k] = vis[k].rows() * vis[k].cols();
+    ncols[k] = (uint32_t)vis[k].cols();
+    total += entries[k];
+  }
+  u.tbr_booked += (uint64_t)total;
+  const UfbCutoff cut = ufb_cutoff(u.logl_cutoff);     // iqtree.cpp:3343: booked iff  -len > logl_cutoff - 1e-4
+  if (cut.none_pass) return MPF_OK;
+  UCHK(b.vmax.reserve(4));
+  UCHK(b.h_vmax.reserve(4));
+  if (!u.rt_valid) {
+    // R_T from the current tree's own row (as nni_eval fills row 2 nb); the pass is not counted among the products
+    const uint64_t counted = u.gemm_rows;
+    UCHK(b.vals.reserve(npat));
+    UCHK(hipMemsetAsync(b.vmax.p, 0, sizeof(uint32_t), st_));
+    UCHK(launch_sankoff_pattern(st_, g_, vec_rows(), slot(back_[start_]), slot(start_), b.vals.p, b.vmax.p));      // (left = far end, right = start: as tree_length)
+    UCHK(hipMemcpyAsync(b.h_vmax.p, b.vmax.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+    UCHK(hipStreamSynchronize(st_));
+    UfbPlanes P;
+    { int rc = ufb_vals_planes(b.vals.p, 1u, b.h_vmax.p[0], P); if (rc) return rc; }
+    { int rc = ufb_weighted_product(P, P.rows_p, nullptr, 0u); if (rc) return rc; }
+    u.gemm_rows = counted;
+    u.rt_valid = true;
+  }
+  UCHK(u.h_rt.reserve((size_t)u.Bp));
+  UCHK(hipMemcpyAsync(u.h_rt.p, u.rt.p, (size_t)(u.Bl + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+  UCHK(hipStreamSynchronize(st_));
+  u.rt_orig = (uint32_t)u.h_rt.p[u.Bl];
+  // a batch's 16-bit rows, its K bit planes and its product each within 256 MiB (tbrplan::book_cap; K bounded by the values' bound)
+  const size_t cap = tbr_book_rows_ > 0 ? (size_t)tbr_book_rows_
+                                        : tbrplan::book_cap(npat, (size_t)u.Wp_s, (size_t)u.Bp, tbrplan::value_bits((uint64_t)n_ * (uint64_t)g_.highest_cost),
+                                                            (size_t)kUfbRowTile);
+  std::vector<tbrplan::BookRun> runs;
+  std::vector<size_t> off;
+  tbrplan::book_batches(entries, cap, runs, off);
+  std::vector<tbrplan::MaskRun> mr;
+  std::vector<tbrplan::MaskCol> mc;
+  std::vector<uint32_t> crow_c, home_r, blen;
+  std::vector<uint8_t> pass;
+  std::vector<UfbEvent> events;
+  const bool self_pass = cut.passes(cur_len);
+  for (size_t bi = 0; bi + 1 < off.size(); bi++) {
+    const tbrplan::BookRun *br = runs.data() + off[bi];
+    const size_t n_runs = off[bi + 1] - off[bi];
+    u.tbr_book_batches++;
+    u.batches++;
+    const double t0 = now_ms();
+    // ---- the lengths the entries are booked under, which of them pass
+    blen.clear();
+    pass.clear();
+    uint32_t n_take = 0;
+    for (size_t r = 0; r < n_runs; r++)
+      for (uint64_t en = br[r].begin; en < br[r].end; en++) {
+        const bool self = en == 0;
+        blen.push_back(self ? cur_len : cost[at[br[r].visit] + (size_t)en]);
+        pass.push_back(self ? 0 : (uint8_t)cut.passes(blen.back()));      // (the current tree is offered from R_T on the host)
+        n_take += pass.back();
+      }
+    const uint32_t n_c = (uint32_t)blen.size(), n_idx = 1u + n_c + (uint32_t)n_runs;
+    events.clear();
+    if (n_take) {
+      // ---- 16-bit rows, bit planes, product, extraction
+      const uint32_t rows = tbrplan::mask_rows(br, n_runs, ncols.data(), pass.data(), mr, mc, crow_c, home_r);
+      const int rows_p = round_up((int)rows, kUfbRowTile);
+      std::vector<uint32_t> home(n_runs), part((size_t)n_idx, 0xFFFFFFFFu), crow((size_t)n_idx, 0xFFFFFFFFu);
+      uint32_t c = 0, rt_row = tbrplan::kNoRow;
+      for (size_t r = 0; r < n_runs; r++) {
+        home[r] = 1u + n_c + (uint32_t)r;
+        crow[home[r]] = home_r[r];
+        if (rt_row == tbrplan::kNoRow) rt_row = home_r[r];      // (any home row: every one of them is the current tree's)
+        for (uint64_t en = br[r].begin; en < br[r].end; en++, c++) { part[1 + c] = (uint32_t)r; crow[1 + c] = crow_c[c]; }
+      }
+      bool timed = false;
+      auto product = [&](int rp, const uint32_t *) -> int {
+        UCHK(b.vals.reserve((size_t)rows * npat));
+        UCHK(b.mruns.reserve(mr.size()));
+        UCHK(b.mcols.reserve(mc.size()));
+        UCHK(hipMemcpyAsync(b.mruns.p, mr.data(), mr.size() * sizeof(tbrplan::MaskRun), hipMemcpyHostToDevice, st_));
+        UCHK(hipMemcpyAsync(b.mcols.p, mc.data(), mc.size() * sizeof(tbrplan::MaskCol), hipMemcpyHostToDevice, st_));
+        UCHK(hipMemsetAsync(b.vmax.p, 0, sizeof(uint32_t), st_));
+        if (timing_) UCHK(hipEventRecord(ev0_, st_));
+        UCHK(launch_tbr_snk_vals(st_, g_, n_, vec_rows(), b.store.p, b.visits.p, b.mruns.p, mr.size(), b.mcols.p, b.vals.p, b.vmax.p));
+        UCHK(hipMemcpyAsync(b.h_vmax.p, b.vmax.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        UCHK(hipStreamSynchronize(st_));               // K follows from the largest value written
+        UfbPlanes P;
+        { int rc = ufb_vals_planes(b.vals.p, rows, b.h_vmax.p[0], P); if (rc) return rc; }      // (the padding rows of every plane are zero)
+        if (timing_) UCHK(hipEventRecord(ev1_, st_));
+        timed = timing_;
+        return ufb_weighted_product(P, rp, nullptr, rt_row);       // (R_T again from a home row: the values it had; ev2_ .. ev3_)
+      };
+      int rc = nni_extract_events(n_idx, home, part, crow, pass, nullptr, rows_p, false, product, events);      // (waits: mr, mc outlive their copies)
+      if (rc) return rc;
+      if (timed) {
+        float m0 = 0.f, m1 = 0.f;
+        if (hipEventElapsedTime(&m0, ev0_, ev1_) == hipSuccess && hipEventElapsedTime(&m1, ev2_, ev3_) == hipSuccess) {
+          tbr_masks_ns_ += (uint64_t)((double)m0 * 1e6);      // (here: the vals kernel and the plane slicing)
+          tbr_product_ns_ += (uint64_t)((double)m1 * 1e6);
+          u.gemm_ms += m1;
+          tbr_extract_ns_ += (uint64_t)(std::max(0.0, now_ms() - t0 - (double)m0 - (double)m1) * 1e6);
+        }
+      }
+    }
+    const double t1 = now_ms();
+    u.t_dev += t1 - t0;
+    // ---- host replay, in booking order
+    TbrReplay replay(*this, vis, br, n_runs);
+    size_t ep = 0;
+    uint32_t c = 0;
+    for (size_t r = 0; r < n_runs; r++)
+      for (uint64_t en = br[r].begin; en < br[r].end; en++, c++) {
+        if (en == 0) {
+          replay.book(cur_len, self_pass, 0xFFFFFFFFu, [&](auto offer) {
+            for (int c2 = 0; c2 < u.Bl; c2++) offer((uint32_t)u.ids[(size_t)c2], (uint32_t)u.h_rt.p[c2]);
+          });
+          continue;
+        }
+        const uint32_t idx = 1u + c;
+        replay.book(blen[c], pass[c] != 0, c, [&](auto offer) {
+          while (ep < events.size() && events[ep].idx < idx) ep++;
+          for (; ep < events.size() && events[ep].idx == idx; ep++) offer(events[ep].b, events[ep].s);
+        });
+      }
+    replay.flush();
+    u.t_replay += now_ms() - t1;
+  }
+  return MPF_OK;
+}
+
 // what the two tracked entries ask of the engine and of the tracker
 int Engine::tbr_tracked_check(const char *what, int maxtrav)
 {
   const std::string w(what);
   if (!ufb_) { set_error("no UFBoot tracker attached"); return MPF_E_STATE; }
   if (!have_tree_) { set_error("no tree set"); return MPF_E_STATE; }
-  if (sankoff_) { set_error(w + ": the tracked TBR sweep is not served on the weighted (-cost) engine (its mask rows are Fitch joins)"); return MPF_E_UNSUPPORTED; }
+  if (sankoff_ && !(tbr_weighted_ && tbr_weighted_tracked_)) { set_error(w + ": the tracked TBR sweep is not served on the weighted (-cost) engine (its mask rows are Fitch joins)"); return MPF_E_UNSUPPORTED; }
   const UfbState &u = *ufb_;
   if (u.exchange || u.Bl != u.B) { set_error(w + ": not served with a sample-sharded tracker"); return MPF_E_UNSUPPORTED; }
   if (u.store_trees) { set_error(w + ": -storetrees is not served"); return MPF_E_UNSUPPORTED; }
   if (u.topboot) { set_error(w + ": -mulhits -topboot is not served"); return MPF_E_UNSUPPORTED; }
   if (u.distinct) { set_error(w + ": -distinct_iter_top_boot is not served"); return MPF_E_UNSUPPORTED; }
   if (u.ratchet) { set_error(w + ": not served on re-weighted (ratchet) patterns with ratchet booking on"); return MPF_E_UNSUPPORTED; }
-  return tbr_check(what, maxtrav, true);
+  int rc = tbr_check(what, maxtrav, true);            // (a cost matrix that is not symmetric is refused here)
+  if (rc) return rc;
+  return sankoff_ ? tbr_snk_vals_check(w) : MPF_OK;
 }
 
 int Engine::ufboot_tbr_sweep(int maxtrav, uint32_t *best_cost, int32_t *best_f, int32_t *best_g, uint64_t *n_pairs)
@@ -608,6 +772,66 @@ int Engine::tbr_pattern_terms(int rec, int maxtrav, std::vector<int32_t> &f, std
         if (site < 0 || (size_t)site >= 32 * Wp) continue;      // (weight 0 behind the last site of a full row: k_pattern_sum)
         (*terms)[r * (size_t)P_ + (size_t)p] = (uint8_t)((h[r * Wp + (size_t)(site >> 5)] >> (site & 31)) & 1u);
       }
+    return MPF_OK;
+  };
+  const int32_t r = rec;
+  rc = tbr_run(&r, 1, maxtrav, vis, nullptr, nullptr, nullptr, &rows_back);
+  if (rc) return rc;
+  f = vis[0].F.rec;
+  g = vis[0].G.rec;
+  return MPF_OK;
+}
+
+// DIAGNOSTIC, the weighted counterpart: every entry's row of per-pattern lengths of one visit, as k_tbr_snk_vals writes it, read back
+// per original pattern
+int Engine::tbr_pattern_lengths(int rec, int maxtrav, std::vector<int32_t> &f, std::vector<int32_t> &g, std::vector<uint16_t> *rows_out)
+{
+  if (!sankoff_) { set_error("mpf_tbr_pattern_lengths: weighted engines only (a Fitch engine has mpf_tbr_pattern_terms)"); return MPF_E_UNSUPPORTED; }
+  if (!tbr_weighted_ || !tbr_weighted_tracked_) {
+    set_error("mpf_tbr_pattern_lengths: the tracked TBR sweep is not served on the weighted (-cost) engine (its mask rows are Fitch joins)");
+    return MPF_E_UNSUPPORTED;
+  }
+  int rc = tbr_check("mpf_tbr_pattern_lengths", maxtrav, true);
+  if (rc) return rc;
+  rc = tbr_snk_vals_check("mpf_tbr_pattern_lengths");
+  if (rc) return rc;
+  if (rec < 3 || rec >= 3 * (2 * n_ - 1) || back_[rec] < 0) { set_error("mpf_tbr_pattern_lengths: bad record"); return MPF_E_INVALID; }
+  std::vector<tbrplan::Visit> vis(1);
+  if (!rows_out) {
+    tbrplan::visit(n_, back_.data(), rec, maxtrav, vis[0]);
+    f = vis[0].F.rec;
+    g = vis[0].G.rec;
+    return MPF_OK;
+  }
+  const size_t npat = (size_t)g_.Wp;
+  const TbrChunkFn rows_back = [&](size_t, size_t, const uint32_t *) -> int {
+    TbrBuffers &b = *tbr_buf_;
+    const size_t nf = vis[0].rows(), ng = vis[0].cols(), rows = nf * ng;
+    std::vector<tbrplan::MaskRun> mr;
+    std::vector<tbrplan::MaskCol> mc;
+    for (size_t i = 0; i < nf; i++)
+      for (size_t j = 0; j < ng; j++) {
+        if (j % tbrplan::kMaskRunCols == 0) mr.push_back(tbrplan::MaskRun{0u, (uint32_t)i, (uint32_t)mc.size(), (uint32_t)mc.size()});
+        mc.push_back(tbrplan::MaskCol{(uint32_t)j, (uint32_t)(i * ng + j)});
+        mr.back().end = (uint32_t)mc.size();
+      }
+    HIPCHK(b.vals.reserve(rows * npat));
+    HIPCHK(b.vmax.reserve(4));
+    HIPCHK(b.mruns.reserve(mr.size()));
+    HIPCHK(b.mcols.reserve(mc.size()));
+    HIPCHK(hipMemcpyAsync(b.mruns.p, mr.data(), mr.size() * sizeof(tbrplan::MaskRun), hipMemcpyHostToDevice, st_));
+    HIPCHK(hipMemcpyAsync(b.mcols.p, mc.data(), mc.size() * sizeof(tbrplan::MaskCol), hipMemcpyHostToDevice, st_));
+    HIPCHK(hipMemsetAsync(b.vmax.p, 0, sizeof(uint32_t), st_));
+    HIPCHK(launch_tbr_snk_vals(st_, g_, n_, vec_rows(), b.store.p, b.visits.p, b.mruns.p, mr.size(), b.mcols.p, b.vals.p, b.vmax.p));
+    std::vector<uint16_t> h(rows * npat);
+    HIPCHK(hipMemcpyAsync(h.data(), b.vals.p, h.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st_));
+    HIPCHK(hipStreamSynchronize(st_));
+    rows_out->assign(rows * (size_t)P_, 0);
+    for (int p = 0; p < P_; p++) {
+      const int j = first_site_[(size_t)p];          // (weighted engine: the pattern's place among the kept ones)
+      if (j < 0 || (size_t)j >= npat) continue;
+      for (size_t r = 0; r < rows; r++) (*rows_out)[r * (size_t)P_ + (size_t)p] = h[r * npat + (size_t)j];
+    }
     return MPF_OK;
   };
   const int32_t r = rec;

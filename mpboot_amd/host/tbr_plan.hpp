@@ -166,6 +166,25 @@ inline void book_batches(const std::vector<size_t> &entries, size_t cap, std::ve
   if (!runs.empty()) off.push_back(runs.size());
 }
 
+// The automatic batch cap of a tracked sweep on the weighted engine (k_tbr_snk_vals, csrc/tbr.hip): the most entries of a batch such
+// that its 16-bit rows (npat values each), its K bit planes (plane_words words a row) and its product C (samples_p sums a row) each
+// stay within `limit` bytes.  mask_rows gives a batch of c entries at most 2 c rows (every run that has a home row has an entry that
+// takes part), and the planes and C are padded to whole row tiles: the cap is half the largest multiple of row_tile rows that fits.
+// K is not known before the kernel has run; value_bits bounds it on the host: every value is at most `top` (n_taxa x highest_cost,
+// k_tbr_snk_vals's comment), K is the number of bits of the largest value written and never more than 16
+inline int value_bits(uint64_t top)
+{
+  int k = 1;
+  while (k < 16 && (top >> k)) k++;
+  return k;
+}
+inline size_t book_cap(size_t npat, size_t plane_words, size_t samples_p, int k_bits, size_t row_tile, size_t limit = (size_t)256 << 20)
+{
+  const size_t per_row = std::max(std::max(npat * sizeof(uint16_t), (size_t)k_bits * plane_words * sizeof(uint32_t)), samples_p * sizeof(uint32_t));
+  const size_t rows = (limit / std::max<size_t>(per_row, 1)) / row_tile * row_tile;
+  return std::max<size_t>(1, rows / 2);
+}
+
 // The mask rows one batch needs (k_tbr_masks, csrc/tbr.hip): one per entry that takes part, and per run with such an entry the
 // visit's home row M[0][0] in front of them -- also where the run begins behind [0][0].  Entry [0][0] itself never takes a row of its
 // own (it is the current tree).  A MaskRun is one matrix row of one visit with at most kMaskRunCols listed columns: one wave's work.
