@@ -92,7 +92,7 @@ typedef struct mpf_stats {
   uint64_t climb_nodes;          /* prune nodes they visited                                  */
   uint64_t climb_moves;          /* moves they accepted                                       */
   double   climb_ms_total;       /* wall time of those launches incl. hand-over               */
-} mpf_stats;
+} mpf_stats;   /* (its size is part of ABI 8: callers hold one on their stack; later counters are read-only options, mpf_get_option) */
 
 const char *mpf_last_error(void);
 int mpf_abi_version(void);

@@ -976,7 +976,7 @@ int mpf_ufboot_get_counters(const mpf_engine *e, uint64_t *tie_draws, uint64_t *
 }
 
 int mpf_get_stats(const mpf_engine *e, mpf_stats *out) { NEED(e); *out = e->eng.stats; return MPF_OK; }
-int mpf_reset_stats(mpf_engine *e) { NEED(e); e->eng.stats = mpf_stats{}; return MPF_OK; }
+int mpf_reset_stats(mpf_engine *e) { NEED(e); e->eng.reset_stats(); return MPF_OK; }
 
 int mpf_set_option(mpf_engine *e, const char *key, int64_t value)
 {

@@ -378,14 +378,21 @@ void Engine::reset_node_order()
   for (int i = 1; i <= 2 * n_ - 1; i++) nodep_[i] = 3 * i;
 }
 
+// option host_front_ns_total: from the entry of mpf_set_tree to the return of the first kernel launch behind it (timing only)
+void Engine::mark_front()
+{
+  if (front_t0_ > 0) { host_front_ms_total_ += now_ms() - front_t0_; front_t0_ = 0; }
+}
+
 int Engine::set_tree(const int32_t *back)
 {
+  front_t0_ = timing_ ? now_ms() : 0.0;
   const size_t len = 3 * (size_t)(2 * n_ - 1);
-  for (int v = 1; v <= 2 * n_ - 2; v++)
-    for (int s = 0; s < (v <= n_ ? 1 : 3); s++) {
-      const int r = 3 * v + s, b = back[r];
-      if (b < 3 || b >= (int)len || back[b] != r) { set_error("mpf_set_tree: inconsistent back links"); return MPF_E_INVALID; }
-    }
+  if (!links::check_and_layout<uint2>(n_, back, nullptr)) {      // (the check alone: the layout is made for the refresh that needs it)
+    set_error(links::bad_links_message());
+    front_t0_ = 0;
+    return MPF_E_INVALID;
+  }
   const bool same = have_tree_ && ntips_ == n_ && std::equal(back + 3, back + len, back_.begin() + 3);
   std::copy(back, back + len, back_.begin());
   start_ = nodep_[1];
@@ -584,23 +591,18 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
   self_active_ = s.self;
   const size_t n_prune = sweep_maxtrav > 0 ? 2 * (size_t)n_ - 2 : 0;
   if (kids_host_.size() != nslots_) kids_host_.assign(nslots_, make_uint2(0u, 0u));
-  for (int v = n_ + 1; v <= 2 * n_ - 2; v++) {
-    const int r0 = 3 * v;
-    const uint32_t s0 = slot(back_[r0]), s1 = slot(back_[r0 + 1]), s2 = slot(back_[r0 + 2]);
-    uint2 *k = &kids_host_[slot(r0)];            // the three records of a node sit side by side, in `next` order
-    k[0] = make_uint2(s1, s2);
-    k[1] = make_uint2(s2, s0);
-    k[2] = make_uint2(s0, s1);
-  }
-  kids_list_.clear();
   const size_t no_ride[2] = {0, 0};               // (the first two regions of the layout go up in one copy)
   const RefreshStage sg = refresh_stage(nslots_, s.nops, (size_t)n_ + 2, n_prune, 64, 0, no_ride);
   // the topology array and the prune records stay in pinned host memory of their own (k_sched reads them over the bus: 40 KB,
   // no copy dispatch in front of the launch; nothing else writes this buffer, and a result of the launch is waited for before
-  // the next one is prepared)
+  // the next one is prepared).  The array is laid out straight into it (links::check_and_layout, the walk mpf_set_tree checks a
+  // tree with); the host's mirror takes its copy behind the launches.
   HIPCHK(h_kstage_.reserve(sg.ops_off));
+  std::memset(h_kstage_.p, 0, (size_t)n_ * sizeof(uint2));      // (tips have nothing behind them)
+  // (the tree the engine holds has passed the check, or was built by the engine: the layout alone)
+  (void)links::check_and_layout<uint2, false>(n_, back_.data(), reinterpret_cast<uint2 *>(h_kstage_.p));
+  kids_list_.clear();
   HIPCHK(d_vstage_.reserve(sg.total));
-  std::memcpy(h_kstage_.p, kids_host_.data(), sg.kids_bytes);
   uint8_t *src = d_vstage_.p;
   SweepDescArgs sw;
   if (n_prune) {
@@ -632,14 +634,21 @@ int Engine::schedule_views_dev(int sweep_maxtrav)
   kids_dirty_ = false;
   kids_upload_ = false;
   kids_dev_ready_ = true;
-  if (s.self)
+  if (n_prune) sweep_ends_active_ = 0;            // (launch_refresh says where the counts go ahead)
+  if (s.self) {
     // all that stands in front of the refresh: the topology array, pinned memory to device, one thread per record
     HIPCHK(launch_kids_copy(st_, reinterpret_cast<const uint2 *>(h_kstage_.p), reinterpret_cast<uint2 *>(src), (uint32_t)n_, (uint32_t)s.nops));
-  else
+    kids_uploads_++;
+    mark_front();
+  } else {
     HIPCHK(launch_sched(st_, reinterpret_cast<const uint2 *>(h_kstage_.p), (uint32_t)n_, (uint32_t)s.nops, reinterpret_cast<NvOp *>(src + sg.ops_off),
                         reinterpret_cast<int32_t *>(src + sg.lev_off), reinterpret_cast<int32_t *>(src + sg.nlev_off), sw, reinterpret_cast<uint2 *>(src)));
+    mark_front();
+  }
   int rc = launch_refresh(src, sg, s);            // (view kernel time = the refresh proper; k_sched reports its own: option sched_ticks)
   if (rc) return rc;
+  // the host's mirror of the topology array (fill_visit_counts, the deltas of later refreshes): the inner records, as laid out
+  std::memcpy(kids_host_.data() + n_, h_kstage_.p + (size_t)n_ * sizeof(uint2), s.nops * sizeof(uint2));
   // what the host still needs is a dependency order for the subtree scores (finish_views): the views looking away from
   // start_, children first, then the ones looking towards it, parents first -- while the device works
   const std::vector<int> &all = plan_.all;         // (preorder, three records per node, the first one facing start_)
@@ -672,6 +681,16 @@ int Engine::launch_refresh(const uint8_t *src, const RefreshStage &sg, const Ref
   // small batch: counts land in the host mirror
   cnt_on_host_ = s.fold_inside && want_host_results_;
   if (cnt_on_host_) x.cnt_host = h_cnt();
+  // a device-planned DNA sweep on the self-scheduled refresh (sweep_ends bit 2): the fold -- the refresh kernel's last workgroup,
+  // or k_cntsum_slots -- writes every count to the host's mirror and raises a flag there behind them; the host makes the subtree
+  // scores and the parts' base lengths while the scan runs, not behind it
+  cnt_early_ = s.self && s.sw && (sweep_ends_ & 2) && host_poll_ && g_.S == 4;
+  if (cnt_early_) {
+    HIPCHK(h_cntflag_.reserve(16));
+    __atomic_store_n(h_cntflag_.p, 0u, __ATOMIC_RELAXED);
+    x.cnt_host = h_cnt();
+    x.cnt_flag = h_cntflag_.p;
+  }
   // what rode on this launch's upload, what it clears for the scan that follows: promises of earlier refreshes are void
   for (int i = 0; i < 2; i++) ride_[i].dev = sg.ride_off[i] ? src + sg.ride_off[i] : nullptr;
   const bool zero = s.ride && zero_req_ptr_;      // the outputs of the scan that follows, cleared by the refresh launch
@@ -737,13 +756,15 @@ int Engine::launch_refresh(const uint8_t *src, const RefreshStage &sg, const Ref
   if (s.self) {
     // (no ops array: the inner slots themselves; the walk plan and the cleared outputs of a sweep ride on this launch -- the
     //  descriptors they need were written by the refresh launch in front of it)
-    if (!s.fold_inside) HIPCHK(launch_cntsum_slots(st_, (uint32_t)n_, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), tiles_for_levels(g_), x));
+    if (!s.fold_inside)
+      HIPCHK(launch_cntsum_slots(st_, (uint32_t)n_, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(), tiles_for_levels(g_), x, d_done_.p + 40));
   } else if (!s.fold_inside)
     // (no host mirror here: hundreds of scattered 4-byte writes over PCIe cost more than the one copy-back they would save)
     HIPCHK(launch_cntsum(st_, g_, dops, (int)s.nops, d_cntp_.p, (uint32_t)nslots_, d_cnt(),
                          (views_mode_ >= 1 && !s.chains) ? tiles_for_levels(g_) : 0));   // rows of cntp the refresh kernel wrote
   if (timing_ >= 2) { HIPCHK(hipEventRecord(ev3_, st_)); view_events_pending_ = true; }
-  cnt_copy_pending_ = true;                 // copied back together with the scan results (or by update_views)
+  cnt_copy_pending_ = !cnt_early_;          // copied back together with the scan results (or by update_views) -- unless on their way already
+  if (cnt_early_) sweep_ends_active_ |= 2;
   return MPF_OK;
 }
 
@@ -876,10 +897,11 @@ int Engine::schedule_views(const std::vector<int> *roots)
 }
 
 // subtree scores in dependency order (reference: tr->parsimonyScore[p] = total + score[q] + score[r], :874);
-// call only after the stream has been synchronised
-void Engine::finish_views()
+// call only after the stream has been synchronised -- or, with events = false, once the counts are known to be in h_cnt() (the
+// count fold's flag): the refresh's event pair is then left for the call behind the synchronisation
+void Engine::finish_views(bool events)
 {
-  if (view_events_pending_) {
+  if (events && view_events_pending_) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, ev2_, ev3_) == hipSuccess) stats.view_kernel_ms_total += ms;
     view_events_pending_ = false;
@@ -1613,6 +1635,8 @@ int Engine::sweep_scan(int mintrav, int maxtrav, uint64_t *n_tests, uint32_t *mi
         (dev_sched_usable() || (dsw_valid_ && sched_cache_valid_ && !kids_dirty_ && !sankoff_)))
       return sweep_scan_dev(mt, n_tests, min_mp);
   }
+  sweep_ends_active_ = 0;                          // (planned on the host: neither end is the device-planned step's)
+  front_t0_ = 0;
   std::vector<ScanPlan> &plans = sweep_plans_;
   const uint32_t *out = nullptr;
   want_part_min_ = true;
@@ -1676,6 +1700,19 @@ int Engine::sweep_scan_dev(int mt, uint64_t *n_tests, uint32_t *min_mp)
   }
   const size_t nd = dsw_parts_, nout = dsw_out_;
   uint32_t best = UINT_MAX;
+  // base length of a prune node's candidates = the two subtrees either side of the cut (reference :2158-2160), per scan part;
+  // needs the subtree scores (finish_views) and the parts' prune nodes (h_dsw_, in place since its flag)
+  bool base_done = false;
+  double t_behind = 0;                             // timing: option host_behind_ns_total, from the minima's flag to the return
+  const auto fill_base = [this](size_t n_parts) {
+    const uint32_t *node = h_dsw_.p + 4;
+    base_.resize(n_parts);
+    for (size_t i = 0; i < n_parts; i++) {
+      const int p = nodep_[node[i] + 1], q = back_[p];
+      base_[i] = (tip(p) ? 0u : sc_[p]) + (tip(q) ? 0u : sc_[q]);
+    }
+  };
+  if (warm) sweep_ends_active_ = 0;                // (a replay: neither the topology nor the fold of k_cntsum_slots is involved)
   if (nd > 0) {
     HIPCHK(d_ncand_.reserve(nd));
     HIPCHK(reserve_results(nout));
@@ -1700,7 +1737,15 @@ int Engine::sweep_scan_dev(int mt, uint64_t *n_tests, uint32_t *min_mp)
     HIPCHK(launch_part_min(st_, d_out(), d_parts_.p, (int)nd, h_pmin_.p, d_cnt(), cnt_copy_pending_ ? h_cnt() : nullptr, (uint32_t)nslots_,
                            d_done_.p + 24));
     cnt_copy_pending_ = false;
+    if (!warm && cnt_early_) {
+      // the counts are final when the fold ends, a scan ahead of the minima: subtree scores and base lengths while the scan runs
+      if (!wait_host_flag(h_cntflag_.p)) HIPCHK(hipStreamSynchronize(st_));
+      finish_views(false);
+      fill_base(nd);
+      base_done = true;
+    }
     if (!wait_host_flag(h_pmin_.p + nd)) HIPCHK(hipStreamSynchronize(st_));
+    if (timing_) t_behind = now_ms();
     float ms = 0;
     if (timing_ && hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) { stats.last_scan_kernel_ms = ms; stats.scan_kernel_ms_total += ms; }
     if (plan_event_pending_) {
@@ -1716,18 +1761,15 @@ int Engine::sweep_scan_dev(int mt, uint64_t *n_tests, uint32_t *min_mp)
     HIPCHK(hipStreamSynchronize(st_));
   }
   finish_views();
-  // base length of a prune node's candidates = the two subtrees either side of the cut (reference :2158-2160)
-  const uint32_t *node = h_dsw_.p + 4;
-  for (size_t i = 0; i < nd; i++) {
-    const uint32_t m = h_pmin_.p[i];
-    if (m == UINT_MAX) continue;                   // (a part without candidates)
-    const int p = nodep_[node[i] + 1], q = back_[p];
-    best = std::min(best, (tip(p) ? 0u : sc_[p]) + (tip(q) ? 0u : sc_[q]) + m);
-  }
+  if (!base_done) fill_base(nd);
+  const uint32_t *pmin = h_pmin_.p, *base = base_.data();
+  for (size_t i = 0; i < nd; i++)
+    if (pmin[i] != UINT_MAX) best = std::min(best, base[i] + pmin[i]);      // (UINT_MAX: a part without candidates)
   stats.insertion_tests += nout;
   stats.algorithmic_bytes += (uint64_t)nout * 6u * (uint64_t)g_.S * (uint64_t)Wref_ * 4u;
   if (n_tests) *n_tests = nout;
   if (min_mp) *min_mp = best;
+  if (t_behind > 0) host_behind_ms_total_ += now_ms() - t_behind;
   return MPF_OK;
 }
 
@@ -1877,7 +1919,15 @@ int Engine::set_option(const std::string &key, int64_t v)
   if (key == "dev_plan") { dev_plan_ = v != 0; plan_ride_ = !(v & 2); dsw_valid_ = false; return MPF_OK; }   // (bit 1: the walk plan as a launch of its own)               // scan descriptors of mpf_sweep_scan laid out on the device   // refresh schedule of a new topology made on the device (k_sched)
   // a from-scratch refresh of a complete tree schedules itself (k_newview_self) where the device could make its schedule (A/B switch)
   if (key == "refresh_self_sched") { refresh_self_sched_ = v != 0; sched_cache_valid_ = false; dsw_valid_ = false; return MPF_OK; }
-  if (key == "refresh_wm") { refresh_wm_ = v != 0; return MPF_OK; }          // refreshes on the word-major copy alone where they can (A/B switch; no effect without that copy)
+  // the far end of a device-planned sweep step (A/B switch): 2 = the refresh's counts reach the host when their fold ends and the
+  // host works on them while the scan runs; 0 = they come with the minima.  (Bit 1 named the early upload of the topology array
+  // from mpf_set_tree, which was measured and not kept: HISTORY.md)
+  if (key == "sweep_ends") {
+    if (v != 0 && v != 2) { set_error("sweep_ends: 0 or 2 (bit 2: the refresh's counts ahead of the minima)"); return MPF_E_INVALID; }
+    sweep_ends_ = (int)v;
+    return MPF_OK;
+  }
+  if (key == "refresh_wm") { refresh_wm_ = v != 0; return MPF_OK; }         // refreshes on the word-major copy alone where they can (A/B switch; no effect without that copy)
   if (key == "scan_shadow") { scan_shadow_ = v != 0; return MPF_OK; }        // planned scan reads the word-major copy when it is current (A/B switch)
   if (key == "reduce") { g_.reduce = v ? 1 : 0; return MPF_OK; }
   if (key == "xcd_map") { g_.map = v ? 1 : 0; return MPF_OK; }
@@ -1996,6 +2046,11 @@ int Engine::get_option(const std::string &key, int64_t *v) const
   else if (key == "refresh_wm_active") *v = (refresh_wm_ && !sankoff_ && g_.S == 4 && g_.shoff != 0) ? 1 : 0;
   else if (key == "refresh_self_sched") *v = refresh_self_sched_ ? 1 : 0;
   else if (key == "refresh_self_sched_active") *v = self_active_ ? 1 : 0;      // the route of the last from-scratch refresh
+  else if (key == "sweep_ends") *v = sweep_ends_;
+  else if (key == "sweep_ends_active") *v = sweep_ends_active_;                // the halves the last mpf_sweep_scan used
+  else if (key == "host_front_ns_total") *v = (int64_t)(host_front_ms_total_ * 1e6);      // (booked with timing >= 1, cleared by mpf_reset_stats)
+  else if (key == "host_behind_ns_total") *v = (int64_t)(host_behind_ms_total_ * 1e6);
+  else if (key == "kids_uploads")*v = (int64_t)kids_uploads_;              // launches of the topology copy kernel so far
   else if (key == "rows_ok") *v = rows_ok_ ? 1 : 0;
   else if (key == "ensure_rows_launches") *v = (int64_t)ensure_rows_launches_;
   else if (key == "scan_batch") *v = scan_batch_;

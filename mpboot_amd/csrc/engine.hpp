@@ -29,6 +29,7 @@
 #include "../host/list_tree.hpp"
 #include "../host/split_sets.hpp"
 #include "../host/refresh_plan.hpp"
+#include "../host/tree_links.hpp"
 #include "../host/many_shape.hpp"
 #include "climb.hpp"
 #include "kernels.hpp"
@@ -312,7 +313,7 @@ class Engine {
   int launch_refresh(const uint8_t *src, const RefreshStage &sg, const RefreshShape &s);
   int commit_refresh(const RefreshStage &sg, const RefreshShape &s, bool full, int made, bool cacheable);
   int sweep_scan_dev(int maxtrav, uint64_t *n_tests, uint32_t *min_mp);
-  void finish_views();                         // after a stream sync: subtree scores of the refreshed vectors
+  void finish_views(bool events = true);       // after a stream sync (or the counts' flag: events = false): subtree scores of the refreshed vectors
   void collect_scan_roots(int p, int mintrav, int maxtrav, std::vector<int> &roots) const;
 
   // ---- SPR neighbourhoods
@@ -494,6 +495,11 @@ class Engine {
   int ufboot_counters(uint64_t *draws, uint64_t *events, uint64_t *gemm_rows, double *gemm_ms) const;
 
   mpf_stats stats{};
+  // the host's time at the two ends of a device-planned sweep step (timing >= 1; options host_front_ns_total / host_behind_ns_total:
+  // mpf_stats keeps the size callers were built with): entry of mpf_set_tree .. return of the first kernel launch of the
+  // mpf_sweep_scan behind it; the minima's flag seen .. return of that mpf_sweep_scan
+  double host_front_ms_total_ = 0, host_behind_ms_total_ = 0;
+  void reset_stats() { stats = mpf_stats{}; host_front_ms_total_ = host_behind_ms_total_ = 0; }
   int set_option(const std::string &key, int64_t v);
   int get_option(const std::string &key, int64_t *v) const;
   int scan_trace(uint64_t *out, uint64_t cap, uint64_t *n);
@@ -988,7 +994,15 @@ private:
   int sc_maxlev_ = 0;                           // < 0: the schedule was made on the device, its level count lives at sc_stage_.nlev_off
   bool dev_sched_ = true;                       // option dev_sched
   bool dev_plan_ = true;                        // option dev_plan: a whole sweep's scan descriptors laid out on the device too
-  PinBuf<uint8_t> h_kstage_;                    // topology array + prune records of a device-scheduled refresh (read by k_sched from host memory)
+  PinBuf<uint8_t> h_kstage_;                    // topology array + prune records of a device-scheduled refresh (read by k_sched / k_kids_copy / k_newview_self from host memory)
+  uint64_t kids_uploads_ = 0;                   // option kids_uploads (read only): launches of the topology copy kernel
+  int sweep_ends_ = 2;                          // option sweep_ends: 2 = the refresh's counts reach the host ahead of the minima, 0 = with them
+  int sweep_ends_active_ = 0;                   // option sweep_ends_active (read only): what the last sweep used
+  PinBuf<uint32_t> h_cntflag_;                 // raised by the count fold's last workgroup once every count is in h_cnt()
+  bool cnt_early_ = false;                      // the last refresh launch sends the counts ahead (launch_refresh -> sweep_scan_dev)
+  std::vector<uint32_t> base_;                  // sweep_scan_dev: base length of every scan part
+  double front_t0_ = 0;                         // timing: entry of the last mpf_set_tree (option host_front_ns_total), 0 = booked
+  void mark_front();
   PinBuf<uint32_t> h_dsw_;                      // {parts, candidates, -, flag}, then the prune-node index of every part (written by k_sched)
   bool dsw_valid_ = false;                      // the descriptors on the device are k_sched's, for ...
   uint64_t dsw_walk_gen_ = 0;                   // ... this walk_gen_, ...

@@ -1206,6 +1206,12 @@ __global__ __launch_bounds__(1024) void k_newview_self(uint32_t *__restrict__ ve
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     fold_counts_of([n](int i) { return n + (uint32_t)i; }, (int)n_ops, cntp, nslots, nt, cnt, (int)tid, 1024, x.cnt_host);
     if (tid == 0u) __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (x.cnt_host && x.cnt_flag) {
+      // every wave's counts are in host memory before the flag goes up (the host reads them while the scan behind this launch runs)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+      __syncthreads();
+      if (tid == 0u) __hip_atomic_store(x.cnt_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
   }
 }
 
@@ -1260,10 +1266,14 @@ hipError_t launch_newview_self(hipStream_t st, const Geometry &g, uint32_t *vec,
 // k_cntsum for a refresh of every inner vector (the slots first .. first + n_ops: there is no ops array).  The first plan_blocks
 // workgroups do what rode on k_newview_wgq's extra workgroups: the walk plan of the sweep that follows and the clearing of its
 // outputs -- both need the descriptors, which the refresh launch in front of this one wrote.
+// x.cnt_flag (pinned, with cnt_host; done: a zeroed device word, left zeroed): a fold workgroup's eight counts leave for the host
+// side by side from its first wave, which then takes a ticket; the last one raises *x.cnt_flag = 1 behind every count, as k_part_min
+// does for its minima -- no pass over the counts, no read beyond the fold's own, nobody waits.  The plan workgroups take no ticket.
 __global__ __launch_bounds__(256) void k_cntsum_slots(uint32_t first, int n_ops, const uint32_t *__restrict__ cntp, uint32_t nslots, int tiles,
                                                       uint32_t *__restrict__ cnt, uint32_t *__restrict__ cnt_host, uint32_t plan_blocks,
-                                                      RefreshExtra x)
+                                                      RefreshExtra x, uint32_t *__restrict__ done)
 {
+  __shared__ uint32_t s_sum[8];
   if (blockIdx.x < plan_blocks) {
     const uint32_t n_parts = x.wp_hdr[0], n_out = x.wp_hdr[1];
     const uint32_t nw = blockDim.x >> 6, wave = threadIdx.x >> 6;
@@ -1274,28 +1284,55 @@ __global__ __launch_bounds__(256) void k_cntsum_slots(uint32_t first, int n_ops,
     return;
   }
   const int l32 = threadIdx.x & 31;
-  const int i = (int)((blockIdx.x - plan_blocks) * (blockDim.x >> 5) + (threadIdx.x >> 5));      // 32 lanes per op
-  if (i >= n_ops) return;
+  uint32_t *const host_flag = x.cnt_flag;
+  const int grp = (int)(threadIdx.x >> 5);
+  const int i0 =(int)((blockIdx.x - plan_blocks) * (blockDim.x >> 5));
+  const int i = i0 + grp;                                                                         // 32 lanes per op
+  if (i >= n_ops && !host_flag) return;
   const uint32_t dst = first + (uint32_t)i;
   uint32_t s = 0;
-  for (int t = l32; t < tiles; t += 32) s += cntp[(size_t)t * nslots + dst];
+  if (i < n_ops) {
+    for (int t = l32; t < tiles; t += 32) s += cntp[(size_t)t * nslots + dst];
 #pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) s += (uint32_t)__shfl_xor((int)s, m, 32);
+    for (int m = 16; m >= 1; m >>= 1) s += (uint32_t)__shfl_xor((int)s, m, 32);
+  }
+  if (!host_flag) {
+    if (l32 == 0) {
+      cnt[dst] = s;
+      if (cnt_host) cnt_host[dst] = s;
+    }
+    return;
+  }
   if (l32 == 0) {
-    cnt[dst] = s;
-    if (cnt_host) cnt_host[dst] = s;
+    if (i < n_ops) cnt[dst] = s;
+    s_sum[grp] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x >= 64u) return;
+  // the first wave alone writes to the host: its words are in host memory before the workgroup's ticket counts
+  if (threadIdx.x < 8u && i0 + (int)threadIdx.x < n_ops) cnt_host[first + (uint32_t)i0 + threadIdx.x] = s_sum[threadIdx.x];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  if (threadIdx.x == 0) {
+    const uint32_t folds = gridDim.x - plan_blocks;
+    const uint32_t ticket = __hip_atomic_fetch_add(done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket == folds - 1u) {
+      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+      __hip_atomic_store(host_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
   }
 }
 
 hipError_t launch_cntsum_slots(hipStream_t st, uint32_t first, int n_ops, const uint32_t *cntp, uint32_t nslots, uint32_t *cnt, int tiles,
-                               const RefreshExtra &x)
+                               const RefreshExtra &x, uint32_t *done)
 {
+  if (x.cnt_flag && (!x.cnt_host || !done || n_ops <= 0)) return hipErrorInvalidValue;
   // (a device-planned sweep: one 4-wave workgroup per 16 possible walk-plan items, as many waves as rode on the refresh launch)
   const unsigned plan_blocks = x.wp_desc ? std::min(2048u, (2u * x.wp_max_parts + 15u) / 16u) : 0u;
   const unsigned fold_blocks = n_ops > 0 ? (unsigned)((n_ops + 7) / 8) : 0u;
   if (plan_blocks + fold_blocks == 0u) return hipSuccess;
   hipLaunchKernelGGL(k_cntsum_slots, dim3(plan_blocks + fold_blocks), dim3(256), 0, st, first, n_ops, cntp, nslots, tiles, cnt, x.cnt_host,
-                     plan_blocks, x);
+                     plan_blocks, x, done);
   return hipGetLastError();
 }
 

@@ -167,7 +167,10 @@ struct RefreshExtra { const uint32_t *kid_upd = nullptr; int n_kid_upd = 0; uint
                       // from that copy.  k_newview_wgq then writes no rows at all; k_newview_chain writes them while `rows` is set
                       // (the rows of every valid vector are current and shall stay so)
                       int wm_only = 0, rows = 0;
-                      int waves_hint = 0; /* launch_newview_levels: waves per workgroup (0 = sixteen); narrow levels need fewer */ };
+                      int waves_hint = 0; /* launch_newview_levels: waves per workgroup (0 = sixteen); narrow levels need fewer */
+                      // launch_newview_self's in-kernel fold and launch_cntsum_slots: a pinned word (zeroed by the caller) that is
+                      // set to 1 once every count is in cnt_host -- the host reads them while the launches behind still run
+                      uint32_t *cnt_flag = nullptr; };
 // Refresh schedule of a COMPLETE tree made on the device from the topology array alone (kids[cid], cids n .. n + n_ops - 1 are
 // the inner records): ops in level order, lev_off[0 .. n_lev] as launch_newview_levels reads them, *n_lev.  One workgroup;
 // trees of up to kSchedMaxSlots vectors.  Order inside a level is not defined (ops of a level are independent).
@@ -205,9 +208,10 @@ hipError_t launch_newview_self(hipStream_t st, const Geometry &g, uint32_t *vec,
 // dst[first .. first + count) = src[first .. first + count), one thread per record (src: pinned host memory)
 hipError_t launch_kids_copy(hipStream_t st, const uint2 *src, uint2 *dst, uint32_t first, uint32_t count);
 // launch_cntsum for the slots first .. first + n_ops; x.wp_desc != nullptr: further workgroups of the same launch plan the scan
-// that follows and clear its outputs (x.wp_*, as they rode on launch_newview_levels)
+// that follows and clear its outputs (x.wp_*, as they rode on launch_newview_levels).  x.cnt_flag needs x.cnt_host and `done`, a
+// zeroed device word that is left zeroed
 hipError_t launch_cntsum_slots(hipStream_t st, uint32_t first, int n_ops, const uint32_t *cntp, uint32_t nslots, uint32_t *cnt, int tiles,
-                               const RefreshExtra &x);
+                               const RefreshExtra &x, uint32_t *done = nullptr);
 // every level in ONE launch (one 16-wave workgroup per tile, workgroup barrier between levels)
 // Fitch mode also folds the per-tile counts into cnt[dst] (last workgroup; `done` = a zeroed device word, left zeroed);
 // weighted mode leaves that to launch_cntsum

@@ -1308,7 +1308,14 @@ class FitchEngine:
     def stats(self) -> dict:
         st = Stats()
         _chk(load_library().mpf_get_stats(self.h, C.byref(st)))
-        return st.as_dict()
+        d = st.as_dict()
+        # the host's time at the two ends of a device-planned sweep step (booked with option timing >= 1): read-only options in
+        # nanoseconds -- mpf_stats keeps its size, callers hold one on their stack
+        for key in ("host_front", "host_behind"):
+            v = C.c_int64(0)
+            if load_library().mpf_get_option(self.h, (key + "_ns_total").encode(), C.byref(v)) == 0:
+                d[key + "_ms_total"] = v.value * 1e-6
+        return d
 
     def reset_stats(self):
         _chk(load_library().mpf_reset_stats(self.h))
